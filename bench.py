@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: explanations/sec on synthetic 16 kHz 4 s clips (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1 without a launcher: this script starts the N ranks itself (child processes through
         `python -m torch.distributed.run`, before anything touches the GPU) and relays rank 0's JSON line;
         under torchrun (WORLD_SIZE set) it is one of the ranks.
@@ -13,20 +13,27 @@ batches (utterances shard with no data-path collective, "weak" scaling); the onl
 fixed-order gather of the per-clip probabilities for the LMAC metrics, done once inside the timed
 region.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, `--warmup` steps, `--steps` timed steps, the JSON line.
+`--dump-outputs DIR` writes what the last timed step computed (the three probability vectors, the mask and the LMAC metrics
+of the timed steps) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.  Everything
+else described below (the second precision, the rooflines, the CPU baseline and the other workloads' keys) runs only
+with `--full`.
+
 Precision: the headline runs the fp32-class mode (`"dtype": "f32"`: split-format operands, three fp16 MFMAs per
 product, fp32 accumulate -- the arithmetic class of the fp32 reference; its matrix peak is 2.5 PFLOP/s / 3).  The
-fp16-operand mode is measured right after it and reported under `"f16"`.  `--precision f16` makes fp16 the headline.
+fp16-operand mode is measured right after it and reported under `"f16"` (`--full`).  `--precision f16` makes fp16 the headline.
 
-`roofline` is for the dominant kernel (the implicit-GEMM tile with the largest total time, csrc/gemm.hip): algorithmic
+`roofline` (`--full`) is for the dominant kernel (the implicit-GEMM tile with the largest total time, csrc/gemm.hip): algorithmic
 FLOPs of its launches / their device time, measured with HIP events recorded on the launch stream inside the timed
-steps.  `cpu_baseline` times the CPU oracle (plain torch, the reference arithmetic) on a bounded sample of the same
-workload on this host's cores (rank 0, N = 1 only).  The default N = 1 invocation also measures BASELINE config 3
+steps (a plain run records none).  `cpu_baseline` times the CPU oracle (plain torch, the reference arithmetic) on a bounded sample of the same
+workload on this host's cores (rank 0, N = 1 only).  The N = 1 `--full` invocation also measures BASELINE config 3
 (`"hifigan"`: HiFi-GAN V1, 256 x 251 mel frames), config 5's per-GPU share (`"ig"`: IntegratedGradients, 50 steps x
 16 clips, wav2vec2-large, fp32-class gradient chain; the fp16 chain under its `"f16"` sub-key), the vocoder variant of the step (`"explain_vocoder"`) and one rank's data-set loop of config 4
 through the drop-in `LMAC_metrics.run_addvisor_metrics` itself (`"dataset"`: 8 905 clips from an in-memory Dataset in pinned host memory,
 DataLoader + per-item upload + collate inside the timed region, ragged last batch) and SURVEY 8(f)'s training step (`"train"`: batch 64,
 U-Net forward / backward + LMAC-loss forward / backward + Adam through the drop-in modules, fp32-class chain; fp16 under `"f16"`) and
-appends them as extra keys; `--workload hifigan|ig|dataset|xlsr2b|train` runs one of them as the headline.
+appends them as extra keys; `--workload hifigan|ig|dataset|xlsr2b|train` runs one of them as the headline (its second precision
+with `--full` only).
 """
 import argparse
 import json
@@ -78,7 +85,15 @@ def parse_args():
     ap.add_argument("--master-port", type=int, default=0)
     ap.add_argument("--no-traffic", action="store_true",
                     help="skip the two child rocprofv3 --pmc passes that measure the dominant kernel's HBM bytes per launch")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (second precision, rooflines, HBM traffic, CPU baseline, the other workloads' "
+                         "keys); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload != "explain":
+        ap.error("--dump-outputs is implemented for the explain workload only")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -143,9 +158,9 @@ def main():
     ctx = dict(args=args, dev=dev, rank=rank, world=world, dist=dist)
 
     if args.workload == "hifigan":
-        line = hifigan_line(ctx, bench_hifigan(ctx, args.batch if args.batch != BATCH else 256, args.steps, args.warmup))
+        line = hifigan_line(ctx, bench_hifigan(ctx, args.batch if args.batch != BATCH else 256, args.steps, args.warmup, both=args.full))
     elif args.workload == "ig":
-        line = ig_line(ctx, bench_ig(ctx, 16, 160, args.precision))
+        line = ig_line(ctx, bench_ig(ctx, 16, 160, args.precision, both=args.full))
     elif args.workload == "xlsr2b":
         r = bench_xlsr2b(ctx, args.precision, args.steps if args.steps != DEFAULT_STEPS else 3, min(args.warmup, 1) or 1)
         line = {"metric": "explanations/sec (16 kHz, 4 s clips), XLS-R-2B-width embedder", "value": r["value"],
@@ -153,7 +168,7 @@ def main():
                 "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic", "config": {"workload": r["workload"]},
                 "lmac": r["lmac"], "roofline": r["roofline"], "pipeline_tflops": r["pipeline_tflops"], "cpu_baseline": None}
     elif args.workload == "train":
-        r = bench_train(ctx, args.precision, args.batch)
+        r = bench_train(ctx, args.precision, args.batch, both=args.full)
         line = {"metric": "mask-decoder training clips/sec (4 s clips, wav2vec2-base frozen)", "value": round(r["value"] * world, 1), "unit": "clips/s",
                 "n_gpus": world, "steps": r["steps"], "warmup": 2, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak",
                 "vs_baseline": None, "dtype": r["dtype"], "data": "synthetic", "config": {"workload": r["workload"]}, "f16": r.get("f16"),
@@ -173,10 +188,11 @@ def main():
 
 
 # ------------------------------------------------------------------------------------------ the explanation step
-def run_explain(ctx, precision, steps, warmup, vocoder=False, cfg=None):
+def run_explain(ctx, precision, steps, warmup, vocoder=False, cfg=None, profile=True, keep_outputs=False):
     """Time `steps` explanation steps in one precision; returns the numbers of that run.  `vocoder`: the north-star variant
     in which both resyntheses are re-rendered by the HiFi-GAN V1 vocoder (mel front end + generator, same precision as the rest
-    of the path) before the classifier re-forward."""
+    of the path) before the classifier re-forward.  `profile`: record HIP events around the GEMM launches for `roofline`.
+    `keep_outputs`: return the last timed step's outputs and the metrics as host arrays under "outputs"."""
     import torch
     from addvisor_hip import gemm as G, pipeline as P, synthetic as syn
     args, dev, rank, world, dist = ctx["args"], ctx["dev"], ctx["rank"], ctx["world"], ctx["dist"]
@@ -210,7 +226,7 @@ def run_explain(ctx, precision, steps, warmup, vocoder=False, cfg=None):
         pipe.explain(batches[i % n_batches])
     barrier()
 
-    G.PROFILE.reset(enabled=os.environ.get("ADDVISOR_BENCH_NO_EVENTS", "0") == "0")     # 1: measure the cost of the per-launch events
+    G.PROFILE.reset(enabled=profile and os.environ.get("ADDVISOR_BENCH_NO_EVENTS", "0") == "0")     # 1: measure the cost of the per-launch events
     probs = []
     t0 = time.perf_counter()
     for i in range(steps):
@@ -230,8 +246,12 @@ def run_explain(ctx, precision, steps, warmup, vocoder=False, cfg=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     res = dict(precision=precision, elapsed=elapsed, steps=steps, value=world * B * steps / elapsed, metrics=metrics,
-               flops_step=pipe.flops(B), roofline=gemm_roofline(G, precision, args.tune, committed=(cfg.hidden_size == 768 and not vocoder and B == BATCH)),
-               cfg=cfg, weights=(emb_sd, coef, icpt, unet_sd))
+               flops_step=pipe.flops(B), cfg=cfg, weights=(emb_sd, coef, icpt, unet_sd),
+               roofline=gemm_roofline(G, precision, args.tune, committed=(cfg.hidden_size == 768 and not vocoder and B == BATCH)) if profile else None)
+    if keep_outputs:
+        import numpy as np
+        res["outputs"] = {k: out[k].float().cpu().numpy() for k in ("predictions", "theta_out", "masked_predictions", "mask")}
+        res["outputs"]["lmac_metrics"] = np.array([metrics[k] for k in P.METRIC_NAMES], dtype=np.float64)
     del pipe, batches
     torch.cuda.empty_cache()
     return res
@@ -320,7 +340,7 @@ def measured_traffic(kernel, precision, batch=BATCH, streams=1):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable,
-                   os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-traffic",
+                   os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--no-traffic",
                    "--precision", precision, "--batch", str(batch), "--streams", str(streams)]      # the SAME workload as the timed run
             r = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600, env=dict(os.environ, TMPDIR="/tmp"))
             vals = []
@@ -358,7 +378,10 @@ def committed_traffic(kernel):
 
 def explain_line(ctx):
     args, rank, world = ctx["args"], ctx["rank"], ctx["world"]
-    head = run_explain(ctx, args.precision, args.steps, args.warmup, vocoder=args.vocoder)
+    head = run_explain(ctx, args.precision, args.steps, args.warmup, vocoder=args.vocoder, profile=args.full,
+                       keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if "outputs" in head:
+        dump_outputs(args.dump_outputs, head["outputs"])
     B, L = args.batch, AUDIO_LENGTH * 16000
     prec_txt = {"f32": "fp32-class: split-format (hi + lo * 2^-11) operands, 3 fp16 MFMAs per product, fp32 accumulate / norms / residual",
                 "f16": "fp16 operands, fp32 accumulate / norms / residual"}
@@ -376,9 +399,11 @@ def explain_line(ctx):
                    "gflop_per_explanation": round(head["flops_step"] / B / 1e9, 1)},
         "lmac": {k: round(v, 6) for k, v in head["metrics"].items()},
         "pipeline_tflops": round(head["flops_step"] * args.steps * world / head["elapsed"] / 1e12, 1),
-        "roofline": head["roofline"],
+        **({"roofline": head["roofline"]} if args.full else {}),
         "cpu_baseline": None,
     }
+    if not args.full:
+        return line
     line["roofline_hbm"] = stft_roofline(ctx["dev"], B)        # every rank runs it (identical, a few ms): no rank leaves the others waiting
     extras = world == 1 and not args.no_extras and not args.tune and not args.vocoder
     if rank == 0 and world == 1 and not args.no_traffic and not args.tune and head["roofline"]["launches"]:
@@ -410,6 +435,25 @@ def explain_line(ctx):
         emb_sd, coef, icpt, unet_sd = head["weights"]
         line["cpu_baseline"] = cpu_baseline(cfg, emb_sd, coef, icpt, unet_sd, args.cpu_clips, L, args.cpu_threads, args.cpu_repeats)
     return line
+
+
+DUMP_BYTES = 60 * 10**6              # array data of --dump-outputs; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(d, arrays):
+    """Write `arrays` (name -> numpy array) as d/<name>.npy in float32 (float64 where it already is), smallest first.  An array
+    larger than the budget still left is replaced by a fixed, seeded sample of its flattened elements: the same positions for
+    every build and run with the same arguments."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_BYTES
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > left:
+            idx = np.random.default_rng(0).choice(a.size, left // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes
 
 
 # ------------------------------------------------------------------------------------------ the reference's own embedder shape

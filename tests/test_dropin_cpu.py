@@ -252,6 +252,27 @@ def test_bench_self_launch_starts_ranks_and_propagates_failure():
     assert r.returncode != 0 and "--gpus 2 but WORLD_SIZE=3" in (r.stdout + r.stderr)
 
 
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """`bench.py --dump-outputs`: float32 / float64 files, at most 64 MB in all; an array past the budget becomes the same seeded
+    sample of its elements on every call, the small arrays stay whole."""
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"predictions": rng.random((64, 1)).astype(np.float32), "lmac_metrics": rng.random(5),
+              "mask": rng.random(bench.DUMP_BYTES // 4 + 1000, dtype=np.float32)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["lmac_metrics.npy", "mask.npy", "predictions.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10**6
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    assert np.load(tmp_path / "a" / "lmac_metrics.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "predictions.npy"), arrays["predictions"])
+    m = np.load(tmp_path / "a" / "mask.npy")
+    assert m.size < arrays["mask"].size and np.isin(m, arrays["mask"]).all()
+
+
 def test_collate_is_lazy_and_lazy_tensors_behave(monkeypatch):
     """SURVEY.md D12 / LMAC_metrics.py:109-114: ``collate_fn`` returns the reference's 5-tuple but does no device work of its
     own -- magnitude / phase / features are computed on first use only (the fused ``run_addvisor_metrics`` never uses them)."""

@@ -32,7 +32,7 @@ per = collections.defaultdict(lambda: collections.defaultdict(list))
 for counter in ("FETCH_SIZE", "WRITE_SIZE"):
     d = os.path.join(tmp, counter)
     subprocess.run(["rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable,
-                    os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-traffic", "--precision", prec],
+                    os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--no-traffic", "--precision", prec],
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900, env=dict(os.environ, TMPDIR="/tmp"))
     for fn in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(fn)):
