@@ -480,6 +480,14 @@ typedef struct advh_taps2d_desc {
     float slope;
 } advh_taps2d_desc;
 int advh_conv_taps2d_f16(const advh_taps2d_desc* d, int C, advh_stream_t stream);
+/* The same layer in the fp32-class mode (csrc/conv_taps2d_x3.hip): X, W, out_h are split-format plane pairs, the lo plane x_lo / w_lo /
+ * o_lo elements behind the hi plane (x_lo, o_lo >= one plane of B*(H+2PH)*(W_+2PW)*C elements, w_lo >= 9*C*C, all multiples of 8);
+ * W [9][C_out][C_in] per plane (tap = kh*3 + kw); X and out_h distinct.  Three MFMAs per fragment pair in the order and K order of the x3
+ * implicit GEMM (gemm.plan_conv2d): the outputs are bit-identical to it.  C = 32: weights resident in LDS; C = 64: streamed tap by tap
+ * through an LDS ring.  Only interior positions of out_h are written (both planes' halos must already be zero).  ADVH_EUNSUPPORTED for
+ * other C.  advh_conv_taps2d_split_lds_bytes(C) = dynamic LDS per workgroup, -1 for an unsupported C.  */
+int advh_conv_taps2d_split_lds_bytes(int C);
+int advh_conv_taps2d_split(const advh_taps2d_desc* d, int C, int64_t x_lo, int64_t w_lo, int64_t o_lo, advh_stream_t stream);
 /* Last decoder stage of the U-Net as ONE line-tile launch: up1 = ConvTranspose2d(64,32,(2,1),stride (2,1)) folded into
  * d1.block.0 = Conv2d(33,32,3,padding 1) + BatchNorm + LeakyReLU (addvisor.py:53-54,78-80).
  *   Xc  coarse map  [B][Hc+2PHc][W_+2PWc][64]  fp16, zero halo (PHc, PWc >= 1)              (y2)

@@ -961,6 +961,45 @@ class Taps2dPlan:
         _lib.check(_lib.lib().advh_conv_taps2d_f16(C.byref(d), self.Cn, stream), "advh_conv_taps2d_f16")
 
 
+def taps2d_split_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, stride=(1, 1), padding=(1, 1),
+                           dilation=(1, 1)) -> bool:
+    """The layers of ``taps2d_supported`` on split-format maps: the ones ``advh_conv_taps2d_split`` takes."""
+    return (len(srcs) == 1 and srcs[0].split and dst.split
+            and taps2d_supported(srcs, dst, weight, stride=stride, padding=padding, dilation=dilation))
+
+
+class Taps2dSplitPlan:
+    """One launch of ``advh_conv_taps2d_split``: the fp32-class form of ``Taps2dPlan``, bit-identical to ``plan_conv2d``'s x3 GEMM on
+    the same maps (the weight's split planes are taken from its fp64 / fp32 value exactly as ``GemmPlan`` takes them)."""
+
+    def __init__(self, src: FMap, dst: FMap, weight: torch.Tensor, bias: Optional[torch.Tensor], *, act: str = "leaky",
+                 slope: float = 0.2, device=None):
+        assert taps2d_split_supported([src], dst, weight)
+        Cn = weight.shape[0]
+        self.Cn = Cn
+        self.w = split_planes(weight.permute(2, 3, 0, 1).reshape(9, Cn, Cn)).contiguous()      # [2][kh*3+kw][co][ci]
+        self.bias = None if bias is None else bias.to(torch.float32).contiguous()
+        if device is not None:
+            self.w = self.w.to(device)
+            self.bias = None if self.bias is None else self.bias.to(device)
+        d = Taps2dDesc()
+        d.B, d.H, d.W_, d.PH, d.PW = dst.B, dst.H, dst.W, dst.PH, dst.PW
+        d.act, d.slope = ACT[act], slope
+        self.desc = d
+        self.flops = 2.0 * dst.B * dst.H * dst.W * Cn * Cn * 9
+
+    def run(self, A0: torch.Tensor, A1=None, *, out_h: torch.Tensor, stream: Optional[int] = None):
+        d = self.desc
+        n = d.B * (d.H + 2 * d.PH) * (d.W_ + 2 * d.PW) * self.Cn
+        for t in (A0, out_h):
+            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.shape[0] == 2 and t.numel() == 2 * n
+        d.X, d.W, d.out_h = A0.data_ptr(), self.w.data_ptr(), out_h.data_ptr()
+        d.bias = self.bias.data_ptr() if self.bias is not None else None
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().advh_conv_taps2d_split(C.byref(d), self.Cn, n, self.w.stride(0), n, stream), "advh_conv_taps2d_split")
+
+
 class ResblockDesc(C.Structure):
     """Mirror of ``advh_resblock_desc`` (include/addvisor_hip.h)."""
     _fields_ = [("X", C.c_void_p), ("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),

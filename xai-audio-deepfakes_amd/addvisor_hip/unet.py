@@ -53,7 +53,8 @@ class HipUNet:
         ``precision``: "f16" | "f32" (default ``ADDVISOR_PRECISION``, i.e. f32): "f32" is the fp32-class mode -- every map a
         split-format plane pair, every convolution three MFMAs per product (``advh_gemm_desc.split``), weights folded in
         fp64 -- whose ``mask > 0.5`` index set reproduces the reference's fp32 CPU result (addvisor.py:57-60; asserted
-        against tests/golden/unet.npz).  The line-tile kernels are fp16-only, so that mode runs the implicit GEMM."""
+        against tests/golden/unet.npz).  In that mode ``line_tile`` covers the 3x3 32- / 64-channel layers only
+        (``advh_conv_taps2d_split``, bit-identical to the implicit GEMM); the other line-tile kernels are fp16-only."""
         _lib.init()
         from .embedder import default_precision
         self.precision = precision or default_precision()
@@ -61,8 +62,6 @@ class HipUNet:
             raise ValueError("precision must be 'f16' or 'f32'")
         self.split = self.precision == "f32"
         self.wdtype = torch.float64 if self.split else torch.float32
-        if self.split:
-            line_tile = False
         if line_tile is None:                                  # both default on; the environment switches are for A/B measurements
             line_tile = os.environ.get("ADDVISOR_UNET_LINE_TILE", "1") != "0"
         if fuse_up is None:
@@ -75,6 +74,18 @@ class HipUNet:
         self.head_w = self.sd["mask_head.0.weight"].float().reshape(32).contiguous().to(device)
         self.head_b = float(self.sd["mask_head.0.bias"].float().reshape(-1)[0])
         self._ws: Dict[Tuple[int, int, int], dict] = {}
+
+    def _line_tile_plan(self, srcs, dst, m, w, b, kw):
+        """The 3x3 same-geometry line-tile plan of a convolution (fp16 or split-format kernel), or None."""
+        if not self.line_tile:
+            return None
+        fs = [m[s] for s in srcs]
+        if self.split:
+            if G.taps2d_split_supported(fs, m[dst], w, **kw):
+                return G.Taps2dSplitPlan(fs[0], m[dst], w, b, slope=SLOPE, device=self.dev)
+        elif G.taps2d_supported(fs, m[dst], w, **kw):
+            return G.Taps2dPlan(fs[0], m[dst], w, b, slope=SLOPE, device=self.dev)
+        return None
 
     def _workspace(self, B: int, H: int, W: int) -> dict:
         key = (B, H, W)
@@ -104,9 +115,8 @@ class HipUNet:
             cin = sum(m[s].C for s in srcs)
             if cin != w.shape[1]:                              # d1: 33 real channels live in a 40-wide map
                 w = torch.cat([w, w.new_zeros(w.shape[0], cin - w.shape[1], *w.shape[2:])], 1)
-            if self.line_tile and G.taps2d_supported([m[s] for s in srcs], m[dst], w, **kw):
-                plan = G.Taps2dPlan(m[srcs[0]], m[dst], w, b, slope=SLOPE, device=dev)
-            else:
+            plan = self._line_tile_plan(srcs, dst, m, w, b, kw)
+            if plan is None:
                 plan = G.plan_conv2d([m[s] for s in srcs], m[dst], w, b, slope=SLOPE, device=dev, **kw)
             steps.append((plan, srcs, dst))
 
@@ -161,11 +171,10 @@ class HipUNet:
 
         def conv(srcs, dst, conv_name, bn_name, **kw):
             w, b = _fold_bn(sd, conv_name, bn_name, self.wdtype)
-            if self.line_tile and G.taps2d_supported([m[s] for s in srcs], m[dst], w, **kw):
-                plan = G.Taps2dPlan(m[srcs[0]], m[dst], w, b, slope=SLOPE, device=dev)
-            elif self.line_tile and G.conv_s21_supported([m[s] for s in srcs], m[dst], w, **kw):
+            plan = self._line_tile_plan(srcs, dst, m, w, b, kw)
+            if plan is None and self.line_tile and not self.split and G.conv_s21_supported([m[s] for s in srcs], m[dst], w, **kw):
                 plan = G.ConvS21TilePlan(m[srcs[0]], m[dst], w, b, slope=SLOPE, device=dev)
-            else:
+            if plan is None:
                 plan = G.plan_conv2d([m[s] for s in srcs], m[dst], w, b, slope=SLOPE, device=dev, **kw)
             steps.append((plan, srcs, dst))
 
@@ -176,7 +185,7 @@ class HipUNet:
         def up_block(coarse, skip, mid, dst, up_name, name, stride, coarse_C, skip_C, indicator):
             wc, bc = _fold_bn(sd, f"{name}.block.0", f"{name}.block.1", self.wdtype)
             wt, bt = sd[up_name + ".weight"].to(self.wdtype), sd[up_name + ".bias"].to(self.wdtype)
-            if self.line_tile and G.upconv_tile_supported(m[coarse], m[skip], m[mid], wt, wc, stride, indicator):
+            if self.line_tile and not self.split and G.upconv_tile_supported(m[coarse], m[skip], m[mid], wt, wc, stride, indicator):
                 plan = G.UpconvTilePlan(m[coarse], m[skip], m[mid], wt, bt, wc, bc, slope=SLOPE, device=dev)
             else:
                 plan = G.plan_upconv2d(m[coarse], m[skip], m[mid], wt, bt, wc, bc, stride=stride, coarse_C=coarse_C,
