@@ -352,6 +352,44 @@ int advh_attr_finalize(const float* g, const float* x, float* out, int mode, int
 int advh_time_mask(const float* attr, float* mask, float* wave_in, float* wave_out, const float* wave, int B, int64_t n,
                    advh_stream_t stream);
 
+/* Baseline-aware attributions (csrc/attribution_paths.hip): IntegratedGradients with a baseline and any Riemann / Gauss-Legendre
+ * rule, and GradientShap (= SmoothGrad noise tunnel over InputBaselineXGradient).  The B * S expanded rows g of one attribution
+ * are either step-major (IG: clip(g) = g % B) or clip-major (GradientShap: clip(g) = g / S); a chunk is the rows
+ * [row0, row0 + rows).  Expanded row g has the noisy input x~ = x[clip(g)] + sigma * N(seed, g, :) (no noise is generated when
+ * sigma = 0) and the baseline b = base[bidx[g]] (bidx != NULL), else base[clip(g)] (base_rows == B) or base[0]
+ * (base_rows == 1).  bidx, alpha and w hold one entry per expanded row (B * S, indexed by g); an index outside
+ * [0, base_rows) yields NaN for that row's values (the attribution's finiteness check reports it).  All rows [.][n] fp32.
+ * Determinism: the noise of (g, j) depends on (seed, g, j) only, sums run in a fixed order, no atomics.
+ *
+ * advh_attr_path_points : out[r] = b + alpha[g] * (x~ - b), g = row0 + r ([rows][n]).
+ * advh_attr_path_accumulate, one launch per chunk; each clip's rows of the chunk are added in global-row order:
+ *   mode 0 (IG, step-major)     : total[c] += w[g] * grad[r]
+ *   mode 1 (SHAP, clip-major)   : total[c] += (x~ - b) * grad[r]    (x~ recomputed from the counter, never stored)
+ *   mode 2 (SHAP, clip-major)   : total[c] += grad[r]               (multiply_by_inputs = False)
+ *   modes 1, 2 with row_sum != NULL also write row_sum[g] = sum_j (x~ - b)_j * grad[r]_j (GradientShap's per-sample delta).
+ *   finalize, row0 = 0, rows = B, grad = the accumulated total, total = the attribution written:
+ *   mode 3 : out[c] = (x[c] - b) * total[c] (IG; bidx must be NULL), row_sum[c] = sum_j out[c][j] if row_sum != NULL
+ *   mode 4 : out[c] = total[c] / S (GradientShap's mean over samples; S = 1 copies the sum).
+ * advh_philox_normal    : out[r][j] = N(seed, row0 + r, j): Philox4x32-10 (Salmon et al., SC'11), key = seed, counter =
+ *                         (j / 4, row lo 32, row hi 32, 0); u = (2 * (word >> 9) + 1) * 2^-24; Box-Muller on the word pairs
+ *                         (0, 1), (2, 3): z = sqrt(-2 ln u_a) * (cos, sin)(2 pi u_b) -- the exact noise the two kernels above add.
+ *                         raw = 1 writes word j % 4 of counter (j / 4, row) instead (its bit pattern in the fp32 slot).
+ * Replaces captum.attr.IntegratedGradients(baselines=..., method=...) and captum.attr.GradientShap (captum_saliency.py:3). */
+typedef struct advh_path_desc {
+    const float* x;        /* [B][n] inputs                                                     */
+    const float* base;     /* [base_rows][n] baselines                                          */
+    const int32_t* bidx;   /* [B * S] baseline row per expanded row, or NULL                    */
+    int64_t n;
+    uint64_t seed;
+    int B, S, base_rows;
+    int clip_major;        /* 0: step-major (IG), 1: clip-major (GradientShap)                   */
+    float sigma;           /* >= 0                                                              */
+} advh_path_desc;
+int advh_attr_path_points(const advh_path_desc* d, const float* alpha, int64_t row0, int rows, float* out, advh_stream_t stream);
+int advh_attr_path_accumulate(const advh_path_desc* d, const float* grad, const float* w, int mode, int64_t row0, int rows,
+                              float* total, float* row_sum, advh_stream_t stream);
+int advh_philox_normal(uint64_t seed, int64_t row0, int rows, int64_t n, int raw, float* out, advh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * fp32-class ("split") mode.  The reference computes the whole path in fp32 (addvisor.py:12-84,
  * transformers/models/wav2vec2/modeling_wav2vec2.py:254-802 under audioprocessor.py:69-77).  In this mode every tensor

@@ -1,13 +1,19 @@
 """Gradient attributions of the waveform -> logit classifier on the HIP backward path: the semantics of
-``captum.attr.Saliency / InputXGradient / IntegratedGradients`` as the reference calls them
-(captum_saliency.py:116-118, 131-143; Captum defaults: ``abs=True``; IG ``n_steps=50``,
-``method="gausslegendre"``, zero baseline, ``multiply_by_inputs=True``, scaled inputs concatenated step-major).
+``captum.attr.Saliency / InputXGradient / IntegratedGradients / GradientShap`` as the reference calls them
+(captum_saliency.py:3, 116-118, 131-143; Captum defaults: ``abs=True``; IG ``n_steps=50``,
+``method="gausslegendre"``, zero baseline, ``multiply_by_inputs=True``, scaled inputs concatenated step-major;
+GradientShap ``n_samples=5``, ``stdevs=0.0``, expanded inputs clip-major).
 
 IntegratedGradients is path-batched: the ``n_steps * B`` interpolation points are pushed through one
-forward + dgrad-only backward in chunks of ``internal_batch_size`` rows (whole steps per chunk).
+forward + dgrad-only backward in chunks of ``internal_batch_size`` rows (whole steps per chunk).  With a baseline (or a
+Riemann rule, ``multiply_by_inputs=False``, a convergence delta) the path points and the weighted, baseline-aware sums run
+on csrc/attribution_paths.hip; so does GradientShap, whose Gaussian input noise comes from the same counter-based generator
+(``philox_normal``) on the device.
 """
 from __future__ import annotations
 
+import ctypes as C
+import inspect
 from typing import Optional, Tuple
 
 import numpy as np
@@ -26,6 +32,122 @@ def gauss_legendre(n_steps: int) -> Tuple[np.ndarray, np.ndarray]:
     """Captum's ``gausslegendre`` rule: alphas = (1 + x) / 2, step sizes = w / 2."""
     x, w = np.polynomial.legendre.leggauss(n_steps)
     return 0.5 * (1.0 + x), 0.5 * w
+
+
+METHODS = ("gausslegendre", "riemann_left", "riemann_right", "riemann_middle", "riemann_trapezoid")
+
+
+def approximation(method: str, n_steps: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``(alphas, step_sizes)`` of Captum's ``approximation_methods`` (restated: captum is absent).  Riemann rules need
+    ``n_steps > 1``: step sizes ``1/n`` each (the first and last halved for the trapezoid), alphas ``linspace(0, 1, n)``
+    (trapezoid), ``linspace(0, 1 - 1/n, n)`` (left), ``linspace(1/(2n), 1 - 1/(2n), n)`` (middle), ``linspace(1/n, 1, n)``
+    (right)."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+    if method == "gausslegendre":
+        return gauss_legendre(n_steps)
+    n = int(n_steps)
+    if n <= 1:
+        raise ValueError("Riemann rules need n_steps > 1")
+    steps = np.full(n, 1.0 / n)
+    if method == "riemann_trapezoid":
+        steps[0] /= 2
+        steps[-1] /= 2
+        return np.linspace(0.0, 1.0, n), steps
+    lo, hi = {"riemann_left": (0.0, 1.0 - 1.0 / n), "riemann_middle": (1.0 / (2 * n), 1.0 - 1.0 / (2 * n)),
+              "riemann_right": (1.0 / n, 1.0)}[method]
+    return np.linspace(lo, hi, n), steps
+
+
+def shap_draws(seed: int, B: int, S: int, n_base: int) -> Tuple[np.ndarray, np.ndarray]:
+    """GradientShap's host-side draws for ``B`` clips x ``S`` samples, clip-major (expanded row ``b * S + s``):
+    baseline indices ``[B*S]`` int32 uniform in ``[0, n_base)``, then path coefficients ``[B*S]`` float32 uniform in
+    ``[0, 1)``, both from ``numpy.random.Generator(PCG64(seed))``.  Captum draws from its own RNG stream, which is not
+    reproduced (captum is absent); the distributions are the same."""
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    idx = rng.integers(0, n_base, size=B * S, dtype=np.int32)
+    alpha = rng.random(B * S, dtype=np.float32)
+    return idx, alpha
+
+
+def draw_seed() -> int:
+    """One 63-bit seed from torch's default CPU generator: ``torch.manual_seed`` reproduces a GradientShap run."""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+
+
+def _dims(waves) -> Tuple[int, int]:
+    if not torch.is_tensor(waves) or waves.dim() not in (1, 2):
+        raise ValueError("waves must be a [B, L] (or [L]) tensor")
+    return (1, waves.shape[0]) if waves.dim() == 1 else tuple(waves.shape)
+
+
+def _float_tensor(t, what):
+    if not torch.is_tensor(t):
+        raise ValueError(f"{what} must be a tensor")
+    if not t.is_floating_point():
+        raise ValueError(f"{what} must be a floating-point tensor, not {t.dtype}")
+    return t
+
+
+def check_ig_baselines(baselines, B: int, L: int):
+    """IntegratedGradients baselines: None (zero), a number, a ``[1, L]`` or a ``[B, L]`` floating tensor.  Returns a
+    ``[1, L]`` / ``[B, L]`` tensor (on the host for a number).  Raises ValueError before any GPU work."""
+    if baselines is None:
+        baselines = 0.0
+    if isinstance(baselines, (int, float)) and not isinstance(baselines, bool):
+        return torch.full((1, L), float(baselines))
+    b = _float_tensor(baselines, "baselines")
+    if b.dim() != 2 or b.shape[1] != L or b.shape[0] not in (1, B):
+        raise ValueError(f"baselines must be a number, [1, {L}] or [{B}, {L}]; got {list(b.shape)}")
+    return b
+
+
+def check_shap_args(baselines, B: int, L: int, n_samples: int, stdevs: float):
+    """GradientShap arguments: a ``[N_b, L]`` floating baseline distribution (N_b >= 1), ``n_samples >= 1``,
+    ``stdevs >= 0``.  Raises ValueError before any GPU work."""
+    b = _float_tensor(baselines, "baselines")
+    if b.dim() != 2 or b.shape[1] != L or b.shape[0] < 1:
+        raise ValueError(f"baselines must be [N_b, {L}]; got {list(b.shape)}")
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
+        raise ValueError("n_samples must be an integer >= 1")
+    if not isinstance(stdevs, (int, float)) or not np.isfinite(stdevs) or stdevs < 0:
+        raise ValueError("stdevs must be a finite number >= 0")
+    return b
+
+
+class PathDesc(C.Structure):
+    """Mirror of ``advh_path_desc`` (include/addvisor_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("base", C.c_void_p), ("bidx", C.c_void_p), ("n", C.c_int64), ("seed", C.c_uint64),
+                ("B", C.c_int), ("S", C.c_int), ("base_rows", C.c_int), ("clip_major", C.c_int), ("sigma", C.c_float)]
+
+
+ACC_IG, ACC_SHAP, ACC_SHAP_GRAD, FIN_IG, FIN_MEAN = range(5)          # advh_attr_path_accumulate modes
+
+
+def _desc(x, base, bidx, S, clip_major, sigma=0.0, seed=0) -> PathDesc:
+    B, L = x.shape
+    return PathDesc(x.data_ptr(), base.data_ptr(), None if bidx is None else bidx.data_ptr(), L, seed, B, S, base.shape[0],
+                    clip_major, sigma)
+
+
+def _points(d, alpha, row0, rows, out):
+    _lib.check(_lib.lib().advh_attr_path_points(C.byref(d), alpha.data_ptr(), row0, rows, out.data_ptr(), _st()),
+               "advh_attr_path_points")
+
+
+def _accumulate(d, grad, w, mode, row0, rows, total, row_sum=None):
+    _lib.check(_lib.lib().advh_attr_path_accumulate(C.byref(d), grad.data_ptr(), None if w is None else w.data_ptr(), mode, row0,
+                                                    rows, total.data_ptr(), None if row_sum is None else row_sum.data_ptr(), _st()),
+               "advh_attr_path_accumulate")
+
+
+def philox_normal(seed: int, row0: int, rows: int, n: int, device, raw: bool = False) -> torch.Tensor:
+    """``[rows, n]`` fp32 standard normals N(seed, row0 + r, j): exactly the noise GradientShap adds to expanded row g
+    (``stdevs * N(seed, g, :)``).  ``raw=True``: the Philox words instead, ``[rows, n]`` int32 (bit patterns).
+    advh_philox_normal."""
+    out = torch.empty((rows, n), dtype=torch.float32, device=device)
+    _lib.check(_lib.lib().advh_philox_normal(int(seed), row0, rows, n, int(raw), out.data_ptr(), _st()), "advh_philox_normal")
+    return out.view(torch.int32) if raw else out
 
 
 class HipAttribution:
@@ -49,6 +171,9 @@ class HipAttribution:
     def _finalize(self, g, x, mode):
         out = torch.empty_like(g)
         _lib.check(_lib.lib().advh_attr_finalize(g.data_ptr(), x.data_ptr(), out.data_ptr(), mode, g.numel(), _st()), "advh_attr_finalize")
+        return self._checked(out)
+
+    def _checked(self, out):
         # the planes between the dgrad GEMMs have fp16's exponent range: an overflow (|scaled gradient| > 65504 somewhere in the
         # chain) surfaces as inf / NaN in the input gradient and in every sum over path points.  One flag read per attribution:
         # raise instead of handing back a poisoned attribution map.
@@ -67,7 +192,117 @@ class HipAttribution:
         x = self._prep(waves)
         return self._finalize(self.input_gradient(x), x, 1)
 
-    def integrated_gradients(self, waves, n_steps: int = 50, internal_batch_size: Optional[int] = None):
+    def logits(self, waves) -> torch.Tensor:
+        """``[B]`` fp32 logits of the gradient chain's own forward (the F of the convergence deltas)."""
+        return self.eg.emb.forward(self._prep(waves), want_hidden=False)[1].view(-1)
+
+    def integrated_gradients(self, waves, n_steps: int = 50, internal_batch_size: Optional[int] = None, baselines=None,
+                             method: str = "gausslegendre", multiply_by_inputs: bool = True, return_convergence_delta: bool = False):
+        """Captum's IntegratedGradients.  ``baselines``: None (zero), a number, ``[1, L]`` or ``[B, L]``; ``method``: one of
+        ``METHODS``.  With ``return_convergence_delta`` returns ``(attr, delta)``, ``delta[b] = sum_j attr[b, j] -
+        (F(x_b) - F(base_b))`` ``[B]`` (F from one extra forward over x and the baselines).  The zero baseline with the
+        default rule and no delta runs the original zero-baseline path.  A constant clip (the alpha = 0 point of a number
+        baseline under ``riemann_left`` / ``riemann_trapezoid``) is where the classifier's per-clip normalisation has no
+        scale: its gradient can leave the chain's range, and the call then raises FloatingPointError."""
+        if baselines is None and method == "gausslegendre" and multiply_by_inputs and not return_convergence_delta:
+            return self._ig_zero(waves, n_steps, internal_batch_size)
+        B, L = _dims(waves)
+        base = check_ig_baselines(baselines, B, L)
+        alphas, steps = approximation(method, n_steps)
+        if return_convergence_delta and not multiply_by_inputs:
+            raise NotImplementedError("the convergence delta needs multiply_by_inputs=True")
+        x = self._prep(waves)
+        base = base.to(x.device, torch.float32).contiguous()
+        per = min(max(1, (internal_batch_size or 128) // B), n_steps)          # whole steps per chunk, as _ig_zero
+        npad = -(-n_steps // per) * per
+        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
+        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
+        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
+        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
+        d = _desc(x, base, None, npad, 0)
+        total = torch.zeros_like(x)
+        pts = torch.empty((per * B, L), dtype=torch.float32, device=x.device)
+        for s0 in range(0, npad, per):
+            _points(d, a_all, s0 * B, per * B, pts)
+            self.eg.forward(pts)
+            g = self.eg.backward(self.loss_scale)                               # [per*B, L], step-major
+            _accumulate(d, g, w_all, ACC_IG, s0 * B, per * B, total)
+        out = torch.empty_like(x)
+        sums = torch.empty(B, dtype=torch.float32, device=x.device) if return_convergence_delta else None
+        if multiply_by_inputs:
+            _accumulate(d, total, None, FIN_IG, 0, B, out, sums)
+        else:
+            d.S = 1                                                             # FIN_MEAN with S = 1: the sum itself
+            _accumulate(d, total, None, FIN_MEAN, 0, B, out)
+        out = self._checked(out)
+        if not return_convergence_delta:
+            return out
+        f = self.logits(torch.cat([x, base])).double()
+        fb = f[B:].expand(B) if base.shape[0] == 1 else f[B:]
+        return out, (sums.double() - (f[:B] - fb)).float()
+
+    def gradient_shap(self, waves, baselines, n_samples: int = 5, stdevs: float = 0.0, multiply_by_inputs: bool = True,
+                      return_convergence_delta: bool = False, seed: Optional[int] = None, internal_batch_size: Optional[int] = None):
+        """Captum's GradientShap (NoiseTunnel "smoothgrad" over InputBaselineXGradient): each clip is expanded to
+        ``n_samples`` rows (clip-major, row ``b * S + s``); row g draws a baseline ``base[idx[g]]`` uniformly from
+        ``baselines [N_b, L]`` (or a callable returning it, called with ``waves`` if it takes an argument), a coefficient
+        ``alpha[g] ~ U[0, 1)`` and the noisy input ``x~ = x_b + stdevs * N(seed, g, :)``; the attribution is the mean over
+        samples of ``(x~ - b) * dF/dx(b + alpha (x~ - b))`` (the gradient alone with ``multiply_by_inputs=False``).
+        ``delta`` ``[B*S]`` (clip-major): ``sum_j (x~ - b)_j dF_j - (F(x~) - F(b))`` per expanded row.
+
+        ``seed=None`` draws one from torch's default CPU generator (``draw_seed``); the host draws are ``shap_draws(seed, ...)``
+        and the noise ``philox_normal(seed, ...)``, so a seed fixes the result bit for bit.  Captum's RNG stream is not
+        reproduced (captum is absent)."""
+        B, L = _dims(waves)
+        if callable(baselines) and not torch.is_tensor(baselines):
+            baselines = baselines(waves) if inspect.signature(baselines).parameters else baselines()
+        base = check_shap_args(baselines, B, L, n_samples, stdevs)
+        if return_convergence_delta and not multiply_by_inputs:
+            raise NotImplementedError("the convergence delta needs multiply_by_inputs=True")
+        seed = draw_seed() if seed is None else int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2**64)")
+        S, nb = int(n_samples), base.shape[0]
+        idx, alpha = shap_draws(seed, B, S, nb)
+        x = self._prep(waves)
+        dev = x.device
+        base = base.to(dev, torch.float32).contiguous()
+        bidx = torch.from_numpy(idx).to(dev)
+        a_all = torch.from_numpy(alpha).to(dev)
+        R = B * S
+        chunk = min(internal_batch_size or 128, R)
+        d = _desc(x, base, bidx, S, 1, float(stdevs), seed)
+        total = torch.zeros_like(x)
+        row_sum = torch.empty(R, dtype=torch.float32, device=dev) if return_convergence_delta else None
+        # one workspace shape: a short last chunk leaves the previous chunk's (finite) points in the rows it does not use
+        pts = torch.zeros((chunk, L), dtype=torch.float32, device=dev)
+        mode = ACC_SHAP if multiply_by_inputs else ACC_SHAP_GRAD
+        for row0 in range(0, R, chunk):
+            rows = min(chunk, R - row0)
+            _points(d, a_all, row0, rows, pts)
+            self.eg.forward(pts)
+            g = self.eg.backward(self.loss_scale)                               # [chunk, L], clip-major
+            _accumulate(d, g, None, mode, row0, rows, total, row_sum)
+        out = torch.empty_like(x)
+        _accumulate(d, total, None, FIN_MEAN, 0, B, out)
+        out = self._checked(out)
+        if not return_convergence_delta:
+            return out
+        fb = self.logits(base).double()[bidx.long()]
+        if stdevs == 0:
+            fx = self.logits(x).double().repeat_interleave(S)
+        else:                                  # F(x~): x~ = 0 + 1 * (x~ - 0) exactly, through the path-point kernel
+            zero = torch.zeros((1, L), dtype=torch.float32, device=dev)
+            dn = _desc(x, zero, None, S, 1, float(stdevs), seed)
+            ones = torch.ones(R, dtype=torch.float32, device=dev)
+            fx = torch.empty(R, dtype=torch.float64, device=dev)
+            for row0 in range(0, R, chunk):
+                rows = min(chunk, R - row0)
+                _points(dn, ones, row0, rows, pts)
+                fx[row0:row0 + rows] = self.logits(pts)[:rows].double()
+        return out, (row_sum.double() - (fx - fb)).float()
+
+    def _ig_zero(self, waves, n_steps: int, internal_batch_size: Optional[int]):
         x = self._prep(waves)
         B, L = x.shape
         alphas, steps = gauss_legendre(n_steps)

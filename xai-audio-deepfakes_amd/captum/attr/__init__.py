@@ -41,18 +41,32 @@ class InputXGradient(_Method):
 class IntegratedGradients(_Method):
     def __init__(self, forward_func, multiply_by_inputs=True):
         super().__init__(forward_func)
-        if not multiply_by_inputs:
-            raise NotImplementedError("multiply_by_inputs=False")
+        self.multiply_by_inputs = multiply_by_inputs
 
     def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, n_steps=50,
                   method="gausslegendre", internal_batch_size=None, return_convergence_delta=False):
+        """Baselines: None (zero), a number, ``[1, L]`` or ``[B, L]``; methods: ``gausslegendre`` and the four Riemann
+        rules.  ``return_convergence_delta=True`` returns ``(attributions, delta [B])``."""
         self._check(inputs, target)
-        if torch.is_tensor(baselines):
-            zero = not bool(baselines.any())
-        else:
-            zero = baselines is None or (isinstance(baselines, (int, float)) and baselines == 0)
-        if not zero:
-            raise NotImplementedError("only the zero baseline (Captum's default) is built")
-        if method != "gausslegendre":
-            raise NotImplementedError("only Captum's default 'gausslegendre' rule is built")
-        return _engine(self.model).integrated_gradients(inputs, n_steps=n_steps, internal_batch_size=internal_batch_size)
+        return _engine(self.model).integrated_gradients(inputs, n_steps=n_steps, internal_batch_size=internal_batch_size,
+                                                        baselines=baselines, method=method,
+                                                        multiply_by_inputs=self.multiply_by_inputs,
+                                                        return_convergence_delta=return_convergence_delta)
+
+
+class GradientShap(_Method):
+    """Captum's GradientShap: the expected gradients of ``n_samples`` random points between a noisy input and a baseline
+    drawn from ``baselines [N_b, L]`` (or a callable returning it).  The random draws follow ``torch``'s default CPU
+    generator through one seed per call (``torch.manual_seed`` reproduces a result); Captum's own RNG stream is not
+    reproduced.  ``return_convergence_delta=True`` returns ``(attributions, delta [B * n_samples])``."""
+
+    def __init__(self, forward_func, multiply_by_inputs=True):
+        super().__init__(forward_func)
+        self.multiply_by_inputs = multiply_by_inputs
+
+    def attribute(self, inputs, baselines, n_samples=5, stdevs=0.0, target=None, additional_forward_args=None,
+                  return_convergence_delta=False):
+        self._check(inputs, target)
+        return _engine(self.model).gradient_shap(inputs, baselines, n_samples=n_samples, stdevs=stdevs,
+                                                 multiply_by_inputs=self.multiply_by_inputs,
+                                                 return_convergence_delta=return_convergence_delta)
