@@ -390,6 +390,39 @@ int advh_attr_path_accumulate(const advh_path_desc* d, const float* grad, const 
                               float* total, float* row_sum, advh_stream_t stream);
 int advh_philox_normal(uint64_t seed, int64_t row0, int rows, int64_t n, int raw, float* out, advh_stream_t stream);
 
+/* Perturbation attributions (csrc/attribution_ablation.hip): Captum's Occlusion and FeatureAblation of the [B][n] inputs x,
+ * restated (captum is absent).  K perturbations; the ablated rows are perturbation-major, row g = k * B + b (Captum's
+ * input.repeat), and F is the classifier logit.
+ *   mode 0 (Occlusion, window win, stride): K = ceil((n - win) / stride) + 1; window k covers [k * stride, min(k * stride + win,
+ *     n)) (Captum pads the window with a negative right pad, which crops the last one).  Captum asserts win <= n and
+ *     stride <= win unless win == n.
+ *   mode 1 (FeatureAblation): mask[.][t] in [0, K) is the feature index of sample t; ablation k replaces every sample of
+ *     feature k in every clip at once.
+ * Ablated row (k, b): base[b or 0][t] where sample t is in window / feature k, x[b][t] elsewhere (Captum's
+ * x * (1 - m) + base * m).  diff[k][b] = F(x)[b] - F(ablated)[k * B + b], fp32.
+ *   Occlusion:       attr[b][t] = (sum_{k = k_lo..k_hi} diff[k][b], in increasing k) / (k_hi - k_lo + 1), with
+ *                    k_lo = max(0, ceil((t - win + 1) / stride)), k_hi = min(K - 1, t / stride) -- Captum's
+ *                    total_attrib += diff * mask; weights += mask; total_attrib / weights, bit for bit for finite diffs.
+ *   FeatureAblation: attr[b][t] = diff[mask[t]][b] (a mask entry outside [0, K) yields NaN).
+ *
+ * advh_ablation_points     : out[r] = ablated row g = row0 + r ([rows][n]); rows g >= K * B copy x[g % B] (padding of a
+ *                            fixed-shape last chunk).  rows = 0 launches nothing.
+ * advh_ablation_accumulate : attr [B][n] from f0 = F(x) [B] and fk = F(ablated) [K * B]; one launch, one thread per (b, t),
+ *                            no atomics.
+ * Replaces captum.attr.Occlusion / captum.attr.FeatureAblation(model).attribute(x, ...) on the waveform -> logit classifier. */
+typedef struct advh_ablation_desc {
+    const float* x;        /* [B][n] inputs                                                     */
+    const float* base;     /* [base_rows][n] baselines, base_rows = 1 or B                       */
+    const int32_t* mask;   /* [mask_rows][n] feature index, mask_rows = 1 or B (mode 1; ignored in mode 0) */
+    int64_t n;
+    int B, base_rows, mask_rows;
+    int mode;              /* 0: Occlusion, 1: FeatureAblation                                   */
+    int win, stride;       /* mode 0 only                                                        */
+    int K;                 /* perturbations (mode 0: must equal the formula above)               */
+} advh_ablation_desc;
+int advh_ablation_points(const advh_ablation_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream);
+int advh_ablation_accumulate(const advh_ablation_desc* d, const float* f0, const float* fk, float* attr, advh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * fp32-class ("split") mode.  The reference computes the whole path in fp32 (addvisor.py:12-84,
  * transformers/models/wav2vec2/modeling_wav2vec2.py:254-802 under audioprocessor.py:69-77).  In this mode every tensor

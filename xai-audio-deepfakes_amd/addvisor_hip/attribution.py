@@ -9,6 +9,10 @@ forward + dgrad-only backward in chunks of ``internal_batch_size`` rows (whole s
 Riemann rule, ``multiply_by_inputs=False``, a convergence delta) the path points and the weighted, baseline-aware sums run
 on csrc/attribution_paths.hip; so does GradientShap, whose Gaussian input noise comes from the same counter-based generator
 (``philox_normal``) on the device.
+
+The perturbation attributions ``captum.attr.Occlusion / FeatureAblation`` need no gradient: the ablated batch is built on the
+device (csrc/attribution_ablation.hip), pushed through the classifier forward in chunks, and the logit differences are
+accumulated in Captum's order by one launch.
 """
 from __future__ import annotations
 
@@ -115,6 +119,92 @@ def check_shap_args(baselines, B: int, L: int, n_samples: int, stdevs: float):
     return b
 
 
+def occlusion_windows(L: int, win: int, stride: int) -> int:
+    """Captum's Occlusion shift count: ``K = ceil((L - win) / stride) + 1`` windows; window k covers
+    ``[k * stride, min(k * stride + win, L))``."""
+    return -(-(L - win) // stride) + 1
+
+
+def _positive_int(v, what) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+        raise ValueError(f"{what} must be an integer >= 1, not {v!r}")
+    return int(v)
+
+
+def _one_dim(v, what) -> int:
+    """An int or a 1-tuple of ints (Captum passes one shape per input dimension; the input here is ``[B, L]``)."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 1:
+            raise ValueError(f"{what} must have one entry (the time dimension), not {len(v)}")
+        v = v[0]
+    return _positive_int(v, what)
+
+
+def check_occlusion_args(L: int, window, stride=None) -> Tuple[int, int, int]:
+    """Occlusion's window and stride (an int or a 1-tuple; ``stride=None`` is 1) -> ``(win, stride, K)``.  Raises ValueError
+    before any GPU work on Captum's assertions: ``win <= L``, and ``stride <= win`` unless ``win == L``."""
+    win = _one_dim(window, "sliding_window_shapes")
+    stride = 1 if stride is None else _one_dim(stride, "strides")
+    if win > L:
+        raise ValueError(f"the occlusion window ({win}) is longer than the input ({L})")
+    if stride > win and win != L:
+        raise ValueError(f"the stride ({stride}) exceeds the window ({win}): samples between windows would be skipped")
+    return win, stride, occlusion_windows(L, win, stride)
+
+
+def check_internal_batch(internal_batch_size) -> int:
+    """Rows per forward of the perturbation attributions (default 128)."""
+    return 128 if internal_batch_size is None else _positive_int(internal_batch_size, "internal_batch_size")
+
+
+def feature_indices(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, int]:
+    """FeatureAblation's ``feature_mask``: None (every sample its own feature) or an integer ``[1, L]`` / ``[B, L]`` tensor of
+    feature ids.  Returns ``(index, K)``: ``index`` int32 on the host, same shape, the rank of each sample's id among the ids
+    present (increasing id order, so ``id - id_min`` for contiguous ids), and K the number of ids present.  Captum up to 0.7
+    also ablates the absent ids of ``[min, max]``; no sample takes their attribution, so skipping them changes nothing.  Raises
+    ValueError before any GPU work on a non-integer mask, a wrong shape or an id range wider than int32."""
+    if feature_mask is None:
+        return torch.arange(L, dtype=torch.int32)[None], L
+    if not torch.is_tensor(feature_mask):
+        raise ValueError("feature_mask must be a tensor")
+    if feature_mask.is_floating_point() or feature_mask.is_complex() or feature_mask.dtype == torch.bool:
+        raise ValueError(f"feature_mask must be an integer tensor, not {feature_mask.dtype}")
+    if feature_mask.dim() != 2 or feature_mask.shape[1] != L or feature_mask.shape[0] not in (1, B):
+        raise ValueError(f"feature_mask must be [1, {L}] or [{B}, {L}]; got {list(feature_mask.shape)}")
+    m = feature_mask.detach().to("cpu", torch.int64)
+    if int(m.max()) - int(m.min()) > 2 ** 31 - 1:
+        raise ValueError("the feature ids of feature_mask span more than the int32 range")
+    ids, index = torch.unique(m, sorted=True, return_inverse=True)
+    return index.to(torch.int32).reshape(m.shape), ids.numel()
+
+
+class AblationDesc(C.Structure):
+    """Mirror of ``advh_ablation_desc`` (include/addvisor_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("base", C.c_void_p), ("mask", C.c_void_p), ("n", C.c_int64), ("B", C.c_int),
+                ("base_rows", C.c_int), ("mask_rows", C.c_int), ("mode", C.c_int), ("win", C.c_int), ("stride", C.c_int),
+                ("K", C.c_int)]
+
+
+ABL_OCCLUSION, ABL_FEATURE = 0, 1                                      # advh_ablation_desc.mode
+
+
+def ablation_desc(x, base, mode, K, win=0, stride=0, mask=None) -> AblationDesc:
+    B, L = x.shape
+    return AblationDesc(x.data_ptr(), base.data_ptr(), None if mask is None else mask.data_ptr(), L, B, base.shape[0],
+                        0 if mask is None else mask.shape[0], mode, win, stride, K)
+
+
+def ablation_points(d: AblationDesc, row0: int, rows: int, out: torch.Tensor) -> None:
+    """Ablated rows ``[row0, row0 + rows)`` (perturbation-major, rows past ``K * B`` copy x) into ``out [rows, L]``."""
+    _lib.check(_lib.lib().advh_ablation_points(C.byref(d), row0, rows, out.data_ptr(), _st()), "advh_ablation_points")
+
+
+def ablation_accumulate(d: AblationDesc, f0: torch.Tensor, fk: torch.Tensor, attr: torch.Tensor) -> None:
+    """The attribution ``attr [B, L]`` from ``f0 = F(x) [B]`` and ``fk = F(ablated) [K * B]``."""
+    _lib.check(_lib.lib().advh_ablation_accumulate(C.byref(d), f0.data_ptr(), fk.data_ptr(), attr.data_ptr(), _st()),
+               "advh_ablation_accumulate")
+
+
 class PathDesc(C.Structure):
     """Mirror of ``advh_path_desc`` (include/addvisor_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("base", C.c_void_p), ("bidx", C.c_void_p), ("n", C.c_int64), ("seed", C.c_uint64),
@@ -173,15 +263,15 @@ class HipAttribution:
         _lib.check(_lib.lib().advh_attr_finalize(g.data_ptr(), x.data_ptr(), out.data_ptr(), mode, g.numel(), _st()), "advh_attr_finalize")
         return self._checked(out)
 
-    def _checked(self, out):
+    def _checked(self, out, what: str = "attribution", cause: Optional[str] = None):
         # the planes between the dgrad GEMMs have fp16's exponent range: an overflow (|scaled gradient| > 65504 somewhere in the
         # chain) surfaces as inf / NaN in the input gradient and in every sum over path points.  One flag read per attribution:
         # raise instead of handing back a poisoned attribution map.
         finite = bool(torch.isfinite(out).all())             # synchronises: every kernel of the chain has run
-        _lib.check_overflow("attribution")                   # fp32-class chain: saturated planes raise SplitRangeError (a FloatingPointError)
+        _lib.check_overflow(what)                            # fp32-class chain: saturated planes raise SplitRangeError (a FloatingPointError)
         if not finite:
-            raise FloatingPointError(f"non-finite attribution: the gradient chain overflowed at loss_scale={self.loss_scale:g} "
-                                     "(lower HipAttribution.loss_scale by a power of two)")
+            raise FloatingPointError(f"non-finite {what}: " + (cause or f"the gradient chain overflowed at loss_scale={self.loss_scale:g} "
+                                                                      "(lower HipAttribution.loss_scale by a power of two)"))
         return out
 
     def saliency(self, waves):
@@ -301,6 +391,53 @@ class HipAttribution:
                 _points(dn, ones, row0, rows, pts)
                 fx[row0:row0 + rows] = self.logits(pts)[:rows].double()
         return out, (row_sum.double() - (fx - fb)).float()
+
+    def occlusion(self, waves, window, stride=1, baselines=None, internal_batch_size: Optional[int] = None):
+        """Captum's Occlusion (restated: captum is absent).  ``window``, ``stride``: ints (or 1-tuples); ``baselines``: None
+        (zero), a number, ``[1, L]`` or ``[B, L]``.  ``K = occlusion_windows(L, window, stride)`` ablated rows per clip, row
+        ``k * B + b`` holding the baseline in ``[k * stride, min(k * stride + window, L))`` and x elsewhere;
+        ``diff[k, b] = F(x)[b] - F(ablated)[k, b]`` (fp32 logits) and ``attr[b, t]`` = the sum of ``diff[k, b]`` over the
+        windows k covering t, in increasing k, divided by their count -- Captum's ``total_attrib / weights``, bit for bit
+        given the same logits.  The ablated rows run through the forward ``internal_batch_size`` (default 128) at a time."""
+        B, L = _dims(waves)
+        win, stride, K = check_occlusion_args(L, window, stride)
+        base = check_ig_baselines(baselines, B, L)
+        chunk = check_internal_batch(internal_batch_size)
+        x = self._prep(waves)
+        base = base.to(x.device, torch.float32).contiguous()
+        return self._ablate(ablation_desc(x, base, ABL_OCCLUSION, K, win, stride), x, K, chunk, "occlusion")
+
+    def feature_ablation(self, waves, baselines=None, feature_mask=None, internal_batch_size: Optional[int] = None):
+        """Captum's FeatureAblation (restated: captum is absent).  ``feature_mask``: None (each sample its own feature: L
+        ablations) or an integer ``[1, L]`` / ``[B, L]`` tensor of feature ids; ``baselines`` as ``occlusion``.  Ablation k
+        replaces the samples of the k-th id present (increasing id order) by the baseline in every clip at once, and
+        ``attr[b, t] = F(x)[b] - F(ablated)[k(b, t), b]``."""
+        B, L = _dims(waves)
+        base = check_ig_baselines(baselines, B, L)
+        index, K = feature_indices(feature_mask, B, L)
+        chunk = check_internal_batch(internal_batch_size)
+        x = self._prep(waves)
+        base = base.to(x.device, torch.float32).contiguous()
+        index = index.to(x.device).contiguous()
+        return self._ablate(ablation_desc(x, base, ABL_FEATURE, K, mask=index), x, K, chunk, "feature ablation")
+
+    def _ablate(self, d: AblationDesc, x, K: int, chunk: int, what: str):
+        """The shared chunk loop: ablated rows -> forward logits -> ``fk``; then ``F(x)`` and one accumulate launch.  Every
+        chunk has ``chunk`` rows (the last one padded with copies of x), so one forward workspace serves them all."""
+        B, L = x.shape
+        R = K * B
+        chunk = min(chunk, R)
+        nchunk = -(-R // chunk)
+        emb = self.eg.emb
+        fk = torch.empty(nchunk * chunk, dtype=torch.float32, device=x.device)
+        pts = torch.empty((chunk, L), dtype=torch.float32, device=x.device)
+        for c in range(nchunk):
+            ablation_points(d, c * chunk, chunk, pts)
+            fk[c * chunk:(c + 1) * chunk] = emb.forward(pts, want_hidden=False)[1].view(-1)
+        f0 = emb.forward(x, want_hidden=False)[1].view(-1)
+        attr = torch.empty_like(x)
+        ablation_accumulate(d, f0, fk, attr)
+        return self._checked(attr, what, "a logit of the clips or of their ablations is not finite (check the inputs and baselines)")
 
     def _ig_zero(self, waves, n_steps: int, internal_batch_size: Optional[int]):
         x = self._prep(waves)

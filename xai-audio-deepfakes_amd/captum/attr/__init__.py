@@ -1,10 +1,14 @@
-"""``captum.attr``-compatible front ends (captum_saliency.py:3, 116-118, 131-135) over the HIP backward path.
+"""``captum.attr``-compatible front ends (captum_saliency.py:3, 116-118, 131-135) over the HIP kernels: the gradient methods
+(Saliency, InputXGradient, IntegratedGradients, GradientShap) on the HIP backward path, the perturbation methods (Occlusion,
+FeatureAblation) on the HIP forward with the ablated batches built on the device.
 
 ``Method(model).attribute(inputs, target=None, ...)`` expects ``model`` to be a
 ``captum_saliency.Wav2vec2LogReg`` (or anything exposing ``.hip_attribution()``): the waveform -> logit
 classifier whose frozen embedder runs on the GPU kernels.  Arbitrary ``nn.Module``s are not supported --
 there is no autograd fallback."""
 import torch
+
+from addvisor_hip import attribution as _A
 
 
 def _engine(model):
@@ -70,3 +74,46 @@ class GradientShap(_Method):
         return _engine(self.model).gradient_shap(inputs, baselines, n_samples=n_samples, stdevs=stdevs,
                                                  multiply_by_inputs=self.multiply_by_inputs,
                                                  return_convergence_delta=return_convergence_delta)
+
+
+def _perturbation_batch(inputs, target, perturbations_per_eval):
+    """Checks shared by the perturbation methods, before any GPU work (ValueError).  Returns the engine's rows per forward:
+    None (its default) for Captum's default of 1 -- the attribution does not depend on the chunking -- else
+    ``perturbations_per_eval * B``."""
+    if target is not None:
+        raise ValueError("the classifier has a single output; target must be None")
+    if not torch.is_tensor(inputs) or inputs.dim() != 2:
+        raise ValueError("inputs must be a [B, L] waveform tensor")
+    ppe = _A._positive_int(perturbations_per_eval, "perturbations_per_eval")
+    return None if ppe == 1 else ppe * inputs.shape[0]
+
+
+class Occlusion(_Method):
+    """Captum's Occlusion: windows of ``sliding_window_shapes = (win,)`` samples every ``strides`` samples (default 1) are
+    replaced by ``baselines`` (None = 0, a number, ``[1, L]`` or ``[B, L]``); ``K = ceil((L - win) / strides) + 1`` windows,
+    the last one cropped at L.  ``attr[b, t]`` is the mean over the windows covering t of ``F(x)[b] - F(occluded)[b]``,
+    summed in window order as Captum does.  Captum's assertions (``win <= L``; ``strides <= win`` unless ``win == L``) raise
+    ValueError."""
+
+    def attribute(self, inputs, sliding_window_shapes, strides=None, baselines=None, target=None, additional_forward_args=None,
+                  perturbations_per_eval=1, show_progress=False):
+        ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
+        B, L = inputs.shape
+        win, stride, _ = _A.check_occlusion_args(L, sliding_window_shapes, strides)
+        _A.check_ig_baselines(baselines, B, L)
+        return _engine(self.model).occlusion(inputs, win, stride, baselines=baselines, internal_batch_size=ibs)
+
+
+class FeatureAblation(_Method):
+    """Captum's FeatureAblation: each feature id of ``feature_mask`` (None = every sample its own feature, else an integer
+    ``[1, L]`` or ``[B, L]`` tensor) is replaced by ``baselines`` in every clip at once, and every sample of the feature gets
+    ``F(x)[b] - F(ablated)[b]``."""
+
+    def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None,
+                  perturbations_per_eval=1, show_progress=False):
+        ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
+        B, L = inputs.shape
+        _A.check_ig_baselines(baselines, B, L)
+        _A.feature_indices(feature_mask, B, L)
+        return _engine(self.model).feature_ablation(inputs, baselines=baselines, feature_mask=feature_mask,
+                                                    internal_batch_size=ibs)

@@ -9,6 +9,7 @@ import torch.nn as nn
 from addvisor_hip import pipeline as _P, runtime as _rt
 from audioprocessor import AudioProcessor
 from captum.attr import Saliency, InputXGradient, IntegratedGradients, GradientShap  # noqa: F401
+from captum.attr import Occlusion, FeatureAblation  # noqa: F401
 from classifier_embedder import TorchLogReg  # noqa: F401  (name kept for callers of the reference module)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -55,14 +56,16 @@ def extract_wavs(metadata):
     return audio_files
 
 
-def explain_waves(model, waves, method="input_x_gradient", n_steps=50):
+def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800):
     """Loop body of compute_camptum_saliency_metrics (captum_saliency.py:125-192) for a batch ``[B, L]``:
     attribution -> |attr|/max time mask -> wave*mask, wave*(1-mask) -> three classifier passes.
+    ``method="occlusion"`` occludes ``window``-sample windows every ``stride`` samples (default 100 ms / 50 ms at 16 kHz).
     Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
     attr = {"saliency": att.saliency, "input_x_gradient": att.input_x_gradient,
-            "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps)}[method](x)
+            "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
+            "occlusion": lambda w: att.occlusion(w, window, stride)}[method](x)
     _, w_rel, w_irr = att.time_mask(attr, x)
     emb = _rt.hip_embedder()
     B = x.shape[0]
