@@ -423,6 +423,49 @@ typedef struct advh_ablation_desc {
 int advh_ablation_points(const advh_ablation_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream);
 int advh_ablation_accumulate(const advh_ablation_desc* d, const float* f0, const float* fk, float* attr, advh_stream_t stream);
 
+/* Shapley attributions over feature groups (csrc/attribution_shapley.hip): Captum's ShapleyValueSampling, ShapleyValues and
+ * KernelShap of the [B][n] inputs x, restated (captum is absent).  index[.][t] in [0, K) is the feature of sample t (the rank of
+ * its id among the ids present); F is the classifier logit.  A coalition row keeps x[b][t] where the feature of t is in the
+ * coalition and base[b or 0][t] elsewhere (Captum's baseline * (1 - m) + x * m).
+ *   mode 0 (rank; ShapleyValueSampling over P drawn permutations, ShapleyValues over all K! in itertools order): rank[pl][k] is
+ *     the position of feature k in permutation p = p0 + pl of the table.  Row g = (p * K + j) * B + b keeps the features of
+ *     rank <= j: step j switches feature perm_p[j] from the baseline to x in every clip at once.
+ *       diff[p][j][b] = F(row p, j, b) - F(row p, j - 1, b), F(row p, -1, b) = F(base)[b];
+ *       attr[b][t] = (sum_p diff[p][rank_p(index[b][t])][b], in increasing p from 0.f) / P -- Captum's
+ *       total_attrib += eval_diff * mask; total_attrib / iter_count, bit for bit for finite logits.
+ *   mode 1 (presence; KernelShap): present[g][k] != 0 when row g keeps feature k.  The host fits each clip's weighted linear
+ *     regression on the logits and scatters its coefficients: attr[b][t] = coef[b][index[b][t]].
+ * A feature index outside [0, K) yields NaN (a rank outside [0, K) too, in the accumulation).
+ *
+ * advh_coalition_points   : out[r] = coalition row g = row0 + r ([rows][n]); rows past the table (rank mode: g >= (p0 + P) * K * B,
+ *                           presence mode: g >= rows) copy x[g % B] (padding of a fixed-shape last chunk).  Rank mode needs
+ *                           row0 >= p0 * K * B.  rows = 0 launches nothing.
+ * advh_shapley_accumulate : total [B][n] += the diffs of permutations [p0, p0 + np) (inside the table), fk = F(rows of those
+ *                           permutations) [np * K * B] starting at permutation p0, fbase = F(base) [B]; finalize_div > 0 then
+ *                           divides once (__fdiv_rn), 0 leaves the sum.  Rank mode only; x, base ignored.  One launch, one
+ *                           thread per (b, t), no atomics.
+ * advh_coalition_scatter  : attr [B][n] = coef [B][K] gathered through the index map; x, base and the tables ignored.
+ * Replaces captum.attr.ShapleyValueSampling / ShapleyValues / KernelShap(model).attribute(x, ...) on the waveform -> logit
+ * classifier. */
+typedef struct advh_coalition_desc {
+    const float* x;          /* [B][n] inputs                                                   */
+    const float* base;       /* [base_rows][n] baselines, base_rows = 1 or B                     */
+    const int32_t* index;    /* [index_rows][n] feature index, index_rows = 1 or B               */
+    const int32_t* rank;     /* mode 0: [P][K] rank of each feature in each permutation          */
+    const uint8_t* present;  /* mode 1: [rows][K] coalition membership of each row               */
+    int64_t n;
+    int64_t p0;              /* mode 0: the permutation the table starts at                      */
+    int64_t rows;            /* mode 1: rows of the table                                        */
+    int B, base_rows, index_rows;
+    int mode;                /* 0: rank (Shapley), 1: presence (KernelShap)                      */
+    int K;                   /* features (row length of the tables)                              */
+    int P;                   /* mode 0: permutations in the table                                */
+} advh_coalition_desc;
+int advh_coalition_points(const advh_coalition_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream);
+int advh_shapley_accumulate(const advh_coalition_desc* d, const float* fbase, const float* fk, int64_t p0, int np, float* total,
+                            float finalize_div, advh_stream_t stream);
+int advh_coalition_scatter(const advh_coalition_desc* d, const float* coef, float* attr, advh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * fp32-class ("split") mode.  The reference computes the whole path in fp32 (addvisor.py:12-84,
  * transformers/models/wav2vec2/modeling_wav2vec2.py:254-802 under audioprocessor.py:69-77).  In this mode every tensor

@@ -72,6 +72,9 @@ SIGNATURES = {
     "advh_philox_normal": (_i, [C.c_uint64, _i64, _i, _i64, _i, _p, _p]),
     "advh_ablation_points": (_i, [_p, _i64, _i, _p, _p]),
     "advh_ablation_accumulate": (_i, [_p, _p, _p, _p, _p]),
+    "advh_coalition_points": (_i, [_p, _i64, _i, _p, _p]),
+    "advh_shapley_accumulate": (_i, [_p, _p, _p, _i64, _i, _p, _f, _p]),
+    "advh_coalition_scatter": (_i, [_p, _p, _p, _p]),
     "advh_istft_masked_bwd": (_i, [_p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "advh_istft_bandswap": (_i, [_p, _p, _i, _i, _i, _p, _i64, _i64, _i, _i, _i, _i, _i, _p, _p]),
     "advh_bn_partial_count": (_i, []),

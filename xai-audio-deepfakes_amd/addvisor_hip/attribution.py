@@ -12,12 +12,18 @@ on csrc/attribution_paths.hip; so does GradientShap, whose Gaussian input noise 
 
 The perturbation attributions ``captum.attr.Occlusion / FeatureAblation`` need no gradient: the ablated batch is built on the
 device (csrc/attribution_ablation.hip), pushed through the classifier forward in chunks, and the logit differences are
-accumulated in Captum's order by one launch.
+accumulated in Captum's order by one launch.  The Shapley attributions ``captum.attr.ShapleyValueSampling / ShapleyValues /
+KernelShap`` build coalition rows the same way (csrc/attribution_shapley.hip): marginal contributions along permutations are
+accumulated on the device in Captum's order; KernelShap's per-clip weighted regression is a host float64 solve whose
+coefficients a kernel scatters back to the samples.
 """
 from __future__ import annotations
 
 import ctypes as C
 import inspect
+import itertools
+import math
+import warnings
 from typing import Optional, Tuple
 
 import numpy as np
@@ -176,6 +182,165 @@ def feature_indices(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, int]:
         raise ValueError("the feature ids of feature_mask span more than the int32 range")
     ids, index = torch.unique(m, sorted=True, return_inverse=True)
     return index.to(torch.int32).reshape(m.shape), ids.numel()
+
+
+def _nonnegative_ids(feature_mask):
+    if torch.is_tensor(feature_mask) and feature_mask.numel() and not (feature_mask.is_floating_point() or feature_mask.is_complex()
+                                                                       or feature_mask.dtype == torch.bool):
+        if int(feature_mask.min()) < 0:
+            raise ValueError("the Shapley attributions take feature ids >= 0 (Captum would leave a negative id at the baseline)")
+
+
+def shapley_feature_indices(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, int]:
+    """``feature_indices`` for ShapleyValueSampling / ShapleyValues: the K ids present in the whole mask are the features;
+    negative ids raise ValueError (Captum's Shapley methods take ids in ``[0, max]``)."""
+    _nonnegative_ids(feature_mask)
+    return feature_indices(feature_mask, B, L)
+
+
+def kernel_shap_feature_indices(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, list]:
+    """KernelShap's features, per clip (each clip is fitted on its own): returns ``(index, Ks)``, ``index`` int32 ``[1, L]`` (a
+    None or ``[1, L]`` mask: the same features in every clip) or ``[B, L]``, the rank of each sample's id among the ids present
+    in its clip, and ``Ks`` the number of those ids per clip.  Raises ValueError on negative ids or a clip with fewer than two
+    features (the regression needs two)."""
+    _nonnegative_ids(feature_mask)
+    index, K = feature_indices(feature_mask, B, L)
+    if index.shape[0] == 1:
+        Ks = [K] * B
+    else:
+        rows = [torch.unique(m, sorted=True, return_inverse=True) for m in index]
+        index = torch.stack([inv.to(torch.int32) for _, inv in rows])
+        Ks = [ids.numel() for ids, _ in rows]
+    if min(Ks) < 2:
+        raise ValueError(f"KernelShap needs at least two features per clip; feature_mask gives {min(Ks)}")
+    return index, Ks
+
+
+def check_n_samples(n_samples, least: int = 1) -> int:
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < least:
+        raise ValueError(f"n_samples must be an integer >= {least}, not {n_samples!r}")
+    return int(n_samples)
+
+
+def _check_seed(seed) -> int:
+    seed = draw_seed() if seed is None else int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2**64)")
+    return seed
+
+
+def _permutation_stream(seed: int):
+    """``rng.random((P, K))`` rows ranked, group by group: ``next_ranks(P, K)`` continues the stream, so drawing P permutations
+    at once or in groups gives the same ones."""
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    return lambda P, K: np.argsort(np.argsort(rng.random((P, K)), axis=1, kind="stable"), axis=1, kind="stable").astype(np.int32)
+
+
+def shapley_permutations(seed: int, P: int, K: int) -> np.ndarray:
+    """ShapleyValueSampling's host draws: ``P`` uniform permutations of the K features from
+    ``numpy.random.Generator(PCG64(seed))``, as an int32 rank table ``[P, K]`` (``rank[p][k]``: the step at which permutation p
+    switches feature k; the permutation itself is ``argsort(rank[p])``).  Captum draws ``torch.randperm`` from its own
+    stream, which is not reproduced; the distribution is the same."""
+    return _permutation_stream(seed)(P, K)
+
+
+def exact_permutation_stream(K: int):
+    """ShapleyValues' permutations: ``next_ranks(G)`` is the int32 rank table ``[G, K]`` of the next G of
+    ``itertools.permutations(range(K))`` (``rank[p][perm[p][j]] = j``), so the K! permutations are never held at once."""
+    perms = itertools.permutations(range(K))
+
+    def next_ranks(G):
+        p = np.array(list(itertools.islice(perms, G)), dtype=np.int32).reshape(-1, K)
+        rank = np.empty_like(p)
+        np.put_along_axis(rank, p, np.arange(K, dtype=np.int32)[None], axis=1)
+        return rank
+    return next_ranks
+
+
+def kernel_shap_probs(K: int) -> np.ndarray:
+    """The coalition size law of Captum's ``kernel_shap_perturb_generator``: ``p(k) = (K - 1) / (k (K - k))``, k = 1 .. K - 1,
+    normalised."""
+    k = np.arange(1, K, dtype=np.float64)
+    w = (K - 1) / (k * (K - k))
+    return w / w.sum()
+
+
+def kernel_shap_draws(seed: int, Ks, S: int) -> list:
+    """KernelShap's host draws: per clip (in order, one ``numpy.random.Generator(PCG64(seed))``) ``S`` binary coalitions
+    ``uint8 [S, K_b]``: all ones, all zeros, then for each further row a size k in ``[1, K_b - 1]`` drawn with
+    ``kernel_shap_probs`` and a uniform k-subset (the k smallest of K_b uniform draws).  Captum's stream is not reproduced."""
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    out = []
+    for K in Ks:
+        z = np.zeros((S, K), np.uint8)
+        z[0] = 1
+        if S > 2:
+            k = rng.choice(np.arange(1, K), size=S - 2, p=kernel_shap_probs(K))
+            order = np.argsort(np.argsort(rng.random((S - 2, K)), axis=1, kind="stable"), axis=1, kind="stable")
+            z[2:] = order < k[:, None]
+        out.append(z)
+    return out
+
+
+def kernel_shap_weights(z: np.ndarray) -> np.ndarray:
+    """Captum's ``kernel_shap_similarity_kernel`` on drawn coalitions: 1e6 for the all-zero and all-one rows, 1 otherwise (the
+    size law already carries the Shapley kernel)."""
+    n = z.sum(1)
+    return np.where((n == 0) | (n == z.shape[1]), 1e6, 1.0)
+
+
+def kernel_shap_fit(z: np.ndarray, y: np.ndarray) -> Tuple[np.ndarray, float]:
+    """One clip's weighted linear regression with intercept, as sklearn's ``LinearRegression().fit(z, y, sample_weight=w)``
+    (Captum's ``SkLearnLinearRegression``): centre z and y by their weighted means, scale the rows by sqrt(w), min-norm
+    ``lstsq`` in float64, intercept = mean(y) - mean(z) . coef.  Returns ``(coef [K] float64, intercept)``."""
+    X = z.astype(np.float64)
+    y = np.asarray(y, np.float64)
+    w = kernel_shap_weights(z)
+    xm = np.average(X, axis=0, weights=w)
+    ym = np.average(y, weights=w)
+    sw = np.sqrt(w)
+    coef = np.linalg.lstsq((X - xm) * sw[:, None], (y - ym) * sw, rcond=None)[0]
+    return coef, float(ym - xm @ coef)
+
+
+class CoalitionDesc(C.Structure):
+    """Mirror of ``advh_coalition_desc`` (include/addvisor_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("base", C.c_void_p), ("index", C.c_void_p), ("rank", C.c_void_p), ("present", C.c_void_p),
+                ("n", C.c_int64), ("p0", C.c_int64), ("rows", C.c_int64), ("B", C.c_int), ("base_rows", C.c_int),
+                ("index_rows", C.c_int), ("mode", C.c_int), ("K", C.c_int), ("P", C.c_int)]
+
+
+COAL_RANK, COAL_PRESENCE = 0, 1                                        # advh_coalition_desc.mode
+
+
+def coalition_desc(x, base, index, K, rank=None, p0=0, present=None) -> CoalitionDesc:
+    """Rank mode with ``rank [P, K]`` int32 (the table of permutations ``p0 .. p0 + P - 1``), presence mode with
+    ``present [rows, K]`` uint8."""
+    B, L = x.shape
+    mode = COAL_RANK if present is None else COAL_PRESENCE
+    return CoalitionDesc(x.data_ptr(), base.data_ptr(), index.data_ptr(), None if rank is None else rank.data_ptr(),
+                         None if present is None else present.data_ptr(), L, p0, 0 if present is None else present.shape[0], B,
+                         base.shape[0], index.shape[0], mode, K, 0 if rank is None else rank.shape[0])
+
+
+def coalition_points(d: CoalitionDesc, row0: int, rows: int, out: torch.Tensor) -> None:
+    """Coalition rows ``[row0, row0 + rows)`` (rows past the table copy x) into ``out [rows, L]``."""
+    _lib.check(_lib.lib().advh_coalition_points(C.byref(d), row0, rows, out.data_ptr(), _st()), "advh_coalition_points")
+
+
+def shapley_accumulate(d: CoalitionDesc, fbase: torch.Tensor, fk: torch.Tensor, p0: int, np_: int, total: torch.Tensor,
+                       finalize_div: float = 0.0) -> None:
+    """``total [B, L] +=`` the marginal contributions of permutations ``[p0, p0 + np_)``; ``finalize_div > 0`` divides once."""
+    _lib.check(_lib.lib().advh_shapley_accumulate(C.byref(d), fbase.data_ptr(), fk.data_ptr(), p0, np_, total.data_ptr(),
+                                                  finalize_div, _st()), "advh_shapley_accumulate")
+
+
+def coalition_scatter(d: CoalitionDesc, coef: torch.Tensor, attr: torch.Tensor) -> None:
+    """``attr[b, t] = coef[b, index[b, t]]`` (``coef [B, K]`` fp32)."""
+    _lib.check(_lib.lib().advh_coalition_scatter(C.byref(d), coef.data_ptr(), attr.data_ptr(), _st()), "advh_coalition_scatter")
+
+
+GROUP_ROWS = 1 << 16                                                   # coalition rows per permutation group (fk, rank table)
 
 
 class AblationDesc(C.Structure):
@@ -427,17 +592,130 @@ class HipAttribution:
         B, L = x.shape
         R = K * B
         chunk = min(chunk, R)
-        nchunk = -(-R // chunk)
-        emb = self.eg.emb
-        fk = torch.empty(nchunk * chunk, dtype=torch.float32, device=x.device)
         pts = torch.empty((chunk, L), dtype=torch.float32, device=x.device)
-        for c in range(nchunk):
-            ablation_points(d, c * chunk, chunk, pts)
-            fk[c * chunk:(c + 1) * chunk] = emb.forward(pts, want_hidden=False)[1].view(-1)
-        f0 = emb.forward(x, want_hidden=False)[1].view(-1)
+        fk = self._row_logits(lambda row0, out: ablation_points(d, row0, chunk, out), 0, R, pts)
+        f0 = self.eg.emb.forward(x, want_hidden=False)[1].view(-1)
         attr = torch.empty_like(x)
         ablation_accumulate(d, f0, fk, attr)
         return self._checked(attr, what, "a logit of the clips or of their ablations is not finite (check the inputs and baselines)")
+
+    def _row_logits(self, points, row0: int, R: int, pts: torch.Tensor) -> torch.Tensor:
+        """Logits of the perturbed rows ``[row0, row0 + R)``: ``points(first_row, pts)`` fills the ``[chunk, L]`` workspace, the
+        classifier forward runs on it, and the logits land in ``fk[:R]`` (``fk`` has whole chunks: the rows past ``R`` of the
+        last chunk are the kernels' padding, copies of x)."""
+        chunk = pts.shape[0]
+        nchunk = -(-R // chunk)
+        fk = torch.empty(nchunk * chunk, dtype=torch.float32, device=pts.device)
+        for c in range(nchunk):
+            points(row0 + c * chunk, pts)
+            fk[c * chunk:(c + 1) * chunk] = self.eg.emb.forward(pts, want_hidden=False)[1].view(-1)
+        return fk
+
+    def _shapley_args(self, waves, baselines, feature_mask, internal_batch_size):
+        B, L = _dims(waves)
+        base = check_ig_baselines(baselines, B, L)
+        index, K = shapley_feature_indices(feature_mask, B, L)
+        chunk = check_internal_batch(internal_batch_size)
+        return base, index, K, chunk
+
+    def shapley_value_sampling(self, waves, baselines=None, feature_mask=None, n_samples: int = 25, seed: Optional[int] = None,
+                               internal_batch_size: Optional[int] = None):
+        """Captum's ShapleyValueSampling (restated: captum is absent).  ``feature_mask``: None (each sample its own feature) or
+        an integer ``[1, L]`` / ``[B, L]`` tensor of ids >= 0; the K ids present are the features (ranked as
+        ``feature_indices`` ranks them).  ``baselines`` as ``occlusion``.  ``n_samples`` permutations are drawn on the host
+        (``shapley_permutations(seed, ...)``; ``seed=None`` draws one from torch's default CPU generator, so ``torch.manual_seed``
+        reproduces a run).  Along permutation p, step j switches feature ``perm_p[j]`` from the baseline to x in every clip at
+        once: row ``(p * K + j) * B + b``; ``diff[p][j][b] = F(row p, j) - F(row p, j - 1)`` with ``F(row p, -1) = F(base)``
+        (one forward over B rows), and ``attr[b, t] = (sum_p diff[p][rank_p(id(b, t))][b]) / n_samples``, summed in
+        increasing p from 0 in fp32 and divided once -- Captum's ``total_attrib += eval_diff * mask; total_attrib /
+        iter_count``, bit for bit given the same logits.  The rows run through the forward ``internal_batch_size`` (default 128)
+        at a time, in groups of whole permutations (``GROUP_ROWS``)."""
+        base, index, K, chunk = self._shapley_args(waves, baselines, feature_mask, internal_batch_size)
+        P = check_n_samples(n_samples)
+        draw = _permutation_stream(_check_seed(seed))
+        return self._shapley(waves, base, index, K, P, lambda G: draw(G, K), chunk)
+
+    def shapley_values(self, waves, baselines=None, feature_mask=None, internal_batch_size: Optional[int] = None):
+        """Captum's ShapleyValues: ``shapley_value_sampling`` over all K! permutations in ``itertools.permutations`` order,
+        divided by K!.  The permutations are streamed in groups; more than 10 features warn (UserWarning), as Captum does."""
+        base, index, K, chunk = self._shapley_args(waves, baselines, feature_mask, internal_batch_size)
+        if K > 10:
+            warnings.warn(f"ShapleyValues with {K} features evaluates {K}! permutations; consider ShapleyValueSampling", UserWarning)
+        return self._shapley(waves, base, index, K, math.factorial(K), exact_permutation_stream(K), chunk)
+
+    def _shapley(self, waves, base, index, K: int, P: int, draw, chunk: int):
+        """The permutation loop: groups of G whole permutations (G * K * B <= max(GROUP_ROWS, chunk) rows, at least one), each
+        ``draw(G) -> rank [G, K]``, its rows through ``_row_logits`` and one accumulate launch; the last one divides by P."""
+        x = self._prep(waves)
+        B, L = x.shape
+        dev = x.device
+        base = base.to(dev, torch.float32).contiguous()
+        index = index.to(dev).contiguous()
+        kb = K * B
+        G = max(1, min(P, max(GROUP_ROWS, chunk) // kb))
+        pts = torch.empty((min(chunk, G * kb), L), dtype=torch.float32, device=dev)
+        fbase = self.eg.emb.forward(base.expand(B, L).contiguous(), want_hidden=False)[1].view(-1)
+        total = torch.zeros_like(x)
+        for p0 in range(0, P, G):
+            g = min(G, P - p0)
+            rank = torch.from_numpy(draw(g)).to(dev)
+            d = coalition_desc(x, base, index, K, rank=rank, p0=p0)
+            fk = self._row_logits(lambda row0, out: coalition_points(d, row0, out.shape[0], out), p0 * kb, g * kb, pts)
+            shapley_accumulate(d, fbase, fk, p0, g, total, float(np.float32(P)) if p0 + g == P else 0.0)
+        return self._checked(total, "Shapley attribution", "a logit of the clips, the baselines or a coalition is not finite "
+                                                           "(check the inputs and baselines)")
+
+    def kernel_shap(self, waves, baselines=None, feature_mask=None, n_samples: int = 25, seed: Optional[int] = None,
+                    internal_batch_size: Optional[int] = None, return_input_shape: bool = True):
+        """Captum's KernelShap (restated: captum is absent).  Each clip is fitted on its own, over the ids >= 0 present in it
+        (``kernel_shap_feature_indices``; K_b >= 2): ``n_samples`` (>= 2) coalitions ``z`` are drawn on the host
+        (``kernel_shap_draws(seed, ...)``: all ones, all zeros, then sizes with the Shapley kernel's law and uniform subsets),
+        row ``s * B + b`` keeps x on the features of ``z_b[s]`` and the baseline elsewhere, and the logits are fitted by
+        ``kernel_shap_fit`` (weights 1e6 on the two end coalitions, 1 elsewhere; float64 on the host).  ``attr[b, t] =
+        coef_b[id(b, t)]`` in fp32; ``return_input_shape=False`` returns the ``[K]`` coefficients of a single clip."""
+        fit = self._kernel_shap_fit(waves, baselines, feature_mask, n_samples, seed, internal_batch_size, return_input_shape)
+        x, d, coefs = fit["x"], fit["desc"], fit["coef"]
+        B = x.shape[0]
+        if not return_input_shape:
+            return torch.from_numpy(coefs[0].astype(np.float32)).to(x.device)
+        coef = np.zeros((B, d.K), np.float32)
+        for b, c in enumerate(coefs):
+            coef[b, :c.shape[0]] = c
+        coef = torch.from_numpy(coef).to(x.device)
+        attr = torch.empty_like(x)
+        coalition_scatter(d, coef, attr)
+        return self._checked(attr, "KernelShap attribution", "a logit of the clips or of a coalition is not finite "
+                                                             "(check the inputs and baselines)")
+
+    def _kernel_shap_fit(self, waves, baselines, feature_mask, n_samples, seed, internal_batch_size, return_input_shape=True):
+        """KernelShap up to the per-clip fits: a dict with the draws ``z`` (per clip ``[S, K_b]``), the logits ``y`` ``[S, B]``
+        float64, ``coef`` (per clip ``[K_b]`` float64), ``intercept`` ``[B]``, the seed, and the device state (``x``, ``desc`` and
+        the tensors it points into)."""
+        B, L = _dims(waves)
+        base = check_ig_baselines(baselines, B, L)
+        index, Ks = kernel_shap_feature_indices(feature_mask, B, L)
+        S = check_n_samples(n_samples, 2)
+        chunk = check_internal_batch(internal_batch_size)
+        if not return_input_shape and B > 1:
+            raise ValueError("return_input_shape=False returns one clip's coefficients: pass a single clip")
+        seed = _check_seed(seed)
+        z = kernel_shap_draws(seed, Ks, S)
+        Kmax = max(Ks)
+        table = np.zeros((S * B, Kmax), np.uint8)
+        for b, zb in enumerate(z):
+            table[b::B, :Ks[b]] = zb                                                        # row s * B + b
+        x = self._prep(waves)
+        dev = x.device
+        base = base.to(dev, torch.float32).contiguous()
+        present = torch.from_numpy(table).to(dev)
+        index = index.to(dev).contiguous()
+        d = coalition_desc(x, base, index, Kmax, present=present)
+        pts = torch.empty((min(chunk, S * B), L), dtype=torch.float32, device=dev)
+        fk = self._row_logits(lambda row0, out: coalition_points(d, row0, out.shape[0], out), 0, S * B, pts)
+        y = fk[:S * B].view(S, B).double().cpu().numpy()
+        fits = [kernel_shap_fit(z[b], y[:, b]) for b in range(B)]
+        return {"x": x, "desc": d, "z": z, "y": y, "seed": seed, "coef": [c for c, _ in fits],
+                "intercept": np.array([i for _, i in fits]), "tensors": (base, present, index)}   # the desc points into them
 
     def _ig_zero(self, waves, n_steps: int, internal_batch_size: Optional[int]):
         x = self._prep(waves)

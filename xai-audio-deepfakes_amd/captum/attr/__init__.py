@@ -1,6 +1,7 @@
 """``captum.attr``-compatible front ends (captum_saliency.py:3, 116-118, 131-135) over the HIP kernels: the gradient methods
 (Saliency, InputXGradient, IntegratedGradients, GradientShap) on the HIP backward path, the perturbation methods (Occlusion,
-FeatureAblation) on the HIP forward with the ablated batches built on the device.
+FeatureAblation) and the Shapley methods (ShapleyValueSampling, ShapleyValues, KernelShap) on the HIP forward with the ablated
+or coalition batches built on the device.
 
 ``Method(model).attribute(inputs, target=None, ...)`` expects ``model`` to be a
 ``captum_saliency.Wav2vec2LogReg`` (or anything exposing ``.hip_attribution()``): the waveform -> logit
@@ -117,3 +118,54 @@ class FeatureAblation(_Method):
         _A.feature_indices(feature_mask, B, L)
         return _engine(self.model).feature_ablation(inputs, baselines=baselines, feature_mask=feature_mask,
                                                     internal_batch_size=ibs)
+
+
+def _shapley_checks(inputs, target, perturbations_per_eval, baselines, feature_mask):
+    ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
+    B, L = inputs.shape
+    _A.check_ig_baselines(baselines, B, L)
+    _A.shapley_feature_indices(feature_mask, B, L)
+    return ibs
+
+
+class ShapleyValueSampling(_Method):
+    """Captum's ShapleyValueSampling: ``n_samples`` random permutations of the features of ``feature_mask`` (None = every
+    sample its own feature, else an integer ``[1, L]`` or ``[B, L]`` tensor of ids >= 0); along each, the features are switched
+    from ``baselines`` (None = 0, a number, ``[1, L]`` or ``[B, L]``) to the input one at a time, and every sample gets the mean
+    over permutations of the logit change its feature caused.  The permutations follow ``torch``'s default CPU generator
+    through one seed per call (``torch.manual_seed`` reproduces a result); Captum's own RNG stream is not reproduced."""
+
+    def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None, n_samples=25,
+                  perturbations_per_eval=1, show_progress=False):
+        ibs = _shapley_checks(inputs, target, perturbations_per_eval, baselines, feature_mask)
+        _A.check_n_samples(n_samples)
+        return _engine(self.model).shapley_value_sampling(inputs, baselines=baselines, feature_mask=feature_mask,
+                                                          n_samples=n_samples, internal_batch_size=ibs)
+
+
+class ShapleyValues(_Method):
+    """Captum's ShapleyValues: ShapleyValueSampling over all K! permutations of the K features (a UserWarning above 10)."""
+
+    def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None,
+                  perturbations_per_eval=1, show_progress=False):
+        ibs = _shapley_checks(inputs, target, perturbations_per_eval, baselines, feature_mask)
+        return _engine(self.model).shapley_values(inputs, baselines=baselines, feature_mask=feature_mask, internal_batch_size=ibs)
+
+
+class KernelShap(_Method):
+    """Captum's KernelShap: per clip, ``n_samples`` (>= 2) coalitions of the features present in the clip (all, none, then
+    sizes drawn with the Shapley kernel's law) and a weighted linear regression of the logits on them; every sample gets its
+    feature's coefficient (``return_input_shape=False``: the ``[K]`` coefficients of a single clip).  Draws as
+    ShapleyValueSampling; the regression is solved in float64 on the host."""
+
+    def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None, n_samples=25,
+                  perturbations_per_eval=1, return_input_shape=True, show_progress=False):
+        ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
+        B, L = inputs.shape
+        _A.check_ig_baselines(baselines, B, L)
+        _A.kernel_shap_feature_indices(feature_mask, B, L)
+        _A.check_n_samples(n_samples, 2)
+        if not return_input_shape and B > 1:
+            raise ValueError("return_input_shape=False returns one clip's coefficients: pass a single clip")
+        return _engine(self.model).kernel_shap(inputs, baselines=baselines, feature_mask=feature_mask, n_samples=n_samples,
+                                               internal_batch_size=ibs, return_input_shape=return_input_shape)

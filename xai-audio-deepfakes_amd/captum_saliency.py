@@ -10,6 +10,7 @@ from addvisor_hip import pipeline as _P, runtime as _rt
 from audioprocessor import AudioProcessor
 from captum.attr import Saliency, InputXGradient, IntegratedGradients, GradientShap  # noqa: F401
 from captum.attr import Occlusion, FeatureAblation  # noqa: F401
+from captum.attr import ShapleyValueSampling, ShapleyValues, KernelShap  # noqa: F401
 from classifier_embedder import TorchLogReg  # noqa: F401  (name kept for callers of the reference module)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -56,16 +57,24 @@ def extract_wavs(metadata):
     return audio_files
 
 
+def _segments(waves, window):
+    """Feature ids of consecutive ``window``-sample segments, ``[1, L]``."""
+    return (torch.arange(waves.shape[-1], device=waves.device) // window)[None]
+
+
 def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800):
     """Loop body of compute_camptum_saliency_metrics (captum_saliency.py:125-192) for a batch ``[B, L]``:
     attribution -> |attr|/max time mask -> wave*mask, wave*(1-mask) -> three classifier passes.
-    ``method="occlusion"`` occludes ``window``-sample windows every ``stride`` samples (default 100 ms / 50 ms at 16 kHz).
+    ``method="occlusion"`` occludes ``window``-sample windows every ``stride`` samples (default 100 ms / 50 ms at 16 kHz);
+    ``method="shapley_value_sampling"`` / ``"kernel_shap"`` attribute ``window``-sample segments (default n_samples = 25).
     Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
     attr = {"saliency": att.saliency, "input_x_gradient": att.input_x_gradient,
             "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
-            "occlusion": lambda w: att.occlusion(w, window, stride)}[method](x)
+            "occlusion": lambda w: att.occlusion(w, window, stride),
+            "shapley_value_sampling": lambda w: att.shapley_value_sampling(w, feature_mask=_segments(w, window)),
+            "kernel_shap": lambda w: att.kernel_shap(w, feature_mask=_segments(w, window))}[method](x)
     _, w_rel, w_irr = att.time_mask(attr, x)
     emb = _rt.hip_embedder()
     B = x.shape[0]
