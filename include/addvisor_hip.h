@@ -475,9 +475,12 @@ int advh_coalition_scatter(const advh_coalition_desc* d, const float* coef, floa
  * direct kernels above: same arithmetic, `*_lo` = distance in ELEMENTS from a tensor's hi plane to its lo plane (both planes
  * share one addressing).  fp32 tensors (residual stream, masks, waveforms, statistics) are unchanged.                     */
 /* RANGE of the split format: hi is an fp16, so a value must satisfy |x| <= 65504 (the reference's fp32: 3.4e38).  Every kernel
- * that WRITES a split tensor saturates a larger value (hi = +-65504, lo = the clamped remainder) instead of producing inf /
- * NaN planes, and raises a sticky process-wide flag in host-mapped memory.  advh_split_overflow returns the flag (1 = some
- * kernel that has already run met an out-of-range value, +-inf included, since the last reset; a NaN passes through as NaN planes) and clears it when reset != 0; it reads
+ * that WRITES a split tensor saturates a larger value, +-inf included (hi = +-65504, lo = the clamped remainder: +-65535.98 in
+ * all), instead of producing inf / NaN planes, and raises a sticky process-wide flag in host-mapped memory.  A NaN is written
+ * as NaN planes (hi = lo = NaN) and does NOT raise the flag, also where it shares a conversion vector with an out-of-range
+ * value; in range (|x| <= 65504) the planes keep x to ~2^-22 relative (|x| < 2^-14: hi = 0, x carried by lo alone).  Every
+ * producer is held to this in tests/test_gpu_split_contract.py.  advh_split_overflow returns the flag (1 = some kernel that
+ * has already run met an out-of-range value since the last reset) and clears it when reset != 0; it reads
  * host memory only -- no synchronisation -- so a kernel still in flight is seen by a later call.  Weights are range-checked
  * on the host when they are packed.                                                                                     */
 int advh_split_overflow(int reset);
@@ -516,7 +519,7 @@ int advh_attention_bwd_split(const void* qkv, int64_t qkv_lo, const void* dctx, 
 int advh_pool_logreg_bwd_split(const float* coef, const float* dlogit, float* dh, void* dh16, int64_t dh16_lo, int B, int T, int H,
                                advh_stream_t stream);
 /* fp32 -> split format on the device: dst[i] = hi, dst[dst_lo + i] = lo of src[i], i < n (csrc/device_math.h split_f32: saturates
- * and raises the sticky range flag above 65 504).  The per-step weight refresh of the training path (train_addvisor.py:376-378
+ * and raises the sticky range flag above 65 504, NaN stays NaN unflagged; any n, the n % 4 tail converted one by one).  The per-step weight refresh of the training path (train_addvisor.py:376-378
  * steps the fp32 parameters with Adam; addvisor_hip/gemm.py GemmPlan.load_weights re-packs them).  src 16-byte aligned. */
 int advh_split_f32(const float* src, void* dst, int64_t dst_lo, int64_t n, advh_stream_t stream);
 /* dh [B][T][H] fp32 times GELU'(dact_src) (split pre-activation of the positional conv) -> split xg, rows [pad_left, pad_left+T) */

@@ -225,3 +225,79 @@ def test_stale_training_forward_is_refused(gpu_device):
     with torch.enable_grad():
         with pytest.raises(RuntimeError, match="no CPU"):
             addvisor.UNet().train()(torch.rand(1, 1, 32, 8))      # parameters on the CPU: no eager-torch path any more
+
+
+# ------------------------------------------------------------------------------------ range errors of the fp32-class LMAC step
+def _lmac_case(gpu_device, sd_edit=None, seed=81):
+    """The tiny embedder in the fp32-class mode on 1 s clips, its weights optionally edited, and one LMAC loss input."""
+    from addvisor_hip.embedder import HipEmbedder
+    from addvisor_hip.embedder_grad import EmbedderGrad
+    cfg = syn.tiny_config(False)
+    sd = {k: v.clone() for k, v in syn.embedder_weights(cfg).items()}
+    if sd_edit:
+        sd_edit(sd)
+    coef, icpt = syn.logreg_weights(cfg.hidden_size)
+    eg = EmbedderGrad(HipEmbedder(cfg, sd, coef, icpt, gpu_device, precision="f32"))
+    B, L = 2, 16000
+    _, mag, ph = spec(B, L, seed, 1)
+    gen = torch.Generator().manual_seed(seed + 1)
+    xhat = torch.rand(B, 1, 513, mag.shape[2], generator=gen)
+    cp = torch.rand(B, 1, generator=gen)
+    return cfg, sd, coef, icpt, eg, mag, ph, xhat, cp, L
+
+
+def test_lmac_forward_overflow_raises_and_keeps_the_scale(gpu_device):
+    """A forward activation past the split format's range (one encoder FFN bias entry of 1e5: the GELU'd intermediate saturates)
+    is a SplitRangeError of the FORWARD (addvisor_hip/lmac_loss.py _LMACTerms.forward): it must not be taken for a backward
+    overflow, back the loss scale off and train on clamped activations.  Afterwards the flag is clear and the next call is clean."""
+    from addvisor_hip import _lib
+    from addvisor_hip.lmac_loss import LossScaler, lmac_terms
+
+    def edit(sd):
+        sd["encoder.layers.0.feed_forward.intermediate_dense.bias"][3] = 1e5
+    _, _, _, _, eg, mag, ph, xhat, cp, L = _lmac_case(gpu_device, edit)
+    d = gpu_device
+    scaler = LossScaler(4096.0)
+    scaler.good_steps = 3
+    with torch.enable_grad():
+        m = xhat.squeeze(1).to(d).requires_grad_(True)
+        with pytest.raises(_lib.SplitRangeError, match="forward"):
+            lmac_terms(m, mag.to(d), ph.to(d), cp.to(d), eg, L, loss_scale=scaler)
+    assert scaler.scale == 4096.0 and scaler.good_steps == 3
+    torch.cuda.synchronize()
+    assert _lib.lib().advh_split_overflow(0) == 0
+    w_in, w_out = ops.istft_masked(mag.to(d), ph.to(d), xhat.squeeze(1).to(d), L, domain="linear")     # an unrelated HIP call
+    torch.cuda.synchronize()
+    _lib.check_overflow("next call")
+    assert torch.isfinite(w_in).all() and torch.isfinite(w_out).all()
+
+
+def test_lmac_backward_overflow_backs_off_the_scale(gpu_device):
+    """Control of the test above: sane weights and an initial loss scale of 2^40 overflow the fp32-class dgrad chain; the
+    LossScaler backs off (and keeps the lower scale), and the input gradient still meets the stated tolerance against autograd on
+    the oracle (1e-4 of max, cosine > 0.999999: test_lmac_loss_backward_matches_oracle_autograd)."""
+    from addvisor_hip import _lib
+    from addvisor_hip.lmac_loss import LossScaler, lmac_terms
+    cfg, sd, coef, icpt, eg, mag, ph, xhat, cp, L = _lmac_case(gpu_device)
+    torch.cuda.synchronize()
+    _lib.lib().advh_split_overflow(1)
+    wr = torch.tensor([3.0, 0.5, 3.0])
+    with torch.enable_grad():
+        xr = xhat.clone().requires_grad_(True)
+        tot_ref, losses_ref, _ = lmac_ref.lmac_loss(xr, mag, ph, cp, wr, sd, cfg, np.asarray(coef).reshape(1, -1),
+                                                    float(np.asarray(icpt).reshape(-1)[0]), audio_length=1)
+        gx_ref, = torch.autograd.grad(tot_ref, [xr])
+        d = gpu_device
+        scaler = LossScaler(2.0 ** 40)
+        m = xhat.squeeze(1).to(d).requires_grad_(True)
+        terms = lmac_terms(m, mag.to(d), ph.to(d), cp.to(d), eg, L, loss_scale=scaler)
+        (F.softplus(wr).to(d) * terms).sum().backward()
+    torch.cuda.synchronize()
+    _lib.check_overflow("after the step")
+    assert scaler.scale < 2.0 ** 40 and scaler.good_steps == 1
+    assert (terms.detach().cpu() - losses_ref.detach()).abs().max().item() < 1e-5
+    gx = m.grad.cpu()
+    err = relerr(gx, gx_ref.squeeze(1))
+    cos = F.cosine_similarity(gx.double().flatten(), gx_ref.double().flatten(), dim=0).item()
+    print(f"LMAC step from loss scale 2^40: backed off to {scaler.scale:g}; d total / d xhat max rel err {err:.3e}, cosine {cos:.8f}")
+    assert err < 1e-4 and cos > 0.999999

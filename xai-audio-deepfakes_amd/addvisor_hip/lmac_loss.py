@@ -53,38 +53,48 @@ class _LMACTerms(torch.autograd.Function):
         need = ctx.needs_input_grad[0]
         m = mask.detach().contiguous()
         w_in, w_out = ops.istft_masked(mag, phase, m, length, domain="linear", hop=hop, win=win)
-        logits, _ = eg.forward(torch.cat([w_in, w_out], 0))
+        # The forward's range check, at one definite point: the finiteness read synchronises, so every forward kernel has run
+        # and the sticky flag holds exactly the forward's overflows.  A forward overflow (saturated activations: the loss and
+        # gradients would be computed from clamped values) is an error of its own -- it never backs the loss scale off.
+        try:
+            logits, _ = eg.forward(torch.cat([w_in, w_out], 0))
+            ok_fwd = bool(torch.isfinite(logits).all())
+            _lib.check_overflow("LMAC loss forward")
+        except _lib.SplitRangeError as e:
+            torch.cuda.synchronize()
+            _lib.lib().advh_split_overflow(1)
+            msg = str(e) if str(e).startswith("LMAC loss forward") else f"LMAC loss forward: {e}"
+            raise _lib.SplitRangeError(msg) from None
+        if not ok_fwd:
+            raise FloatingPointError("LMAC loss: non-finite classifier logits in the forward pass (bad input or weights)")
         l_rel, l_irr = logits[:B].reshape(-1), logits[B:].reshape(-1)
         cp = class_pred.reshape(-1)
         bce = torch.nn.functional.binary_cross_entropy_with_logits
         terms = torch.stack([bce(l_rel, cp), bce(l_irr, 1 - cp), m.abs().mean()])
         if need:
             seed = torch.cat([torch.sigmoid(l_rel) - cp, torch.sigmoid(l_irr) - (1 - cp)]) / B
-            # One flag read per step (the only host synchronisation of the loss): an overflow shows up as inf / NaN in the input
-            # gradient.  Back the power-of-two scale off (exact), keep it for the following steps and redo this backward
-            # rather than hand a poisoned gradient to the optimiser.  A NaN that is not an overflow (bad input) fails at once
-            # when the forward logits are already non-finite.
+            # One more flag read per step (two host synchronisations in all): an overflow of the backward shows up as inf / NaN
+            # in the input gradient.  Back the power-of-two scale off (exact), keep it for the following steps and redo this
+            # backward rather than hand a poisoned gradient to the optimiser.
             def attempt():
-                """dL/d wave at the current scale and whether it is usable.  An overflow shows up as inf / NaN (fp16 chain) or
-                as the split format's sticky range flag (fp32-class chain: its planes saturate) -- possibly as a SplitRangeError
-                out of a later launch of the same chain."""
+                """dL/d wave at the current scale and whether it is usable.  The forward is known clean here, so an overflow is
+                the backward's: inf / NaN (fp16 chain) or the split format's sticky range flag (fp32-class chain: its planes
+                saturate) -- possibly as a SplitRangeError out of a later launch of the same chain."""
                 try:
                     gg = eg.backward(scaler.scale, seed=seed)               # [2B, length]
-                    flags = torch.stack([torch.isfinite(logits).all(), torch.isfinite(gg).all()]).tolist()   # ONE read for both flags (synchronises)
+                    ok_bwd = bool(torch.isfinite(gg).all())                 # synchronises
                     _lib.check_overflow("LMAC loss backward")
-                    return gg, flags[0], flags[1]
+                    return gg, ok_bwd
                 except _lib.SplitRangeError:
                     torch.cuda.synchronize()
                     _lib.lib().advh_split_overflow(1)
-                    return None, bool(torch.isfinite(logits).all()), False
+                    return None, False
 
-            g, ok_fwd, ok = attempt()
-            if not ok_fwd:
-                raise FloatingPointError("LMAC loss: non-finite classifier logits in the forward pass (bad input or weights)")
+            g, ok = attempt()
             while not ok:
                 if not scaler.backoff():
                     raise FloatingPointError(f"LMAC loss backward: non-finite input gradient at every loss scale down to {scaler.scale:g}")
-                g, _, ok = attempt()
+                g, ok = attempt()
             scaler.good()
             g_in = ops.istft_masked_bwd(g[:B], mag, phase, m, 0, domain="linear", hop=hop, win=win)
             g_out = ops.istft_masked_bwd(g[B:], mag, phase, m, 1, domain="linear", hop=hop, win=win)

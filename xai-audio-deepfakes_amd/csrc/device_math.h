@@ -38,7 +38,9 @@ __device__ __forceinline__ float gelu_fast(float x) { return 0.5f * x * (1.f + f
 // A value beyond that SATURATES (hi = +-65504, lo = the clamped remainder: x up to +-65535.98 is still exact) instead of
 // turning into inf / NaN downstream, and raises the library's sticky range flag -- one host-mapped word the device writes
 // and the host reads without synchronising (advh_split_overflow; the Python binding turns it into an error at its next call).
-// A NaN passes through as NaN planes (visible to any isfinite check downstream); +-inf saturates and raises the flag.
+// A NaN passes through as NaN planes (hi = lo = NaN, visible to any isfinite check downstream) and leaves the flag clear, also
+// when it shares a conversion vector with an out-of-range value; +-inf saturates and raises the flag.  The flag is raised iff
+// some converted value is out of range (tests/test_gpu_split_contract.py holds every producer to this).
 constexpr float SPLIT_LO_SCALE = 2048.f, SPLIT_LO_INV = 1.f / 2048.f, SPLIT_MAX = 65504.f;
 static __constant__ int* g_split_flag = nullptr;     // this translation unit's copy of the flag pointer (set by advh_init); constant
                                                      // address space: the load is scalar and never ordered against the epilogue's stores
@@ -49,13 +51,17 @@ __device__ __forceinline__ void split_f32_raw(float x, _Float16& hi, _Float16& l
     hi = h;
     lo = (_Float16)((x - (float)h) * SPLIT_LO_SCALE);
 }
-// saturating conversion + sticky flag (the rare path of the vector form below, and scalar call sites)
+// saturating conversion + sticky flag (the rare path of the vector form below, and scalar call sites).  The clamp of lo is
+// selected only for an out-of-range x: v_med3_f32 returns the min3 of its operands when one is NaN, so a clamp applied to a NaN
+// would turn it into a finite -65535.98.  `fabsf(x) > SPLIT_MAX` is false for NaN, which converts to NaN planes unflagged.
 __device__ __forceinline__ void split_f32(float x, _Float16& hi, _Float16& lo) {
-    _Float16 h = (_Float16)__builtin_amdgcn_fmed3f(x, -SPLIT_MAX, SPLIT_MAX);
+    const bool over = fabsf(x) > SPLIT_MAX;          // out of range, +-inf included
+    _Float16 h = (_Float16)(over ? copysignf(SPLIT_MAX, x) : x);
     if (fabsf(x) < 6.103515625e-05f) h = (_Float16)0.f;
     hi = h;
-    lo = (_Float16)__builtin_amdgcn_fmed3f((x - (float)h) * SPLIT_LO_SCALE, -SPLIT_MAX, SPLIT_MAX);
-    if (fabsf(x) > SPLIT_MAX) {                      // out of range: one exec-masked store on a path that is never taken in range
+    const float r = (x - (float)h) * SPLIT_LO_SCALE;
+    lo = (_Float16)(over ? __builtin_amdgcn_fmed3f(r, -SPLIT_MAX, SPLIT_MAX) : r);
+    if (over) {                                      // one exec-masked store on a path that is never taken in range
         int* f = g_split_flag;
         if (f) *(volatile int*)f = 1;
     }
@@ -63,7 +69,8 @@ __device__ __forceinline__ void split_f32(float x, _Float16& hi, _Float16& lo) {
 // VW values at once (the epilogues convert 4 or 8 consecutive channels per lane): ONE range test on max|v| in front of the
 // unchecked conversions -- ~1 extra VALU instruction per value instead of the 3-4 of a per-value clamp + test (round 3: the
 // per-value form cost 5 % of gemm_x3_kernel's launch time) -- and the saturating form only when some lane is out of range.
-// (NaN does not win a max: NaN values pass through as NaN planes, unflagged; inf is flagged and saturates.)
+// (NaN does not win a max, and split_f32 keeps NaN planes on the rare path too: NaN lanes stay NaN, unflagged; inf is flagged
+// and saturates.)
 template <int VW, typename HV>
 __device__ __forceinline__ void split_f32_vec(const float (&v)[VW], HV& hv, HV& lv) {
     float m = fabsf(v[0]);

@@ -157,14 +157,13 @@ __global__ __launch_bounds__(256, 2) void resblock_pair_x3_kernel(const advh_res
         __syncthreads();
         for (int i = tid; i < SRC; i += NTH) {                             // LeakyReLU on the joined value, re-split in place
             f16x8 hv = *(f16x8*)(xh + (size_t)i * 16), lv = *(f16x8*)(xl + (size_t)i * 16);
+            float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                float v = join_f32(hv[e], lv[e]);
-                v = v > 0.f ? v : p.slope * v;
-                _Float16 h, l;
-                split_f32(v, h, l);
-                hv[e] = h; lv[e] = l;
+                const float t = join_f32(hv[e], lv[e]);
+                v[e] = t > 0.f ? t : p.slope * t;
             }
+            split_f32_vec<8>(v, hv, lv);
             *(f16x8*)(xh + (size_t)i * 16) = hv;
             *(f16x8*)(xl + (size_t)i * 16) = lv;
         }
@@ -186,14 +185,13 @@ __global__ __launch_bounds__(256, 2) void resblock_pair_x3_kernel(const advh_res
             const int c = wv * WP + j * 16 + fr;
             const bool ok = in_clip(base - h2 + c);
             f16x8 hv, lv;
+            float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                float v = fmaf(accx[e >> 2][j][e & 3], SPLIT_LO_INV, acc[e >> 2][j][e & 3]) + b1[e];
-                v = ok ? (v > 0.f ? v : p.slope * v) : 0.f;
-                _Float16 h, l;
-                split_f32(v, h, l);
-                hv[e] = h; lv[e] = l;
+                const float t = fmaf(accx[e >> 2][j][e & 3], SPLIT_LO_INV, acc[e >> 2][j][e & 3]) + b1[e];
+                v[e] = ok ? (t > 0.f ? t : p.slope * t) : 0.f;
             }
+            split_f32_vec<8>(v, hv, lv);
             const size_t o = ((size_t)c * CH + (g ^ swz(c))) * 16;
             *(f16x8*)(xh + o) = hv;
             *(f16x8*)(xl + o) = lv;
