@@ -390,6 +390,24 @@ int advh_attr_path_accumulate(const advh_path_desc* d, const float* grad, const 
                               float* total, float* row_sum, advh_stream_t stream);
 int advh_philox_normal(uint64_t seed, int64_t row0, int rows, int64_t n, int raw, float* out, advh_stream_t stream);
 
+/* NoiseTunnel (csrc/attribution_paths.hip): Captum's SmoothGrad / SmoothGrad-squared / VarGrad over any attribution of the
+ * [B][n] inputs x, restated (captum is absent).  S samples per clip, processed in partitions of p' consecutive samples
+ * [s0, s0 + p'); a partition's rows are clip-major, row b * p' + s' (Captum's repeat_interleave), and hold
+ * x~ = x[b] + sigma * N(seed, g, :) with the global counter g = b * S + s0 + s': advh_attr_path_points with base 0 (one row),
+ * alpha 1 and clip_major = 1 writes them exactly (rows [b * S + s0, b * S + s0 + p') per clip), so the noise of a sample does
+ * not depend on the partitioning.  The wrapped method attributes those rows; a = its fp32 attribution of one row.
+ *
+ * advh_nt_fold     : sum[b][j] += a, sumsq[b][j] += a * a over the partition's p rows of clip b (attr [B * p][n], row b * p + s),
+ *                    in fp64, in increasing s, one thread per (b, j), no atomics: a fixed seed gives bit-identical sums.
+ *                    sum and sumsq ([B][n] fp64) start at zero before the first partition.
+ * advh_nt_finalize : out [B][n] fp32 from the sums over all S samples, m = sum / S, m2 = sumsq / S (fp64):
+ *                    nt_type 0 (smoothgrad) m, 1 (smoothgrad_sq) m2, 2 (vargrad) m2 - m * m (not clamped, as Captum).
+ * NaN / inf in attr propagate into the sums and the output (the caller's finiteness check reports them).  Null pointers,
+ * B, p, n or S <= 0, and an nt_type outside [0, 2] return ADVH_EINVAL before any HIP call.
+ * Replaces captum.attr.NoiseTunnel(method).attribute(x, nt_type=..., nt_samples=..., stdevs=...). */
+int advh_nt_fold(const float* attr, int B, int p, int64_t n, double* sum, double* sumsq, advh_stream_t stream);
+int advh_nt_finalize(const double* sum, const double* sumsq, int B, int64_t n, int S, int nt_type, float* out, advh_stream_t stream);
+
 /* Perturbation attributions (csrc/attribution_ablation.hip): Captum's Occlusion and FeatureAblation of the [B][n] inputs x,
  * restated (captum is absent).  K perturbations; the ablated rows are perturbation-major, row g = k * B + b (Captum's
  * input.repeat), and F is the classifier logit.

@@ -16,6 +16,10 @@ accumulated in Captum's order by one launch.  The Shapley attributions ``captum.
 KernelShap`` build coalition rows the same way (csrc/attribution_shapley.hip): marginal contributions along permutations are
 accumulated on the device in Captum's order; KernelShap's per-clip weighted regression is a host float64 solve whose
 coefficients a kernel scatters back to the samples.
+
+``captum.attr.NoiseTunnel`` wraps any of them (``noise_tunnel``): the noisy rows of each partition of samples come from the same
+counter-based generator through the path-point kernel, the wrapped method attributes them, and the first and second moments are
+folded in fp64 on the device (csrc/attribution_paths.hip).
 """
 from __future__ import annotations
 
@@ -301,6 +305,103 @@ def kernel_shap_fit(z: np.ndarray, y: np.ndarray) -> Tuple[np.ndarray, float]:
     sw = np.sqrt(w)
     coef = np.linalg.lstsq((X - xm) * sw[:, None], (y - ym) * sw, rcond=None)[0]
     return coef, float(ym - xm @ coef)
+
+
+NT_TYPES = ("smoothgrad", "smoothgrad_sq", "vargrad")                 # advh_nt_finalize's nt_type = the index
+
+
+def check_noise_tunnel_args(nt_type, nt_samples, nt_samples_batch_size=None, stdevs=1.0, target=None) -> Tuple[int, int, float]:
+    """NoiseTunnel's own arguments -> ``(S, p, stdevs)``: ``S = nt_samples >= 1``, partitions of ``p = min(S,
+    nt_samples_batch_size or S)`` samples, ``stdevs`` a finite number >= 0 (or a 1-tuple of one: the input is a single
+    tensor).  ``target`` must be None (one output).  Raises ValueError before any GPU work."""
+    if nt_type not in NT_TYPES:
+        raise ValueError(f"nt_type must be one of {NT_TYPES}, not {nt_type!r}")
+    S = _positive_int(nt_samples, "nt_samples")
+    p = S if nt_samples_batch_size is None else min(S, _positive_int(nt_samples_batch_size, "nt_samples_batch_size"))
+    if isinstance(stdevs, (tuple, list)):
+        if len(stdevs) != 1:
+            raise ValueError(f"stdevs must be a number or a 1-tuple (one input tensor), not {len(stdevs)} entries")
+        stdevs = stdevs[0]
+    if isinstance(stdevs, bool) or not isinstance(stdevs, (int, float, np.integer, np.floating)) or not np.isfinite(stdevs) \
+            or stdevs < 0:
+        raise ValueError(f"stdevs must be a finite number >= 0, not {stdevs!r}")
+    if target is not None:
+        raise ValueError("the classifier has a single output; target must be None")
+    return S, p, float(stdevs)
+
+
+def noise_tunnel_partitions(S: int, p: int) -> list:
+    """Captum's partition loop: ``S // p`` partitions of p samples, then one of ``S % p`` if non-zero, as ``[(s0, p'), ...]``."""
+    return [(s0, min(p, S - s0)) for s0 in range(0, S, p)]
+
+
+def noise_tunnel_rows(B: int, S: int, s0: int, pp: int) -> np.ndarray:
+    """The global (clip, sample) index ``g = b * S + s0 + s'`` of each row ``b * pp + s'`` of the partition ``[s0, s0 + pp)``:
+    the noise counter of the row, and its entry in ``noise_tunnel_baseline_draws``."""
+    return (np.arange(B)[:, None] * S + s0 + np.arange(pp)[None]).reshape(-1)
+
+
+def noise_tunnel_baseline_draws(seed: int, B: int, S: int, n_base: int) -> np.ndarray:
+    """``draw_baseline_from_distrib=True``: the baseline row of each (clip, sample) ``b * S + s``, drawn up front as
+    ``numpy.random.Generator(PCG64(seed)).integers(0, n_base, B * S)``.  Captum's stream is not reproduced."""
+    return np.random.Generator(np.random.PCG64(int(seed))).integers(0, n_base, B * S)
+
+
+def check_baseline_distribution(baselines, L: int):
+    """``draw_baseline_from_distrib=True`` needs ``baselines``, a floating ``[N_b, L]`` tensor (N_b >= 1)."""
+    b = _float_tensor(baselines, "baselines (draw_baseline_from_distrib=True)")
+    if b.dim() != 2 or b.shape[1] != L or b.shape[0] < 1:
+        raise ValueError(f"draw_baseline_from_distrib=True takes baselines [N_b, {L}]; got {list(b.shape)}")
+    return b
+
+
+def noise_tunnel_kwargs(kwargs: dict, B: int, pp: int, drawn_rows=None) -> dict:
+    """The wrapped method's arguments for a partition of ``pp`` samples, Captum's expansion: ``baselines`` ->
+    ``baselines[drawn_rows]`` when drawn from the distribution (``drawn_rows``: the partition's indices), else a tensor with
+    first dimension ``B > 1`` is ``repeat_interleave``d by pp; ``feature_mask`` with first dimension > 1 is
+    ``repeat_interleave``d; everything else passes unchanged."""
+    kw = dict(kwargs)
+    base = kw.get("baselines")
+    if drawn_rows is not None:
+        kw["baselines"] = base[torch.as_tensor(drawn_rows, dtype=torch.long, device=base.device)]
+    elif torch.is_tensor(base) and base.dim() >= 1 and base.shape[0] == B and B > 1:
+        kw["baselines"] = base.repeat_interleave(pp, 0)
+    mask = kw.get("feature_mask")
+    if torch.is_tensor(mask) and mask.dim() >= 1 and mask.shape[0] > 1:
+        kw["feature_mask"] = mask.repeat_interleave(pp, 0)
+    return kw
+
+
+def nt_noisy_rows(x: torch.Tensor, seed: int, S: int, s0: int, pp: int, stdevs: float, out: Optional[torch.Tensor] = None):
+    """The partition's ``[B * pp, L]`` rows ``x[b] + stdevs * N(seed, b * S + s0 + s', :)`` (row ``b * pp + s'``):
+    advh_attr_path_points with base 0 and alpha 1 (``0 + 1 * x~ = x~`` exactly), one launch per clip unless the partition
+    holds every sample (then the rows are one contiguous run)."""
+    B, L = x.shape
+    if out is None:
+        out = torch.empty((B * pp, L), dtype=torch.float32, device=x.device)
+    zero = torch.zeros((1, L), dtype=torch.float32, device=x.device)
+    ones = torch.ones(B * S, dtype=torch.float32, device=x.device)
+    d = _desc(x, zero, None, S, 1, float(stdevs), seed)
+    if pp == S:
+        _points(d, ones, 0, B * S, out)
+    else:
+        for b in range(B):
+            _points(d, ones, b * S + s0, pp, out[b * pp:(b + 1) * pp])
+    return out
+
+
+def nt_fold(attr: torch.Tensor, B: int, pp: int, total: torch.Tensor, total_sq: torch.Tensor) -> None:
+    """``total += a``, ``total_sq += a * a`` (fp64 ``[B, L]``) over the partition's attributions ``attr [B * pp, L]``."""
+    _lib.check(_lib.lib().advh_nt_fold(attr.data_ptr(), B, pp, attr.shape[1], total.data_ptr(), total_sq.data_ptr(), _st()),
+               "advh_nt_fold")
+
+
+def nt_finalize(total: torch.Tensor, total_sq: torch.Tensor, S: int, nt_type: str) -> torch.Tensor:
+    """The fp32 ``[B, L]`` NoiseTunnel attribution from the fp64 sums over S samples."""
+    out = torch.empty(total.shape, dtype=torch.float32, device=total.device)
+    _lib.check(_lib.lib().advh_nt_finalize(total.data_ptr(), total_sq.data_ptr(), total.shape[0], total.shape[1], S,
+                                           NT_TYPES.index(nt_type), out.data_ptr(), _st()), "advh_nt_finalize")
+    return out
 
 
 class CoalitionDesc(C.Structure):
@@ -716,6 +817,53 @@ class HipAttribution:
         fits = [kernel_shap_fit(z[b], y[:, b]) for b in range(B)]
         return {"x": x, "desc": d, "z": z, "y": y, "seed": seed, "coef": [c for c, _ in fits],
                 "intercept": np.array([i for _, i in fits]), "tensors": (base, present, index)}   # the desc points into them
+
+    def noise_tunnel(self, waves, attribute, nt_type: str = "smoothgrad", nt_samples: int = 5,
+                     nt_samples_batch_size: Optional[int] = None, stdevs: float = 1.0, draw_baseline_from_distrib: bool = False,
+                     seed: Optional[int] = None, return_convergence_delta: bool = False, **kwargs):
+        """Captum's NoiseTunnel (restated from Captum 0.7's ``noise_tunnel.py``: captum is absent) around ``attribute``, the
+        callable that attributes a ``[rows, L]`` batch (an engine method, or a ``captum.attr`` shim object's ``attribute``).
+        The S = ``nt_samples`` samples of each clip run in partitions of ``p = min(S, nt_samples_batch_size or S)`` (the last
+        one holds ``S mod p``); partition ``[s0, s0 + p')`` attributes ``B * p'`` rows, row ``b * p' + s'`` =
+        ``x_b + stdevs * N(seed, b * S + s0 + s', :)`` (``nt_noisy_rows``), with ``kwargs`` expanded by
+        ``noise_tunnel_kwargs``; with ``draw_baseline_from_distrib`` row (b, s) takes ``baselines[idx[b * S + s]]``
+        (``noise_tunnel_baseline_draws``).  The attributions a are folded into fp64 sums on the device (advh_nt_fold) and
+        finalized (advh_nt_finalize): ``smoothgrad`` E[a], ``smoothgrad_sq`` E[a^2], ``vargrad`` E[a^2] - E[a]^2.
+
+        ``seed=None`` draws one from torch's default CPU generator before any wrapped call, so a wrapped method that draws its
+        own seed draws it afterwards, once per partition, and ``torch.manual_seed`` reproduces the whole call.
+        ``return_convergence_delta`` needs an ``attribute`` that takes it (IntegratedGradients, GradientShap, or a callable
+        with ``**kwargs`` that passes it on) and returns
+        ``(attr, delta)``, delta = the wrapped deltas concatenated in partition order."""
+        B, L = _dims(waves)
+        S, p, sigma = check_noise_tunnel_args(nt_type, nt_samples, nt_samples_batch_size, stdevs)
+        if return_convergence_delta:
+            params = inspect.signature(attribute).parameters
+            if "return_convergence_delta" not in params and not any(v.kind is v.VAR_KEYWORD for v in params.values()):
+                raise ValueError("return_convergence_delta=True needs a wrapped method with a convergence delta "
+                                 "(IntegratedGradients, GradientShap)")
+            kwargs["return_convergence_delta"] = True
+        dist = check_baseline_distribution(kwargs.get("baselines"), L) if draw_baseline_from_distrib else None
+        seed = _check_seed(seed)
+        idx = noise_tunnel_baseline_draws(seed, B, S, dist.shape[0]) if dist is not None else None
+        x = self._prep(waves)
+        total = torch.zeros((B, L), dtype=torch.float64, device=x.device)
+        total_sq = torch.zeros_like(total)
+        rows = torch.empty((B * p, L), dtype=torch.float32, device=x.device)
+        deltas = []
+        for s0, pp in noise_tunnel_partitions(S, p):
+            noisy = nt_noisy_rows(x, seed, S, s0, pp, sigma, rows[:B * pp])
+            drawn = idx[noise_tunnel_rows(B, S, s0, pp)] if idx is not None else None
+            res = attribute(noisy, **noise_tunnel_kwargs(kwargs, B, pp, drawn))
+            if return_convergence_delta:
+                res, delta = res
+                deltas.append(delta)
+            if not torch.is_tensor(res) or tuple(res.shape) != (B * pp, L):
+                raise ValueError(f"the wrapped method must return a [{B * pp}, {L}] attribution of the noisy rows, "
+                                 f"not {tuple(res.shape) if torch.is_tensor(res) else type(res).__name__}")
+            nt_fold(res.to(x.device, torch.float32).contiguous(), B, pp, total, total_sq)
+        out = self._checked(nt_finalize(total, total_sq, S, nt_type), "NoiseTunnel attribution")
+        return (out, torch.cat(deltas)) if return_convergence_delta else out
 
     def _ig_zero(self, waves, n_steps: int, internal_batch_size: Optional[int]):
         x = self._prep(waves)

@@ -1,7 +1,8 @@
 """``captum.attr``-compatible front ends (captum_saliency.py:3, 116-118, 131-135) over the HIP kernels: the gradient methods
 (Saliency, InputXGradient, IntegratedGradients, GradientShap) on the HIP backward path, the perturbation methods (Occlusion,
 FeatureAblation) and the Shapley methods (ShapleyValueSampling, ShapleyValues, KernelShap) on the HIP forward with the ablated
-or coalition batches built on the device.
+or coalition batches built on the device; NoiseTunnel (SmoothGrad, SmoothGrad-squared, VarGrad) around any of those nine, with
+the noisy rows and the moments on the device.
 
 ``Method(model).attribute(inputs, target=None, ...)`` expects ``model`` to be a
 ``captum_saliency.Wav2vec2LogReg`` (or anything exposing ``.hip_attribution()``): the waveform -> logit
@@ -169,3 +170,44 @@ class KernelShap(_Method):
             raise ValueError("return_input_shape=False returns one clip's coefficients: pass a single clip")
         return _engine(self.model).kernel_shap(inputs, baselines=baselines, feature_mask=feature_mask, n_samples=n_samples,
                                                internal_batch_size=ibs, return_input_shape=return_input_shape)
+
+
+_WRAPPABLE = (Saliency, InputXGradient, IntegratedGradients, GradientShap, Occlusion, FeatureAblation, ShapleyValueSampling,
+              ShapleyValues, KernelShap)
+
+
+class NoiseTunnel:
+    """Captum's NoiseTunnel, restated from Captum 0.7's ``noise_tunnel.py`` (captum is absent): the wrapped method attributes
+    ``nt_samples`` noisy copies ``x + stdevs * N(0, 1)`` of each clip, ``nt_samples_batch_size`` samples per call (Captum's
+    partitions, rows ``repeat_interleave``d), and the attributions a are reduced per element to ``smoothgrad`` E[a],
+    ``smoothgrad_sq`` E[a^2] or ``vargrad`` E[a^2] - E[a]^2.  ``baselines`` / ``feature_mask`` and the other keyword arguments
+    go to the wrapped method's ``attribute``, expanded per partition as Captum does; ``draw_baseline_from_distrib=True`` draws
+    each noisy row's baseline from ``baselines [N_b, L]``.  ``return_convergence_delta=True`` (IntegratedGradients and
+    GradientShap only) returns ``(attributions, delta)``, the wrapped deltas concatenated over partitions.  The noise and the
+    draws follow ``torch``'s default CPU generator through one seed per call, drawn before the wrapped method draws its own
+    (``torch.manual_seed`` reproduces a result); Captum's own RNG stream is not reproduced."""
+
+    def __init__(self, attribution_method):
+        if not isinstance(attribution_method, _WRAPPABLE):
+            raise TypeError("NoiseTunnel (HIP build) wraps Saliency, InputXGradient, IntegratedGradients, GradientShap, Occlusion, "
+                            f"FeatureAblation, ShapleyValueSampling, ShapleyValues or KernelShap, not {type(attribution_method).__name__}")
+        self.attribution_method = attribution_method
+        self.is_delta_supported = isinstance(attribution_method, (IntegratedGradients, GradientShap))
+
+    def has_convergence_delta(self):
+        return self.is_delta_supported
+
+    def attribute(self, inputs, nt_type="smoothgrad", nt_samples=5, nt_samples_batch_size=None, stdevs=1.0,
+                  draw_baseline_from_distrib=False, **kwargs):
+        return_convergence_delta = kwargs.pop("return_convergence_delta", False)
+        _A.check_noise_tunnel_args(nt_type, nt_samples, nt_samples_batch_size, stdevs, kwargs.pop("target", None))
+        if not torch.is_tensor(inputs) or inputs.dim() != 2:
+            raise ValueError("inputs must be a [B, L] waveform tensor")
+        if return_convergence_delta and not self.is_delta_supported:
+            raise ValueError(f"{type(self.attribution_method).__name__} has no convergence delta")
+        if draw_baseline_from_distrib:
+            _A.check_baseline_distribution(kwargs.get("baselines"), inputs.shape[1])
+        return _engine(self.attribution_method.model).noise_tunnel(
+            inputs, self.attribution_method.attribute, nt_type=nt_type, nt_samples=nt_samples,
+            nt_samples_batch_size=nt_samples_batch_size, stdevs=stdevs, draw_baseline_from_distrib=draw_baseline_from_distrib,
+            return_convergence_delta=return_convergence_delta, **kwargs)

@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from addvisor_hip import pipeline as _P, runtime as _rt
 from audioprocessor import AudioProcessor
-from captum.attr import Saliency, InputXGradient, IntegratedGradients, GradientShap  # noqa: F401
+from captum.attr import Saliency, InputXGradient, IntegratedGradients, GradientShap, NoiseTunnel  # noqa: F401
 from captum.attr import Occlusion, FeatureAblation  # noqa: F401
 from captum.attr import ShapleyValueSampling, ShapleyValues, KernelShap  # noqa: F401
 from classifier_embedder import TorchLogReg  # noqa: F401  (name kept for callers of the reference module)
@@ -62,19 +62,23 @@ def _segments(waves, window):
     return (torch.arange(waves.shape[-1], device=waves.device) // window)[None]
 
 
-def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800):
+def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5,
+                  stdevs=0.01):
     """Loop body of compute_camptum_saliency_metrics (captum_saliency.py:125-192) for a batch ``[B, L]``:
     attribution -> |attr|/max time mask -> wave*mask, wave*(1-mask) -> three classifier passes.
     ``method="occlusion"`` occludes ``window``-sample windows every ``stride`` samples (default 100 ms / 50 ms at 16 kHz);
     ``method="shapley_value_sampling"`` / ``"kernel_shap"`` attribute ``window``-sample segments (default n_samples = 25).
-    Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
+    ``nt_type`` ("smoothgrad", "smoothgrad_sq", "vargrad") wraps the method in NoiseTunnel over ``nt_samples`` noisy copies
+    of each clip; ``stdevs`` is the noise's standard deviation in waveform units (Captum's default of 1.0 would drown a
+    waveform in [-1, 1]).  Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
-    attr = {"saliency": att.saliency, "input_x_gradient": att.input_x_gradient,
-            "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
-            "occlusion": lambda w: att.occlusion(w, window, stride),
-            "shapley_value_sampling": lambda w: att.shapley_value_sampling(w, feature_mask=_segments(w, window)),
-            "kernel_shap": lambda w: att.kernel_shap(w, feature_mask=_segments(w, window))}[method](x)
+    fn = {"saliency": att.saliency, "input_x_gradient": att.input_x_gradient,
+          "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
+          "occlusion": lambda w: att.occlusion(w, window, stride),
+          "shapley_value_sampling": lambda w: att.shapley_value_sampling(w, feature_mask=_segments(w, window)),
+          "kernel_shap": lambda w: att.kernel_shap(w, feature_mask=_segments(w, window))}[method]
+    attr = fn(x) if nt_type is None else att.noise_tunnel(x, fn, nt_type=nt_type, nt_samples=nt_samples, stdevs=stdevs)
     _, w_rel, w_irr = att.time_mask(attr, x)
     emb = _rt.hip_embedder()
     B = x.shape[0]
@@ -83,15 +87,16 @@ def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=16
 
 
 def compute_camptum_saliency_metrics(model, metadata_path, target_class=None, root="LJSpeech_vocoded",
-                                     method="input_x_gradient", batch_size=8):
-    """captum_saliency.py:112-212 (name kept as in the reference); prints faithfulness and fidelity."""
+                                     method="input_x_gradient", batch_size=8, nt_type=None, nt_samples=5, stdevs=0.01):
+    """captum_saliency.py:112-212 (name kept as in the reference); prints faithfulness and fidelity.  ``nt_type`` runs the
+    masks of NoiseTunnel over ``method`` (``explain_waves``)."""
     model.eval()
     wav_paths = extract_wavs(metadata_path)
     print(f"computing saliency for {len(wav_paths)} files")
     preds, thetas, masked = [], [], []
     for i in range(0, len(wav_paths), batch_size):
         waves = torch.stack([audioprocessor.load_audio(os.path.join(root, p))[0] for p in wav_paths[i:i + batch_size]])
-        p, t, o = explain_waves(model, waves, method)
+        p, t, o = explain_waves(model, waves, method, nt_type=nt_type, nt_samples=nt_samples, stdevs=stdevs)
         preds.append(p), thetas.append(t), masked.append(o)
     predictions, theta_out, masked_predictions = torch.cat(preds), torch.cat(thetas), torch.cat(masked)
     m = _P.lmac_metrics(predictions, theta_out, masked_predictions)

@@ -1,5 +1,6 @@
 // Path points, accumulation and Gaussian noise of the baseline-aware attributions (IntegratedGradients with a baseline,
-// GradientShap): include/addvisor_hip.h, advh_attr_path_points / advh_attr_path_accumulate / advh_philox_normal.
+// GradientShap): include/addvisor_hip.h, advh_attr_path_points / advh_attr_path_accumulate / advh_philox_normal; and the
+// moments of NoiseTunnel (advh_nt_fold / advh_nt_finalize), whose noisy rows are advh_attr_path_points' x~.
 //
 // Every kernel here is elementwise or a row reduction over fp32 rows (~40 MB per 160-row chunk at 4 s, next to hundreds of
 // milliseconds of GEMMs per chunk), so they stay simple: grid-stride loops, float4 access when every row pointer is 16-byte
@@ -8,7 +9,8 @@
 // Determinism contract: the noise of element (g, j) is a pure function of (seed, g, j) -- Philox4x32-10 keyed by the seed,
 // counter (j / 4, g lo, g hi, 0), Box-Muller on the four words -- so a row's values depend on neither the grid nor the
 // chunking; each clip's rows of a chunk are added in global-row order by one thread per element, and every row sum is a
-// fixed-shape tree in one workgroup.  No atomics.
+// fixed-shape tree in one workgroup.  NoiseTunnel's fp64 moments add each element's samples in increasing sample order, one
+// thread per element.  No atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -262,6 +264,38 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(uint64_t seed, long 
     }
 }
 
+enum { NT_SMOOTHGRAD = 0, NT_SMOOTHGRAD_SQ = 1, NT_VARGRAD = 2 };
+
+// NoiseTunnel fold: element (b, j) adds the partition's p attributions a = attr[b * p + s][j], s = 0 .. p - 1 in increasing
+// order, to the running fp64 sums of a and a * a (exact: a product of two fp32 fits a double's mantissa)
+__global__ __launch_bounds__(256) void nt_fold_kernel(const float* __restrict__ attr, int B, int p, long n, double* __restrict__ sum,
+                                                      double* __restrict__ sumsq) {
+    const long total = (long)B * n;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long b = i / n, j = i - b * n;
+        const float* a = attr + b * p * n + j;
+        double s = sum[i], q = sumsq[i];
+        for (int k = 0; k < p; ++k) {
+            const double v = a[(long)k * n];
+            s = __dadd_rn(s, v);
+            q = __dadd_rn(q, __dmul_rn(v, v));
+        }
+        sum[i] = s;
+        sumsq[i] = q;
+    }
+}
+
+// NoiseTunnel finalize: m = sum / S, m2 = sumsq / S; out = m (smoothgrad), m2 (smoothgrad_sq), m2 - m * m (vargrad), each
+// operation rounded on its own in fp64, then one rounding to fp32
+__global__ __launch_bounds__(256) void nt_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq, long total,
+                                                          int S, int nt_type, float* __restrict__ out) {
+    const double dS = (double)S;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const double m = __ddiv_rn(sum[i], dS), m2 = __ddiv_rn(sumsq[i], dS);
+        out[i] = (float)(nt_type == NT_SMOOTHGRAD ? m : nt_type == NT_SMOOTHGRAD_SQ ? m2 : __dsub_rn(m2, __dmul_rn(m, m)));
+    }
+}
+
 }  // namespace advh
 
 using namespace advh;
@@ -353,5 +387,19 @@ extern "C" int advh_philox_normal(uint64_t seed, int64_t row0, int rows, int64_t
         hipLaunchKernelGGL(philox_normal_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, seed, (long)row0, rows, (long)n, raw, out);
     else
         hipLaunchKernelGGL(philox_normal_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, seed, (long)row0, rows, (long)n, raw, out);
+    return ADVH_LAUNCH_CHECK();
+}
+
+extern "C" int advh_nt_fold(const float* attr, int B, int p, int64_t n, double* sum, double* sumsq, advh_stream_t stream) {
+    if (!attr || !sum || !sumsq || B <= 0 || p <= 0 || n <= 0) return ADVH_EINVAL;
+    hipLaunchKernelGGL(nt_fold_kernel, dim3(grid_for((long)B * n)), dim3(256), 0, (hipStream_t)stream, attr, B, p, (long)n, sum, sumsq);
+    return ADVH_LAUNCH_CHECK();
+}
+
+extern "C" int advh_nt_finalize(const double* sum, const double* sumsq, int B, int64_t n, int S, int nt_type, float* out,
+                                advh_stream_t stream) {
+    if (!sum || !sumsq || !out || B <= 0 || n <= 0 || S <= 0 || nt_type < NT_SMOOTHGRAD || nt_type > NT_VARGRAD) return ADVH_EINVAL;
+    hipLaunchKernelGGL(nt_finalize_kernel, dim3(grid_for((long)B * n)), dim3(256), 0, (hipStream_t)stream, sum, sumsq, (long)B * n, S,
+                       nt_type, out);
     return ADVH_LAUNCH_CHECK();
 }
