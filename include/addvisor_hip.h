@@ -408,6 +408,52 @@ int advh_philox_normal(uint64_t seed, int64_t row0, int rows, int64_t n, int raw
 int advh_nt_fold(const float* attr, int B, int p, int64_t n, double* sum, double* sumsq, advh_stream_t stream);
 int advh_nt_finalize(const double* sum, const double* sumsq, int B, int64_t n, int S, int nt_type, float* out, advh_stream_t stream);
 
+/* Attribution metrics (csrc/attribution_metrics.hip): Captum's infidelity and sensitivity_max of the [B][n] inputs x, restated
+ * (captum is absent).  S perturbed samples per clip, processed in chunks of p consecutive samples [s0, s0 + p); a chunk's rows
+ * are clip-major, row b * p + s' (Captum's repeat_interleave), and the noise of a row comes from its global counter
+ * g = b * S + s0 + s' (the Philox words of advh_philox_normal), so a sample's row does not depend on the chunking.
+ *
+ * advh_metric_rows : rows [row0, row0 + rows) of the chunk (rr = row0 + r, clip b = rr / p) into out [rows][n], with w_k the
+ *     Philox words of counter (j / 4, g) and u = (2 * (w >> 9) + 1) * 2^-24:
+ *   mode 0 (sensitivity_max's default perturbation): out = x[b] + scale * (2u - 1)   (2u - 1 exact; dot must be NULL, mul 0)
+ *   mode 1 (infidelity's noisy perturbation):        out = x[b] - scale * N(seed, g, :)  and
+ *     dot[rr] = sum_j pert_j * attr[b][j], pert = scale * N (mul = 0) or the decorator's safe_div(x - out, x - base) (mul = 1,
+ *     base[b or 0], or x itself when base is NULL; a zero denominator divides by 1).  The perturbation is never stored.
+ *   Every product is rounded before its add or subtraction (no FMA contraction).
+ * advh_metric_row_dot : dot[r] = sum_j pert[r][j] * attr[r / p][j], r < B * p: mode 1's dot for an explicit perturbation (a
+ *     Python perturb_func), over the same fixed tree, so equal terms give equal bits.
+ * advh_infidelity_fold : one thread per clip, samples in increasing order: a = dot[b * p + s], d = f0[b] - fk[b * p + s] (fp32
+ *     logits F(x) [B] and F(x~) [B * p]); fp64 acc[b] += (a - d)^2, or (normalize) acc[3b .. 3b + 2] += (a^2, a d, d^2).
+ *     acc starts at zero before the first chunk.
+ * advh_infidelity_finalize : out[b] = acc[b] / S, or (normalize) beta = AD / (A != 0 ? A : 1) and
+ *     ((beta^2 A - 2 beta AD) + D) / S, each operation in fp64, one rounding to fp32.
+ * advh_row_norm : out[r] = ||v[r]||_ord over the row's fixed tree (fp32), ord 0: 2-norm, 1: 1-norm, 2: max norm.
+ * advh_sensitivity_fold : ratio[b * p + s] = ||e[b] - et[b * p + s]||_ord / (enorm[b] != 0 ? enorm[b] : 1), then
+ *     smax[b] = max(smax[b], ratio[...]) over s in increasing order (smax starts at zero; NaN propagates).
+ * Every row reduction is one workgroup, a fixed-shape tree, no atomics.  NaN / inf propagate into the results (the caller's
+ * finiteness check reports them).  Null pointers, non-positive sizes, rows outside the chunk, a scale that is negative, NaN or
+ * infinite, and a mode, ord or flag out of range return ADVH_EINVAL before any HIP call.
+ * Replaces captum.metrics.infidelity(...) and captum.metrics.sensitivity_max(...). */
+typedef struct advh_metric_desc {
+    const float* x;        /* [B][n] inputs                                                      */
+    const float* attr;     /* [B][n] attributions (mode 1)                                       */
+    const float* base;     /* [base_rows][n] baselines of mode 1's denominator, or NULL           */
+    int64_t n;
+    uint64_t seed;
+    int B, S, s0, p;       /* the chunk: samples [s0, s0 + p) of each clip, s0 + p <= S            */
+    int base_rows;         /* 1 or B                                                             */
+    int mode;              /* 0: uniform rows (sensitivity_max), 1: Gaussian rows + dot (infidelity) */
+    int mul;               /* mode 1: multiply_by_inputs                                         */
+    float scale;           /* mode 0: perturb_radius, mode 1: stdevs                             */
+} advh_metric_desc;
+int advh_metric_rows(const advh_metric_desc* d, int64_t row0, int rows, float* out, float* dot, advh_stream_t stream);
+int advh_metric_row_dot(const float* pert, const float* attr, int B, int p, int64_t n, float* dot, advh_stream_t stream);
+int advh_infidelity_fold(const float* dot, const float* f0, const float* fk, int B, int p, int normalize, double* acc, advh_stream_t stream);
+int advh_infidelity_finalize(const double* acc, int B, int S, int normalize, float* out, advh_stream_t stream);
+int advh_row_norm(const float* v, int rows, int64_t n, int ord, float* out, advh_stream_t stream);
+int advh_sensitivity_fold(const float* e, const float* et, const float* enorm, int B, int p, int64_t n, int ord, float* ratio,
+                          float* smax, advh_stream_t stream);
+
 /* Perturbation attributions (csrc/attribution_ablation.hip): Captum's Occlusion and FeatureAblation of the [B][n] inputs x,
  * restated (captum is absent).  K perturbations; the ablated rows are perturbation-major, row g = k * B + b (Captum's
  * input.repeat), and F is the classifier logit.

@@ -72,6 +72,12 @@ SIGNATURES = {
     "advh_philox_normal": (_i, [C.c_uint64, _i64, _i, _i64, _i, _p, _p]),
     "advh_nt_fold": (_i, [_p, _i, _i, _i64, _p, _p, _p]),
     "advh_nt_finalize": (_i, [_p, _p, _i, _i64, _i, _i, _p, _p]),
+    "advh_metric_rows": (_i, [_p, _i64, _i, _p, _p, _p]),
+    "advh_metric_row_dot": (_i, [_p, _p, _i, _i, _i64, _p, _p]),
+    "advh_infidelity_fold": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
+    "advh_infidelity_finalize": (_i, [_p, _i, _i, _i, _p, _p]),
+    "advh_row_norm": (_i, [_p, _i, _i64, _i, _p, _p]),
+    "advh_sensitivity_fold": (_i, [_p, _p, _p, _i, _i, _i64, _i, _p, _p, _p]),
     "advh_ablation_points": (_i, [_p, _i64, _i, _p, _p]),
     "advh_ablation_accumulate": (_i, [_p, _p, _p, _p, _p]),
     "advh_coalition_points": (_i, [_p, _i64, _i, _p, _p]),

@@ -20,6 +20,10 @@ coefficients a kernel scatters back to the samples.
 ``captum.attr.NoiseTunnel`` wraps any of them (``noise_tunnel``): the noisy rows of each partition of samples come from the same
 counter-based generator through the path-point kernel, the wrapped method attributes them, and the first and second moments are
 folded in fp64 on the device (csrc/attribution_paths.hip).
+
+``captum.metrics.infidelity`` / ``sensitivity_max`` score any of them (``infidelity``, ``sensitivity_max``): the perturbed rows
+of each chunk of samples come from the same counter-based generator (or a Python perturb_func), and the per-row dot products,
+norms and per-clip folds run on csrc/attribution_metrics.hip.
 """
 from __future__ import annotations
 
@@ -404,6 +408,251 @@ def nt_finalize(total: torch.Tensor, total_sq: torch.Tensor, S: int, nt_type: st
     return out
 
 
+NORM_ORDS = {"fro": 0, 2: 0, 1: 1, math.inf: 2}                       # norm_ord -> advh_row_norm's ord
+
+
+def metric_partitions(B: int, S: int, max_examples_per_batch=None) -> list:
+    """Captum's ``_divide_and_aggregate_metrics`` plan as ``[(s0, p'), ...]``: with ``m = max_examples_per_batch // B < S``,
+    ``S // m`` chunks of m samples, then one of ``S % m`` if non-zero; otherwise one chunk of S.  ``m == 0`` raises ValueError
+    (Captum asserts).  The plan of NoiseTunnel's partitions (``noise_tunnel_partitions``) with p = m."""
+    if max_examples_per_batch is None or max_examples_per_batch // B >= S:
+        return noise_tunnel_partitions(S, S)
+    m = max_examples_per_batch // B
+    if m == 0:
+        raise ValueError(f"max_examples_per_batch ({max_examples_per_batch}) must be at least the batch size ({B})")
+    return noise_tunnel_partitions(S, m)
+
+
+_NO_ATTR = object()
+
+
+def check_metric_args(inputs, n_perturb_samples, max_examples_per_batch=None, target=None, additional_forward_args=None,
+                      attributions=_NO_ATTR) -> Tuple[int, int, int, list]:
+    """The checks common to infidelity and sensitivity_max -> ``(B, L, S, plan)``: ``inputs`` a ``[B, L]`` tensor, the
+    attributions (infidelity) a tensor of its shape, ``n_perturb_samples >= 1``, ``max_examples_per_batch`` None or an integer
+    >= B, ``target`` and ``additional_forward_args`` None (one input, one output).  Raises ValueError before any GPU work."""
+    if target is not None:
+        raise ValueError("the classifier has a single output; target must be None")
+    if additional_forward_args is not None:
+        raise ValueError("the classifier takes no additional forward arguments; additional_forward_args must be None")
+    if not torch.is_tensor(inputs) or inputs.dim() != 2:
+        raise ValueError("inputs must be a [B, L] waveform tensor")
+    B, L = inputs.shape
+    if attributions is not _NO_ATTR and (not torch.is_tensor(attributions) or tuple(attributions.shape) != (B, L)):
+        raise ValueError(f"attributions must be a tensor of the inputs' shape [{B}, {L}], not "
+                         f"{list(attributions.shape) if torch.is_tensor(attributions) else type(attributions).__name__}")
+    S = _positive_int(n_perturb_samples, "n_perturb_samples")
+    if max_examples_per_batch is not None:
+        _positive_int(max_examples_per_batch, "max_examples_per_batch")
+    return B, L, S, metric_partitions(B, S, max_examples_per_batch)
+
+
+def check_norm_ord(norm_ord) -> int:
+    """sensitivity_max's ``norm_ord``: "fro" or 2, 1, inf -> advh_row_norm's ord; anything else raises ValueError."""
+    if isinstance(norm_ord, bool) or not isinstance(norm_ord, (str, int, float, np.integer, np.floating)):
+        raise ValueError(f"norm_ord must be 'fro', 2, 1 or inf, not {norm_ord!r}")
+    key = norm_ord if isinstance(norm_ord, str) else float(norm_ord)
+    if key not in NORM_ORDS:
+        raise ValueError(f"norm_ord must be 'fro', 2, 1 or inf, not {norm_ord!r}")
+    return NORM_ORDS[key]
+
+
+def _finite_scale(v, what) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+        raise ValueError(f"{what} must be a finite number >= 0, not {v!r}")
+    return float(v)
+
+
+def expand_metric_baselines(baselines, B: int, L: int, pp: int):
+    """Captum's expansion of ``baselines`` for a chunk of pp samples (infidelity's ``_generate_perturbations``,
+    ``_expand_and_update_baselines``): a ``[B, L]`` tensor with B > 1 is ``repeat_interleave``d; ``[1, L]`` tensors, numbers
+    and None pass unchanged."""
+    if torch.is_tensor(baselines) and tuple(baselines.shape) == (B, L) and B > 1:
+        return baselines.repeat_interleave(pp, 0)
+    return baselines
+
+
+def sensitivity_kwargs(kwargs: dict, B: int, L: int, pp: int) -> dict:
+    """The explanation function's keyword arguments for a chunk of pp samples: ``baselines`` expanded as
+    ``expand_metric_baselines``, everything else -- ``feature_mask`` included, unlike ``noise_tunnel_kwargs`` -- unchanged."""
+    kw = dict(kwargs)
+    if "baselines" in kw:
+        kw["baselines"] = expand_metric_baselines(kw["baselines"], B, L, pp)
+    return kw
+
+
+def _perturb_params(fn) -> int:
+    try:
+        return len(inspect.signature(fn).parameters)
+    except (TypeError, ValueError):
+        return 1
+
+
+class MetricDesc(C.Structure):
+    """Mirror of ``advh_metric_desc`` (include/addvisor_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("attr", C.c_void_p), ("base", C.c_void_p), ("n", C.c_int64), ("seed", C.c_uint64),
+                ("B", C.c_int), ("S", C.c_int), ("s0", C.c_int), ("p", C.c_int), ("base_rows", C.c_int), ("mode", C.c_int),
+                ("mul", C.c_int), ("scale", C.c_float)]
+
+
+MR_UNIFORM, MR_GAUSS = 0, 1                                            # advh_metric_desc.mode
+
+
+def metric_device(t: torch.Tensor) -> torch.device:
+    """The GPU the metric kernels run on for ``t``: its own device when it is on a GPU, else the current one."""
+    return t.device if t.is_cuda else torch.device("cuda")
+
+
+def _on_gpu(*tensors) -> None:
+    """Every tensor whose pointer goes to a kernel must be GPU memory: a host pointer would reach the device.  Raises ValueError
+    before any launch."""
+    for t in tensors:
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise ValueError("the metric kernels take GPU tensors; got " + (f"a tensor on {t.device}" if torch.is_tensor(t)
+                                                                             else type(t).__name__))
+
+
+def metric_desc(x, seed, S, s0, pp, mode, scale, attr=None, base=None, mul=False) -> MetricDesc:
+    B, L = x.shape
+    d = MetricDesc(x.data_ptr(), None if attr is None else attr.data_ptr(), None if base is None else base.data_ptr(), L, seed,
+                   B, S, s0, pp, 1 if base is None else base.shape[0], mode, int(mul), scale)
+    d.tensors = (x, attr, base)                             # checked by metric_rows, and kept alive as long as the desc
+    return d
+
+
+def metric_rows(d: MetricDesc, row0: int, rows: int, out: torch.Tensor, dot: Optional[torch.Tensor] = None) -> None:
+    """Chunk rows ``[row0, row0 + rows)`` into ``out [rows, L]``; Gaussian mode also writes ``dot[row0:row0 + rows]``."""
+    _on_gpu(*d.tensors, out, dot)
+    _lib.check(_lib.lib().advh_metric_rows(C.byref(d), row0, rows, out.data_ptr(), None if dot is None else dot.data_ptr(), _st()),
+               "advh_metric_rows")
+
+
+def uniform_rows(x: torch.Tensor, seed: int, S: int, s0: int, pp: int, radius: float) -> torch.Tensor:
+    """sensitivity_max's default perturbation of the chunk ``[s0, s0 + pp)``: row ``b * pp + s'`` =
+    ``x_b + radius * (2u - 1)``, u the uniform of the Philox words of row ``b * S + s0 + s'``."""
+    B, L = x.shape
+    out = torch.empty((B * pp, L), dtype=torch.float32, device=x.device)
+    metric_rows(metric_desc(x, seed, S, s0, pp, MR_UNIFORM, radius), 0, B * pp, out)
+    return out
+
+
+def metric_row_dot(pert: torch.Tensor, attr: torch.Tensor, pp: int) -> torch.Tensor:
+    """``dot[r] = sum_j pert[r, j] * attr[r // pp, j]`` (``[B * pp]`` fp32)."""
+    _on_gpu(pert, attr)
+    dot = torch.empty(pert.shape[0], dtype=torch.float32, device=pert.device)
+    _lib.check(_lib.lib().advh_metric_row_dot(pert.data_ptr(), attr.data_ptr(), attr.shape[0], pp, attr.shape[1], dot.data_ptr(),
+                                              _st()), "advh_metric_row_dot")
+    return dot
+
+
+def infidelity_fold(dot, f0, fk, B: int, pp: int, normalize: bool, acc) -> None:
+    _on_gpu(dot, f0, fk, acc)
+    _lib.check(_lib.lib().advh_infidelity_fold(dot.data_ptr(), f0.data_ptr(), fk.data_ptr(), B, pp, int(normalize), acc.data_ptr(),
+                                               _st()), "advh_infidelity_fold")
+
+
+def infidelity_finalize(acc, B: int, S: int, normalize: bool) -> torch.Tensor:
+    _on_gpu(acc)
+    out = torch.empty(B, dtype=torch.float32, device=acc.device)
+    _lib.check(_lib.lib().advh_infidelity_finalize(acc.data_ptr(), B, S, int(normalize), out.data_ptr(), _st()),
+               "advh_infidelity_finalize")
+    return out
+
+
+def row_norm(v: torch.Tensor, ord_: int) -> torch.Tensor:
+    _on_gpu(v)
+    out = torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
+    _lib.check(_lib.lib().advh_row_norm(v.data_ptr(), v.shape[0], v.shape[1], ord_, out.data_ptr(), _st()), "advh_row_norm")
+    return out
+
+
+def sensitivity_fold(e, et, enorm, pp: int, ord_: int, smax) -> None:
+    _on_gpu(e, et, enorm, smax)
+    ratio = torch.empty(et.shape[0], dtype=torch.float32, device=et.device)
+    _lib.check(_lib.lib().advh_sensitivity_fold(e.data_ptr(), et.data_ptr(), enorm.data_ptr(), e.shape[0], pp, e.shape[1], ord_,
+                                                ratio.data_ptr(), smax.data_ptr(), _st()), "advh_sensitivity_fold")
+
+
+class NoisyPerturbation:
+    """Infidelity's noisy perturbation (an extension of this build, not a Captum name): ``noise = stdevs * N(0, 1)``, returning
+    ``(noise, inputs - noise)`` as in Captum's tutorial and Yeh et al., or -- ``multiply_by_inputs=True`` -- the perturbation of
+    ``infidelity_perturb_func_decorator(True)`` around it, ``safe_div(x - x~, x - baselines)`` (denominator 1 where zero).
+    ``infidelity`` recognises it and runs fused: the rows ``x_b - stdevs * N(seed, b * S + s, :)`` go straight into the forward's
+    workspace and the dot product with the attribution is formed in the same pass (advh_metric_rows).  Called directly it is an
+    ordinary perturb_func: one seed from torch's default CPU generator, ``N(seed, r, :)`` for row r of ``inputs [R, L]``, drawn
+    on ``metric_device(inputs)`` (a host tensor's noise is drawn on the current GPU); both results come back on the inputs'
+    device."""
+
+    def __init__(self, stdevs: float = 0.01, multiply_by_inputs: bool = False):
+        self.stdevs = _finite_scale(stdevs, "stdevs")
+        self.multiply_by_inputs = bool(multiply_by_inputs)
+
+    def __call__(self, inputs, baselines=None):
+        if not torch.is_tensor(inputs) or inputs.dim() != 2:
+            raise ValueError("inputs must be a [R, L] waveform tensor")
+        dev = metric_device(inputs)
+        noise = self.stdevs * philox_normal(draw_seed(), 0, inputs.shape[0], inputs.shape[1], dev)
+        x = inputs.to(dev, torch.float32)
+        xt = x - noise
+        if self.multiply_by_inputs:
+            den = x if baselines is None else x - (baselines.to(dev, torch.float32) if torch.is_tensor(baselines) else baselines)
+            noise = (x - xt) / torch.where(den != 0, den, torch.ones_like(den))
+        return noise.to(inputs.device), xt.to(inputs.device)
+
+
+def _checked_metric(out: torch.Tensor, what: str, cause: str) -> torch.Tensor:
+    """The engine's ``_checked`` for a metric: one synchronisation, the split-format range flag, then finiteness."""
+    finite = bool(torch.isfinite(out).all())
+    _lib.check_overflow(what)
+    if not finite:
+        raise FloatingPointError(f"non-finite {what}: {cause}")
+    return out
+
+
+def sensitivity_max(explain, waves, device, perturb_func=None, perturb_radius: float = 0.02, n_perturb_samples: int = 10,
+                    norm_ord="fro", max_examples_per_batch=None, seed: Optional[int] = None, **kwargs) -> torch.Tensor:
+    """Captum's sensitivity_max (restated from Captum 0.7's ``metrics/_core/sensitivity.py``: captum is absent) on ``device``;
+    ``HipAttribution.sensitivity_max`` documents it.  The metric needs no model: ``explain`` brings its own.  ``device`` must
+    be a GPU: the kernel wrappers reject host tensors with ValueError before any launch."""
+    B, L, S, plan = check_metric_args(waves, n_perturb_samples, max_examples_per_batch, kwargs.pop("target", None),
+                                      kwargs.pop("additional_forward_args", None))     # None once checked: not passed on
+    ord_ = check_norm_ord(norm_ord)
+    radius = _finite_scale(perturb_radius, "perturb_radius")
+    if perturb_func is not None and not callable(perturb_func):
+        raise ValueError("perturb_func must be callable")
+    seed = _check_seed(seed)                                 # drawn before explain draws its own
+    x = waves.to(device, torch.float32).contiguous()
+
+    def explained(rows, kw, R):
+        res = explain(rows, **kw)
+        if not torch.is_tensor(res) or tuple(res.shape) != (R, L):
+            raise ValueError(f"explanation_func must return a [{R}, {L}] attribution, "
+                             f"not {tuple(res.shape) if torch.is_tensor(res) else type(res).__name__}")
+        return res.to(device, torch.float32).contiguous()
+
+    def perturbed(s0, pp):
+        R = B * pp
+        if perturb_func is None:
+            return uniform_rows(x, seed, S, s0, pp, radius)
+        xe = x.repeat_interleave(pp, 0)
+        xt = perturb_func(xe, perturb_radius) if _perturb_params(perturb_func) > 1 else perturb_func(xe)
+        if isinstance(xt, (tuple, list)) and len(xt) == 1:
+            xt = xt[0]
+        if not torch.is_tensor(xt) or tuple(xt.shape) != (R, L):
+            raise ValueError(f"perturb_func must return the [{R}, {L}] perturbed inputs, "
+                             f"not {tuple(xt.shape) if torch.is_tensor(xt) else type(xt).__name__}")
+        return xt.to(device, torch.float32).contiguous()
+
+    xt = perturbed(*plan[0])                                 # a perturb_func of the wrong shape raises before any explanation
+    e = explained(x, kwargs, B)
+    enorm = row_norm(e, ord_)
+    smax = torch.zeros(B, dtype=torch.float32, device=device)
+    for k, (s0, pp) in enumerate(plan):
+        xt = xt if k == 0 else perturbed(s0, pp)
+        sensitivity_fold(e, explained(xt, sensitivity_kwargs(kwargs, B, L, pp), B * pp), enorm, pp, ord_, smax)
+    return _checked_metric(smax, "sensitivity_max", "an explanation of the clips or of their perturbations is not finite")
+
+
 class CoalitionDesc(C.Structure):
     """Mirror of ``advh_coalition_desc`` (include/addvisor_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("base", C.c_void_p), ("index", C.c_void_p), ("rank", C.c_void_p), ("present", C.c_void_p),
@@ -500,7 +749,9 @@ def _accumulate(d, grad, w, mode, row0, rows, total, row_sum=None):
 def philox_normal(seed: int, row0: int, rows: int, n: int, device, raw: bool = False) -> torch.Tensor:
     """``[rows, n]`` fp32 standard normals N(seed, row0 + r, j): exactly the noise GradientShap adds to expanded row g
     (``stdevs * N(seed, g, :)``).  ``raw=True``: the Philox words instead, ``[rows, n]`` int32 (bit patterns).
-    advh_philox_normal."""
+    advh_philox_normal.  ``device`` must be a GPU (ValueError before any launch: a host buffer would reach the kernel)."""
+    if torch.device(device).type != "cuda":
+        raise ValueError(f"philox_normal draws on a GPU, not on {device}")
     out = torch.empty((rows, n), dtype=torch.float32, device=device)
     _lib.check(_lib.lib().advh_philox_normal(int(seed), row0, rows, n, int(raw), out.data_ptr(), _st()), "advh_philox_normal")
     return out.view(torch.int32) if raw else out
@@ -864,6 +1115,102 @@ class HipAttribution:
             nt_fold(res.to(x.device, torch.float32).contiguous(), B, pp, total, total_sq)
         out = self._checked(nt_finalize(total, total_sq, S, nt_type), "NoiseTunnel attribution")
         return (out, torch.cat(deltas)) if return_convergence_delta else out
+
+    def infidelity(self, waves, perturb_func, attributions, baselines=None, n_perturb_samples: int = 10,
+                   max_examples_per_batch: Optional[int] = None, normalize: bool = False, seed: Optional[int] = None,
+                   internal_batch_size: Optional[int] = None, target=None, additional_forward_args=None) -> torch.Tensor:
+        """Captum's infidelity (Yeh et al., NeurIPS 2019; restated from Captum 0.7's ``metrics/_core/infidelity.py``: captum is
+        absent) of ``attributions [B, L]`` of the classifier logit F, ``[B]`` fp32.  The S = ``n_perturb_samples`` samples of
+        each clip run in Captum's chunks (``metric_partitions`` of ``max_examples_per_batch``); chunk ``[s0, s0 + p')`` has
+        ``B * p'`` rows, row ``b * p' + s'`` (``repeat_interleave``).  ``perturb_func(inputs_expanded[, baselines_expanded])``
+        returns ``(perturbation, perturbed_inputs)``, ``[B * p', L]`` each (``baselines`` expanded by
+        ``expand_metric_baselines``); per row ``a = sum_j perturbation_j * attr_b,j`` and ``d = F(x_b) - F(x~)`` (fp32).  The
+        result is ``sum_s (a - d)^2 / S``, or with ``normalize`` ``(beta^2 sum a^2 - 2 beta sum a d + sum d^2) / S`` with
+        ``beta = safe_div(sum a d, sum a^2, 1)``: the sums are fp64 on the device in sample order (advh_infidelity_fold), so
+        they do not depend on the chunking; only the forward's logits can.  The perturbed rows go through the forward
+        ``internal_batch_size`` (default 128) at a time.
+
+        A ``NoisyPerturbation`` runs fused: row (b, s) = ``x_b - stdevs * N(seed, b * S + s, :)`` written into the forward's
+        workspace with its dot product (advh_metric_rows); any other callable is called once per chunk (the generic path).
+        ``seed=None`` draws one from torch's default CPU generator first, so ``torch.manual_seed`` reproduces a call; Captum's
+        own RNG stream is not reproduced.  The perturbed rows share one forward workspace of
+        ``min(internal_batch_size, B * p_0)`` rows (p_0: the first chunk's samples); a chunk with fewer rows forwards only its
+        own, and the last forward batch inside a chunk is padded to the workspace with the previous batch's rows, as
+        ``_row_logits`` pads.  A Python perturb_func is called for the first chunk before the forward of the clips, so that a
+        result of the wrong shape raises ValueError before any GPU work.  Raises ValueError on bad arguments before any GPU
+        work, FloatingPointError (or SplitRangeError) when a logit or the attribution is not finite."""
+        B, L, S, plan = check_metric_args(waves, n_perturb_samples, max_examples_per_batch, target, additional_forward_args,
+                                          attributions)
+        if not callable(perturb_func):
+            raise ValueError("perturb_func must be callable")
+        if baselines is not None:
+            check_ig_baselines(baselines, B, L)
+        chunk = check_internal_batch(internal_batch_size)
+        fused = isinstance(perturb_func, NoisyPerturbation)
+        seed = _check_seed(seed)
+        x = self._prep(waves)
+        dev = x.device
+        attr = attributions.to(dev, torch.float32).contiguous()
+        base = baselines.to(dev, torch.float32) if torch.is_tensor(baselines) else baselines
+        if fused and perturb_func.multiply_by_inputs and base is not None:
+            base = check_ig_baselines(baselines, B, L).to(dev, torch.float32).contiguous()      # a number -> [1, L]
+
+        def generic(pp):
+            """The chunk's ``(perturbation, perturbed rows)`` from the Python perturb_func, shapes checked."""
+            R = B * pp
+            be = expand_metric_baselines(base, B, L, pp)
+            xe = x.repeat_interleave(pp, 0)
+            res = perturb_func(xe, be) if be is not None else perturb_func(xe)
+            if not isinstance(res, (tuple, list)) or len(res) != 2:
+                raise ValueError("perturb_func must return (perturbations, perturbed_inputs)")
+            pert, xt = (t[0] if isinstance(t, (tuple, list)) and len(t) == 1 else t for t in res)
+            for t, what in ((pert, "perturbations"), (xt, "perturbed inputs")):
+                if not torch.is_tensor(t) or tuple(t.shape) != (R, L):
+                    raise ValueError(f"perturb_func must return [{R}, {L}] {what}, "
+                                     f"not {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            return pert.to(dev, torch.float32).contiguous(), xt.to(dev, torch.float32).contiguous()
+
+        first = None if fused else generic(plan[0][1])      # a perturb_func of the wrong shape raises before the forward
+        acc = torch.zeros(3 * B if normalize else B, dtype=torch.float64, device=dev)
+        f0 = self.eg.emb.forward(x, want_hidden=False)[1].view(-1)
+        # one workspace for every chunk: the first chunk fills it whole, a shorter chunk leaves the previous (finite) rows behind
+        pts = torch.empty((min(chunk, B * plan[0][1]), L), dtype=torch.float32, device=dev)
+        for k, (s0, pp) in enumerate(plan):
+            R = B * pp
+            if fused:
+                d = metric_desc(x, seed, S, s0, pp, MR_GAUSS, perturb_func.stdevs, attr,
+                                base if perturb_func.multiply_by_inputs else None, perturb_func.multiply_by_inputs)
+                dot = torch.empty(R, dtype=torch.float32, device=dev)
+                fill = lambda row0, out, d=d, dot=dot, R=R: metric_rows(d, row0, min(out.shape[0], R - row0), out, dot)
+            else:
+                pert, xt = first if k == 0 else generic(pp)
+                dot = metric_row_dot(pert, attr, pp)
+                fill = lambda row0, out, xt=xt, R=R: out[:min(out.shape[0], R - row0)].copy_(xt[row0:row0 + out.shape[0]])
+            fk = self._row_logits(fill, 0, R, pts if R >= pts.shape[0] else pts[:R])
+            infidelity_fold(dot, f0, fk, B, pp, normalize, acc)
+        return self._checked(infidelity_finalize(acc, B, S, normalize), "infidelity",
+                             "a logit of the clips or of their perturbations, or the attribution, is not finite")
+
+    def sensitivity_max(self, explain, waves, perturb_func=None, perturb_radius: float = 0.02, n_perturb_samples: int = 10,
+                        norm_ord="fro", max_examples_per_batch: Optional[int] = None, seed: Optional[int] = None, **kwargs):
+        """Captum's sensitivity_max (restated from Captum 0.7's ``metrics/_core/sensitivity.py``: captum is absent), ``[B]``
+        fp32: ``e = explain(x, **kwargs)``; the S = ``n_perturb_samples`` samples of each clip run in Captum's chunks
+        (``metric_partitions``), chunk ``[s0, s0 + p')`` explains its ``B * p'`` perturbed rows (row ``b * p' + s'``) with
+        ``explain(x~, **kwargs_expanded)`` (``sensitivity_kwargs``: a ``[B, L]`` baseline is ``repeat_interleave``d, every other
+        argument passes unchanged), and the result is ``max_s ||e_b - e~||_ord / ||e_b||_ord`` (a zero norm counts as 1) over a
+        fixed tree on the device (advh_sensitivity_fold).  ``norm_ord``: "fro" / 2, 1 or inf.  ``explain`` is any callable
+        attributing a ``[R, L]`` tensor (an engine method, a ``captum.attr`` object's ``attribute``, ``NoiseTunnel.attribute``).
+
+        ``perturb_func=None`` (Captum's ``default_perturb_func``, ``x + U(-r, r)``) runs on the device: row (b, s) =
+        ``x_b + r * (2u - 1)``, u from the Philox words of row ``b * S + s`` (advh_metric_rows), so the rows do not depend on the
+        chunking.  A callable gets the expanded inputs (and ``perturb_radius`` if it takes two parameters) and returns the
+        perturbed inputs.  Unlike Captum, which explains the clips first, the first chunk's perturbation is made before the
+        explanation of the clips, so that a perturb_func result of the wrong shape raises ValueError before any explanation
+        runs.  ``target`` and ``additional_forward_args`` must be None and are not passed on to ``explain``.  ``seed=None``
+        draws one from torch's default CPU generator before ``explain`` runs, so a method that draws its own seed draws it
+        afterwards and ``torch.manual_seed`` reproduces the call; Captum's RNG stream is not reproduced."""
+        return sensitivity_max(explain, waves, self.emb.dev, perturb_func, perturb_radius, n_perturb_samples, norm_ord,
+                               max_examples_per_batch, seed, **kwargs)
 
     def _ig_zero(self, waves, n_steps: int, internal_batch_size: Optional[int]):
         x = self._prep(waves)

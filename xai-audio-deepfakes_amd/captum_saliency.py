@@ -11,6 +11,7 @@ from audioprocessor import AudioProcessor
 from captum.attr import Saliency, InputXGradient, IntegratedGradients, GradientShap, NoiseTunnel  # noqa: F401
 from captum.attr import Occlusion, FeatureAblation  # noqa: F401
 from captum.attr import ShapleyValueSampling, ShapleyValues, KernelShap  # noqa: F401
+from captum.metrics import infidelity, sensitivity_max, NoisyPerturbation  # noqa: F401
 from classifier_embedder import TorchLogReg  # noqa: F401  (name kept for callers of the reference module)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -62,6 +63,19 @@ def _segments(waves, window):
     return (torch.arange(waves.shape[-1], device=waves.device) // window)[None]
 
 
+def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5, stdevs=0.01):
+    """The attribution of ``explain_waves``'s ``method`` (wrapped in NoiseTunnel when ``nt_type`` is set) as a callable
+    ``[R, L] -> [R, L]`` on the engine ``att``."""
+    fn = {"saliency": att.saliency, "input_x_gradient": att.input_x_gradient,
+          "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
+          "occlusion": lambda w: att.occlusion(w, window, stride),
+          "shapley_value_sampling": lambda w: att.shapley_value_sampling(w, feature_mask=_segments(w, window)),
+          "kernel_shap": lambda w: att.kernel_shap(w, feature_mask=_segments(w, window))}[method]
+    if nt_type is None:
+        return fn
+    return lambda w: att.noise_tunnel(w, fn, nt_type=nt_type, nt_samples=nt_samples, stdevs=stdevs)
+
+
 def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5,
                   stdevs=0.01):
     """Loop body of compute_camptum_saliency_metrics (captum_saliency.py:125-192) for a batch ``[B, L]``:
@@ -73,12 +87,7 @@ def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=16
     waveform in [-1, 1]).  Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
-    fn = {"saliency": att.saliency, "input_x_gradient": att.input_x_gradient,
-          "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
-          "occlusion": lambda w: att.occlusion(w, window, stride),
-          "shapley_value_sampling": lambda w: att.shapley_value_sampling(w, feature_mask=_segments(w, window)),
-          "kernel_shap": lambda w: att.kernel_shap(w, feature_mask=_segments(w, window))}[method]
-    attr = fn(x) if nt_type is None else att.noise_tunnel(x, fn, nt_type=nt_type, nt_samples=nt_samples, stdevs=stdevs)
+    attr = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs)(x)
     _, w_rel, w_irr = att.time_mask(attr, x)
     emb = _rt.hip_embedder()
     B = x.shape[0]
@@ -86,22 +95,47 @@ def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=16
     return p[:B], p[B:2 * B], p[2 * B:]
 
 
+def score_explanations(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5,
+                       stdevs=0.01, n_perturb_samples=10, perturb_radius=0.02, norm_ord="fro", multiply_by_inputs=False):
+    """Captum's two explanation metrics of ``explain_waves``'s attribution (``method``, optionally in NoiseTunnel) for a batch
+    ``[B, L]``: ``{"infidelity": [B], "sensitivity_max": [B]}`` fp32.  Infidelity perturbs each clip ``n_perturb_samples``
+    times with ``NoisyPerturbation(stdevs, multiply_by_inputs)`` (``x - stdevs * N(0, 1)``; ``stdevs`` in waveform units, as in
+    ``explain_waves``); sensitivity_max re-runs the attribution on ``n_perturb_samples`` copies ``x + U(-perturb_radius,
+    perturb_radius)`` and takes the largest relative change in ``norm_ord``."""
+    att = model.hip_attribution()
+    x = waves.to(device, torch.float32)
+    explain = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs)
+    attr = explain(x)
+    return {"infidelity": infidelity(model, NoisyPerturbation(stdevs, multiply_by_inputs), x, attr,
+                                     n_perturb_samples=n_perturb_samples),
+            "sensitivity_max": sensitivity_max(explain, x, perturb_radius=perturb_radius, n_perturb_samples=n_perturb_samples,
+                                               norm_ord=norm_ord)}
+
+
 def compute_camptum_saliency_metrics(model, metadata_path, target_class=None, root="LJSpeech_vocoded",
-                                     method="input_x_gradient", batch_size=8, nt_type=None, nt_samples=5, stdevs=0.01):
+                                     method="input_x_gradient", batch_size=8, nt_type=None, nt_samples=5, stdevs=0.01,
+                                     explanation_metrics=False):
     """captum_saliency.py:112-212 (name kept as in the reference); prints faithfulness and fidelity.  ``nt_type`` runs the
-    masks of NoiseTunnel over ``method`` (``explain_waves``)."""
+    masks of NoiseTunnel over ``method`` (``explain_waves``).  ``explanation_metrics=True`` also prints the means of
+    Captum's infidelity and sensitivity_max of the attributions (``score_explanations``)."""
     model.eval()
     wav_paths = extract_wavs(metadata_path)
     print(f"computing saliency for {len(wav_paths)} files")
-    preds, thetas, masked = [], [], []
+    preds, thetas, masked, infid, sens = [], [], [], [], []
     for i in range(0, len(wav_paths), batch_size):
         waves = torch.stack([audioprocessor.load_audio(os.path.join(root, p))[0] for p in wav_paths[i:i + batch_size]])
         p, t, o = explain_waves(model, waves, method, nt_type=nt_type, nt_samples=nt_samples, stdevs=stdevs)
         preds.append(p), thetas.append(t), masked.append(o)
+        if explanation_metrics:
+            sc = score_explanations(model, waves, method, nt_type=nt_type, nt_samples=nt_samples, stdevs=stdevs)
+            infid.append(sc["infidelity"]), sens.append(sc["sensitivity_max"])
     predictions, theta_out, masked_predictions = torch.cat(preds), torch.cat(thetas), torch.cat(masked)
     m = _P.lmac_metrics(predictions, theta_out, masked_predictions)
     print(f"faithfulness : {m['faithfulness']:.2f}")
     print(f"fidelity: {m['fidelity']:.2f}")
+    if explanation_metrics:
+        print(f"infidelity: {torch.cat(infid).mean().item():.4g}")
+        print(f"sensitivity_max: {torch.cat(sens).mean().item():.4g}")
     counter = int((theta_out[-batch_size:] >= 0.5).sum().item())
     print(f"number of relevant masks classified as manipulated: {counter} out of {min(batch_size, len(wav_paths))}")
     return None
