@@ -530,6 +530,53 @@ int advh_shapley_accumulate(const advh_coalition_desc* d, const float* fbase, co
                             float finalize_div, advh_stream_t stream);
 int advh_coalition_scatter(const advh_coalition_desc* d, const float* coef, float* attr, advh_stream_t stream);
 
+/* Lime and FeaturePermutation (csrc/attribution_lime.hip): Captum's Lime and FeaturePermutation of the [B][n] inputs x,
+ * restated (captum is absent).
+ *   FeaturePermutation: index[t] in [0, K) is the feature of sample t (one mask for every clip, Captum's assert); perm[k][b] is
+ *     the clip whose samples row (k, b) takes on feature k, a permutation of [0, B) that is not the identity, drawn per feature
+ *     on the host.  Rows are perturbation-major, row g = k * B + b (FeatureAblation's order):
+ *       row (k, b)[t] = x[perm[k][b]][t] where index[t] == k, x[b][t] elsewhere (Captum's _permute_feature).
+ *     attr[b][t] = F(x)[b] - F(row index[t], b) is advh_ablation_accumulate in mode 1 with mask = index (base unread).
+ *   Lime: the perturbed rows are KernelShap's presence-mode coalition rows (advh_coalition_points, mode 1: row s * B + b keeps
+ *     x[b] on the features drawn on and the baseline elsewhere), and the weight of row g against its clip x[g % B] is Captum's
+ *     get_exp_kernel_similarity_function(mode, w): exp(-d^2 / (2 w^2)), d computed on the raw row the classifier reads:
+ *       mode 0 (cosine):    d = 1 - <x, v> / (max(||x||, 1e-8) * max(||v||, 1e-8))   (torch.nn.CosineSimilarity(dim=0))
+ *       mode 1 (euclidean): d = ||x - v||
+ *     The host fits each clip's interpretable model on (draws, logits, weights); the default SkLearnLasso solves with
+ *     advh_lasso_cd, and the coefficients go back to the samples with advh_coalition_scatter.
+ *
+ * advh_permutation_points : out[r] = permuted row g = row0 + r ([rows][n]); rows g >= K * B copy x[g % B] (padding of a
+ *                           fixed-shape last chunk).  A perm entry outside [0, B) gives NaN on that feature's samples; an index
+ *                           outside [0, K) keeps x.  Needs B >= 2.  rows = 0 launches nothing.
+ * advh_row_similarity     : sim[row0 + r] for the chunk rows [rows][n] (row r is global row g = row0 + r, clip g % B), one
+ *                           workgroup per row: the sums (<x, v>, ||x||^2, ||v||^2, or ||x - v||^2) in fp64 over a fixed order
+ *                           (so a row's weight does not depend on the chunking), exp in fp64, one rounding to fp32.  It only
+ *                           reads the chunk, so it may run before or after the forward that reads the same rows.  rows = 0
+ *                           launches nothing.
+ * advh_lasso_cd           : HOST function, no HIP call.  Minimises 1/2 ||y - X c||^2 + alpha ||c||_1 (X [S][K] given column
+ *                           by column: column k at X + k * S; the caller centres and scales by sqrt(w / sum w), which makes it
+ *                           sklearn's weighted Lasso) by cyclic coordinate descent from the coef passed in, in fp64.  The
+ *                           duality gap (sklearn's, on a residual recomputed from scratch) is evaluated when the largest step of
+ *                           a sweep is <= tol relative to the largest coefficient, and after sweep max_iter; the solve stops at
+ *                           gap <= tol * ||y||^2.  Writes the last gap and the sweeps done (== max_iter with gap > tol ||y||^2:
+ *                           not converged).
+ * Null pointers, non-positive sizes, B < 2 (permutation), a mode outside [0, 1], a kernel width that is not finite and > 0, a
+ * negative or non-finite alpha or tol, and max_iter < 1 return ADVH_EINVAL before any HIP call.
+ * Replaces captum.attr.Lime(model).attribute(x, ...) and captum.attr.FeaturePermutation(model).attribute(x, ...) on the
+ * waveform -> logit classifier. */
+typedef struct advh_permutation_desc {
+    const float* x;          /* [B][n] inputs                                                   */
+    const int32_t* index;    /* [n] feature index of each sample                                */
+    const int32_t* perm;     /* [K][B] source clip of row (k, b)                                */
+    int64_t n;
+    int B, K;
+} advh_permutation_desc;
+int advh_permutation_points(const advh_permutation_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream);
+int advh_row_similarity(const float* rows_ptr, const float* x, int64_t row0, int rows, int B, int64_t n, int mode, float kernel_width,
+                        float* sim, advh_stream_t stream);
+int advh_lasso_cd(const double* X, const double* y, int S, int K, double alpha, double tol, int max_iter, double* coef, double* gap,
+                  int* iters);
+
 /* ---------------------------------------------------------------------------------------------
  * fp32-class ("split") mode.  The reference computes the whole path in fp32 (addvisor.py:12-84,
  * transformers/models/wav2vec2/modeling_wav2vec2.py:254-802 under audioprocessor.py:69-77).  In this mode every tensor

@@ -83,6 +83,9 @@ SIGNATURES = {
     "advh_coalition_points": (_i, [_p, _i64, _i, _p, _p]),
     "advh_shapley_accumulate": (_i, [_p, _p, _p, _i64, _i, _p, _f, _p]),
     "advh_coalition_scatter": (_i, [_p, _p, _p, _p]),
+    "advh_permutation_points": (_i, [_p, _i64, _i, _p, _p]),
+    "advh_row_similarity": (_i, [_p, _p, _i64, _i, _i, _i64, _i, _f, _p, _p]),
+    "advh_lasso_cd": (_i, [_p, _p, _i, _i, C.c_double, C.c_double, _i, _p, _p, _p]),
     "advh_istft_masked_bwd": (_i, [_p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "advh_istft_bandswap": (_i, [_p, _p, _i, _i, _i, _p, _i64, _i64, _i, _i, _i, _i, _i, _p, _p]),
     "advh_bn_partial_count": (_i, []),

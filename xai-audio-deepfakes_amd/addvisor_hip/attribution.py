@@ -15,7 +15,10 @@ device (csrc/attribution_ablation.hip), pushed through the classifier forward in
 accumulated in Captum's order by one launch.  The Shapley attributions ``captum.attr.ShapleyValueSampling / ShapleyValues /
 KernelShap`` build coalition rows the same way (csrc/attribution_shapley.hip): marginal contributions along permutations are
 accumulated on the device in Captum's order; KernelShap's per-clip weighted regression is a host float64 solve whose
-coefficients a kernel scatters back to the samples.
+coefficients a kernel scatters back to the samples.  ``captum.attr.Lime`` reuses KernelShap's coalition rows with Bernoulli(0.5)
+draws; the similarity weight of every row is reduced on the device from the chunk the forward reads, and each clip's
+interpretable model (a weighted Lasso by default, addvisor_hip.linear_model) is fitted on the host.  ``captum.attr.FeaturePermutation``
+builds FeatureAblation's rows with each feature taken from another clip of the batch (csrc/attribution_lime.hip).
 
 ``captum.attr.NoiseTunnel`` wraps any of them (``noise_tunnel``): the noisy rows of each partition of samples come from the same
 counter-based generator through the path-point kernel, the wrapped method attributes them, and the first and second moments are
@@ -206,19 +209,22 @@ def shapley_feature_indices(feature_mask, B: int, L: int) -> Tuple[torch.Tensor,
     return feature_indices(feature_mask, B, L)
 
 
-def kernel_shap_feature_indices(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, list]:
-    """KernelShap's features, per clip (each clip is fitted on its own): returns ``(index, Ks)``, ``index`` int32 ``[1, L]`` (a
-    None or ``[1, L]`` mask: the same features in every clip) or ``[B, L]``, the rank of each sample's id among the ids present
-    in its clip, and ``Ks`` the number of those ids per clip.  Raises ValueError on negative ids or a clip with fewer than two
-    features (the regression needs two)."""
-    _nonnegative_ids(feature_mask)
+def per_clip_feature_indices(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, list]:
+    """The features of each clip on its own: returns ``(index, Ks)``, ``index`` int32 ``[1, L]`` (a None or ``[1, L]`` mask: the
+    same features in every clip) or ``[B, L]``, the rank of each sample's id among the ids present in its clip, and ``Ks`` the
+    number of those ids per clip.  Any integer id is a feature (``feature_indices`` checks the mask)."""
     index, K = feature_indices(feature_mask, B, L)
     if index.shape[0] == 1:
-        Ks = [K] * B
-    else:
-        rows = [torch.unique(m, sorted=True, return_inverse=True) for m in index]
-        index = torch.stack([inv.to(torch.int32) for _, inv in rows])
-        Ks = [ids.numel() for ids, _ in rows]
+        return index, [K] * B
+    rows = [torch.unique(m, sorted=True, return_inverse=True) for m in index]
+    return torch.stack([inv.to(torch.int32) for _, inv in rows]), [ids.numel() for ids, _ in rows]
+
+
+def kernel_shap_feature_indices(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, list]:
+    """KernelShap's features, per clip (each clip is fitted on its own): ``per_clip_feature_indices``.  Raises ValueError on
+    negative ids or a clip with fewer than two features (the regression needs two)."""
+    _nonnegative_ids(feature_mask)
+    index, Ks = per_clip_feature_indices(feature_mask, B, L)
     if min(Ks) < 2:
         raise ValueError(f"KernelShap needs at least two features per clip; feature_mask gives {min(Ks)}")
     return index, Ks
@@ -298,17 +304,114 @@ def kernel_shap_weights(z: np.ndarray) -> np.ndarray:
 
 
 def kernel_shap_fit(z: np.ndarray, y: np.ndarray) -> Tuple[np.ndarray, float]:
-    """One clip's weighted linear regression with intercept, as sklearn's ``LinearRegression().fit(z, y, sample_weight=w)``
-    (Captum's ``SkLearnLinearRegression``): centre z and y by their weighted means, scale the rows by sqrt(w), min-norm
-    ``lstsq`` in float64, intercept = mean(y) - mean(z) . coef.  Returns ``(coef [K] float64, intercept)``."""
-    X = z.astype(np.float64)
+    """One clip's KernelShap regression: ``weighted_linear_fit`` with the weights of ``kernel_shap_weights``."""
+    return weighted_linear_fit(z, y, kernel_shap_weights(z))
+
+
+def weighted_linear_fit(z: np.ndarray, y: np.ndarray, w: np.ndarray) -> Tuple[np.ndarray, float]:
+    """A weighted linear regression with intercept, as sklearn's ``LinearRegression().fit(z, y, sample_weight=w)`` (Captum's
+    ``SkLearnLinearRegression``): centre z and y by their weighted means, scale the rows by sqrt(w), min-norm ``lstsq`` in
+    float64, intercept = mean(y) - mean(z) . coef.  Returns ``(coef [K] float64, intercept)``."""
+    X = np.asarray(z).astype(np.float64)
     y = np.asarray(y, np.float64)
-    w = kernel_shap_weights(z)
+    w = np.asarray(w, np.float64)
     xm = np.average(X, axis=0, weights=w)
     ym = np.average(y, weights=w)
     sw = np.sqrt(w)
     coef = np.linalg.lstsq((X - xm) * sw[:, None], (y - ym) * sw, rcond=None)[0]
     return coef, float(ym - xm @ coef)
+
+
+def lime_draws(seed: int, Ks, S: int) -> list:
+    """Lime's default draws (Captum's ``default_perturb_func``, Bernoulli(0.5) per feature): per clip (in order, one
+    ``numpy.random.Generator(PCG64(seed))``) ``uint8 [S, K_b]`` = ``rng.random((S, K_b)) < 0.5``; no forced all-on or all-off
+    rows.  Captum's stream is not reproduced."""
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    return [(rng.random((S, K)) < 0.5).astype(np.uint8) for K in Ks]
+
+
+def feature_permutation_draws(seed: int, K: int, B: int) -> np.ndarray:
+    """FeaturePermutation's draws: ``int32 [K, B]``, row k a uniform permutation of the B clips that is not the identity
+    (Captum's rejection loop in ``_permute_feature``), from ``numpy.random.Generator(PCG64(seed))``: all K drawn as
+    ``argsort(rng.random((K, B)))``, then the identity rows drawn again, in feature order, until none is left.  Captum's stream
+    is not reproduced."""
+    if B < 2:
+        raise ValueError("FeaturePermutation permutes the clips of the batch: it needs at least two")
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    ident = np.arange(B)
+    perm = np.argsort(rng.random((K, B)), axis=1, kind="stable")
+    same = (perm == ident).all(1)
+    while same.any():
+        perm[same] = np.argsort(rng.random((int(same.sum()), B)), axis=1, kind="stable")
+        same = (perm == ident).all(1)
+    return perm.astype(np.int32)
+
+
+def check_permutation_args(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, int]:
+    """FeaturePermutation's input rules, Captum's asserts raised as ValueError before any GPU work: ``B >= 2``; ``feature_mask``
+    None or one ``[1, L]`` integer mask for every clip.  Returns ``feature_indices``' ``(index [1, L], K)``."""
+    if B < 2:
+        raise ValueError("FeaturePermutation permutes the clips of the batch: it needs at least two")
+    if torch.is_tensor(feature_mask) and feature_mask.dim() == 2 and feature_mask.shape[0] != 1:
+        raise ValueError("FeaturePermutation takes one [1, L] feature_mask (the same features permuted in every clip), "
+                         f"not {list(feature_mask.shape)}")
+    return feature_indices(feature_mask, B, L)
+
+
+SIM_MODES = ("cosine", "euclidean")                                    # advh_row_similarity's mode = the index
+
+
+def check_kernel(distance_mode, kernel_width) -> Tuple[int, float]:
+    """Captum's ``get_exp_kernel_similarity_function`` arguments -> ``(mode, width)``: ``distance_mode`` "cosine" or
+    "euclidean", ``kernel_width`` a finite number > 0.  Raises ValueError."""
+    if distance_mode not in SIM_MODES:
+        raise ValueError(f"distance_mode must be 'cosine' or 'euclidean', not {distance_mode!r}")
+    if isinstance(kernel_width, bool) or not isinstance(kernel_width, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(kernel_width) or not 0 < kernel_width <= float(np.finfo(np.float32).max):
+        raise ValueError(f"kernel_width must be a finite number > 0, not {kernel_width!r}")
+    return SIM_MODES.index(distance_mode), float(kernel_width)
+
+
+class ExpKernelSimilarity:
+    """Captum's ``get_exp_kernel_similarity_function(distance_mode, kernel_width)``: ``exp(-d^2 / (2 w^2))`` between the clip
+    and a perturbed row, ``d = 1 - cos`` (``torch.nn.CosineSimilarity(dim=0)``: each norm clamped at 1e-8) or ``||x - v||_2``.
+    ``lime`` recognises it and computes the weights on the device (advh_row_similarity, fp64 sums); called directly it is
+    Captum's function, in torch on the inputs' device."""
+
+    def __init__(self, distance_mode: str = "cosine", kernel_width: float = 1.0):
+        check_kernel(distance_mode, kernel_width)
+        self.distance_mode, self.kernel_width = distance_mode, kernel_width
+
+    def __call__(self, original_inp, perturbed_inp, interpretable_sample=None, **kwargs) -> float:
+        a = original_inp.reshape(-1).float()
+        v = perturbed_inp.reshape(-1).float()
+        if self.distance_mode == "cosine":
+            d = 1 - torch.nn.CosineSimilarity(dim=0)(a, v)
+        else:
+            d = torch.norm(a - v)
+        return math.exp(-1 * float(d) ** 2 / (2 * self.kernel_width ** 2))
+
+    def __repr__(self):
+        return f"ExpKernelSimilarity(distance_mode={self.distance_mode!r}, kernel_width={self.kernel_width!r})"
+
+
+def check_lime_callables(similarity_func, perturb_func, interpretable_model):
+    """Lime's pluggable parts, checked before any GPU work (ValueError): a callable ``similarity_func`` (an
+    ``ExpKernelSimilarity`` with a valid mode and width), a plain callable ``perturb_func`` -- a generator function is refused --
+    and an ``interpretable_model`` with ``fit`` and ``representation``.  None stands for the default of each."""
+    if similarity_func is not None:
+        if not callable(similarity_func):
+            raise ValueError("similarity_func must be callable")
+        if isinstance(similarity_func, ExpKernelSimilarity):
+            check_kernel(similarity_func.distance_mode, similarity_func.kernel_width)
+    if perturb_func is not None:
+        if not callable(perturb_func):
+            raise ValueError("perturb_func must be callable")
+        if inspect.isgeneratorfunction(perturb_func) or inspect.isgeneratorfunction(getattr(perturb_func, "__call__", None)):
+            raise ValueError("perturb_func must return one interpretable sample per call, not be a generator function")
+    if interpretable_model is not None and not (callable(getattr(interpretable_model, "fit", None))
+                                                and callable(getattr(interpretable_model, "representation", None))):
+        raise ValueError("interpretable_model must have fit(DataLoader) and representation()")
 
 
 NT_TYPES = ("smoothgrad", "smoothgrad_sq", "vargrad")                 # advh_nt_finalize's nt_type = the index
@@ -720,6 +823,33 @@ def ablation_accumulate(d: AblationDesc, f0: torch.Tensor, fk: torch.Tensor, att
                "advh_ablation_accumulate")
 
 
+class PermutationDesc(C.Structure):
+    """Mirror of ``advh_permutation_desc`` (include/addvisor_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("index", C.c_void_p), ("perm", C.c_void_p), ("n", C.c_int64), ("B", C.c_int), ("K", C.c_int)]
+
+
+def permutation_desc(x, index, perm) -> PermutationDesc:
+    """``index [1, L]`` int32 feature ranks, ``perm [K, B]`` int32 (``feature_permutation_draws``)."""
+    B, L = x.shape
+    d = PermutationDesc(x.data_ptr(), index.data_ptr(), perm.data_ptr(), L, B, perm.shape[0])
+    d.tensors = (x, index, perm)                                          # kept alive as long as the desc
+    return d
+
+
+def permutation_points(d: PermutationDesc, row0: int, rows: int, out: torch.Tensor) -> None:
+    """Permuted rows ``[row0, row0 + rows)`` (perturbation-major, rows past ``K * B`` copy x) into ``out [rows, L]``."""
+    _on_gpu(*d.tensors, out)
+    _lib.check(_lib.lib().advh_permutation_points(C.byref(d), row0, rows, out.data_ptr(), _st()), "advh_permutation_points")
+
+
+def row_similarity(rows: torch.Tensor, x: torch.Tensor, row0: int, n_rows: int, mode: int, kernel_width: float,
+                   sim: torch.Tensor) -> None:
+    """``sim[row0 + r]`` = the exp-kernel weight of ``rows[r]`` against its clip ``x[(row0 + r) % B]``, ``r < n_rows``."""
+    _on_gpu(rows, x, sim)
+    _lib.check(_lib.lib().advh_row_similarity(rows.data_ptr(), x.data_ptr(), row0, n_rows, x.shape[0], x.shape[1], mode,
+                                              kernel_width, sim.data_ptr(), _st()), "advh_row_similarity")
+
+
 class PathDesc(C.Structure):
     """Mirror of ``advh_path_desc`` (include/addvisor_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("base", C.c_void_p), ("bidx", C.c_void_p), ("n", C.c_int64), ("seed", C.c_uint64),
@@ -938,14 +1068,15 @@ class HipAttribution:
         index = index.to(x.device).contiguous()
         return self._ablate(ablation_desc(x, base, ABL_FEATURE, K, mask=index), x, K, chunk, "feature ablation")
 
-    def _ablate(self, d: AblationDesc, x, K: int, chunk: int, what: str):
+    def _ablate(self, d: AblationDesc, x, K: int, chunk: int, what: str, points=None):
         """The shared chunk loop: ablated rows -> forward logits -> ``fk``; then ``F(x)`` and one accumulate launch.  Every
-        chunk has ``chunk`` rows (the last one padded with copies of x), so one forward workspace serves them all."""
+        chunk has ``chunk`` rows (the last one padded with copies of x), so one forward workspace serves them all.
+        ``points(row0, out)``: the rows' builder when it is not ``advh_ablation_points`` (FeaturePermutation)."""
         B, L = x.shape
         R = K * B
         chunk = min(chunk, R)
         pts = torch.empty((chunk, L), dtype=torch.float32, device=x.device)
-        fk = self._row_logits(lambda row0, out: ablation_points(d, row0, chunk, out), 0, R, pts)
+        fk = self._row_logits(points or (lambda row0, out: ablation_points(d, row0, chunk, out)), 0, R, pts)
         f0 = self.eg.emb.forward(x, want_hidden=False)[1].view(-1)
         attr = torch.empty_like(x)
         ablation_accumulate(d, f0, fk, attr)
@@ -1068,6 +1199,164 @@ class HipAttribution:
         fits = [kernel_shap_fit(z[b], y[:, b]) for b in range(B)]
         return {"x": x, "desc": d, "z": z, "y": y, "seed": seed, "coef": [c for c, _ in fits],
                 "intercept": np.array([i for _, i in fits]), "tensors": (base, present, index)}   # the desc points into them
+
+    def lime(self, waves, baselines=None, feature_mask=None, n_samples: int = 50, seed: Optional[int] = None,
+             internal_batch_size: Optional[int] = None, return_input_shape: bool = True, interpretable_model=None,
+             similarity_func=None, perturb_func=None):
+        """Captum's Lime (restated from Captum 0.7's ``attr/_core/lime.py``: captum is absent).  Each clip is fitted on its own
+        over the integer ids present in it, negative ids included (``per_clip_feature_indices``; Captum also fits columns for the
+        ids of ``[min, max]`` absent from a clip, which touch no sample: they are left out).  ``n_samples`` interpretable samples
+        ``z [S, K_b]`` per clip: ``perturb_func=None`` draws Captum's Bernoulli(0.5) on the host (``lime_draws(seed, ...)``;
+        ``seed=None`` draws one from torch's default CPU generator); a callable is called once per sample, clip by clip, as
+        ``perturb_func(x_b [1, L], num_interp_features=K_b, baselines=base_b, feature_mask=index_b [1, L])`` and returns a
+        ``[1, K_b]`` 0/1 tensor.  Row ``s * B + b`` keeps x on the features that are on and the baseline elsewhere (KernelShap's
+        presence rows, advh_coalition_points); ``baselines`` as ``occlusion``.
+
+        The weight of a row is ``similarity_func(x_b, row, z)``: None is ``ExpKernelSimilarity("cosine", 1.0)``, and an
+        ``ExpKernelSimilarity`` runs on the device over the chunk the forward reads (advh_row_similarity, the raw waveform row
+        before the classifier's own normalisation, as Captum passes it); any other callable is called once per row, in row order,
+        on device slices ``(x_b [1, L], row [1, L], z [1, K_b], num_interp_features=, baselines=, feature_mask=)``.  The logits
+        y and the weights w are fitted clip by clip as Captum does: ``interpretable_model.fit(DataLoader(TensorDataset(z, y, w),
+        batch_size=S))`` (float32 tensors), then ``representation()`` ``[1, K_b]``; None is ``SkLearnLasso(alpha=0.01)``
+        (addvisor_hip.linear_model, whose three models get the same arrays through ``fit_arrays``, without the DataLoader's
+        per-sample collation).  ``attr[b, t] = coef_b[id(b, t)]`` in fp32 (advh_coalition_scatter);
+        ``return_input_shape=False`` returns the ``[1, K]`` coefficients of a single clip.  The rows run through the forward
+        ``internal_batch_size`` (default 128) at a time.  Raises FloatingPointError when a logit is not finite or a clip's weights
+        sum to zero (an underflowing kernel), ValueError on bad arguments before any GPU work."""
+        fit = self._lime_fit(waves, baselines, feature_mask, n_samples, seed, internal_batch_size, return_input_shape,
+                             interpretable_model, similarity_func, perturb_func)
+        x, d, coefs = fit["x"], fit["desc"], fit["coef"]
+        B = x.shape[0]
+        if not return_input_shape:
+            return torch.from_numpy(coefs[0]).view(1, -1).to(x.device)
+        coef = np.zeros((B, d.K), np.float32)
+        for b, c in enumerate(coefs):
+            coef[b, :c.shape[0]] = c
+        attr = torch.empty_like(x)
+        coalition_scatter(d, torch.from_numpy(coef).to(x.device), attr)
+        return self._checked(attr, "Lime attribution", "an interpretable model's coefficient is not finite")
+
+    def _lime_fit(self, waves, baselines=None, feature_mask=None, n_samples=50, seed=None, internal_batch_size=None,
+                  return_input_shape=True, interpretable_model=None, similarity_func=None, perturb_func=None):
+        """Lime up to the per-clip fits: a dict with the draws ``z`` (per clip ``[S, K_b]`` uint8), the logits ``y`` and the
+        weights ``w`` (``[S, B]`` float32, row ``s * B + b``), ``coef`` (per clip ``[K_b]`` float32, the representation), the
+        seed, and the device state (``x``, ``desc`` and the tensors it points into)."""
+        B, L = _dims(waves)
+        base = check_ig_baselines(baselines, B, L)
+        index, Ks = per_clip_feature_indices(feature_mask, B, L)
+        S = check_n_samples(n_samples)
+        chunk = check_internal_batch(internal_batch_size)
+        if not return_input_shape and B > 1:
+            raise ValueError("return_input_shape=False returns one clip's coefficients: pass a single clip")
+        check_lime_callables(similarity_func, perturb_func, interpretable_model)
+        sim_fn = ExpKernelSimilarity() if similarity_func is None else similarity_func
+        on_device = isinstance(sim_fn, ExpKernelSimilarity)
+        if interpretable_model is None:
+            from .linear_model import SkLearnLasso
+            interpretable_model = SkLearnLasso(alpha=0.01)
+        seed = _check_seed(seed)
+        x = self._prep(waves)
+        dev = x.device
+        base = base.to(dev, torch.float32).contiguous()
+        index = index.to(dev).contiguous()
+        base_of = lambda b: base[0 if base.shape[0] == 1 else b][None]
+        index_of = lambda b: index[0 if index.shape[0] == 1 else b][None].long()
+        kw_of = lambda b: {"num_interp_features": Ks[b], "baselines": base_of(b), "feature_mask": index_of(b)}
+        z = lime_draws(seed, Ks, S) if perturb_func is None else self._lime_user_draws(perturb_func, x, Ks, S, kw_of)
+        Kmax = max(Ks)
+        table = np.zeros((S * B, Kmax), np.uint8)
+        for b, zb in enumerate(z):
+            table[b::B, :Ks[b]] = zb                                                        # row s * B + b
+        present = torch.from_numpy(table).to(dev)
+        d = coalition_desc(x, base, index, Kmax, present=present)
+        R = S * B
+        pts = torch.empty((min(chunk, R), L), dtype=torch.float32, device=dev)
+        if on_device:
+            mode, width = check_kernel(sim_fn.distance_mode, sim_fn.kernel_width)
+            sim = torch.empty(R, dtype=torch.float32, device=dev)
+        else:
+            zt = [torch.from_numpy(zb).to(dev, torch.long) for zb in z]
+            sim = np.empty(R, np.float32)
+
+        def points(row0, out):
+            coalition_points(d, row0, out.shape[0], out)
+            n = min(out.shape[0], R - row0)
+            if on_device:                                   # the chunk the forward reads next, on the same stream
+                row_similarity(out, x, row0, n, mode, width, sim)
+                return
+            for r in range(n):
+                g = row0 + r
+                b, s = g % B, g // B
+                v = sim_fn(x[b][None], out[r][None], zt[b][s][None], **kw_of(b))
+                v = torch.as_tensor(v).reshape(-1)
+                if v.numel() != 1:
+                    raise ValueError(f"similarity_func must return one number per row, not {v.numel()}")
+                sim[g] = float(v[0])
+
+        fk = self._row_logits(points, 0, R, pts)
+        self._checked(fk[:R], "Lime logits", "a logit of the clips or of a perturbed row is not finite (check the inputs and "
+                                             "baselines)")
+        y = fk[:R].view(S, B).cpu().numpy()
+        w = (sim.cpu().numpy() if on_device else sim).reshape(S, B)
+        what = f"kernel_width={sim_fn.kernel_width}" if on_device else f"similarity_func={sim_fn!r}"
+        for b in range(B):
+            wb = w[:, b].astype(np.float64)
+            if not np.isfinite(wb).all():
+                raise FloatingPointError(f"non-finite Lime similarity weight in clip {b} ({what})")
+            if wb.sum() == 0:
+                raise FloatingPointError(f"the Lime similarity weights of clip {b} sum to zero ({what}): the kernel underflows "
+                                         "for every perturbed row; widen it")
+        from torch.utils.data import DataLoader, TensorDataset
+        from .linear_model import _SkLearnModel
+        coefs = []
+        for b in range(B):
+            zb, yb, wb = z[b].astype(np.float32), y[:, b].copy(), w[:, b].copy()
+            if isinstance(interpretable_model, _SkLearnModel):     # the arrays the DataLoader would hand it, without the collation
+                interpretable_model.fit_arrays(zb, yb, wb)
+            else:
+                interpretable_model.fit(DataLoader(TensorDataset(torch.from_numpy(zb), torch.from_numpy(yb), torch.from_numpy(wb)),
+                                                   batch_size=S))
+            c = torch.as_tensor(interpretable_model.representation()).detach().to("cpu", torch.float32).reshape(-1)
+            if c.numel() != Ks[b]:
+                raise ValueError(f"interpretable_model.representation() must hold {Ks[b]} coefficients, not {c.numel()}")
+            coefs.append(c.numpy())
+        return {"x": x, "desc": d, "z": z, "y": y, "w": w, "seed": seed, "coef": coefs, "tensors": (base, present, index)}
+
+    @staticmethod
+    def _lime_user_draws(perturb_func, x, Ks, S, kw_of) -> list:
+        """A user perturb_func's samples, ``S`` calls per clip in clip order, each a ``[1, K_b]`` 0/1 tensor (ValueError
+        otherwise)."""
+        out = []
+        for b, K in enumerate(Ks):
+            zb = np.empty((S, K), np.uint8)
+            for s in range(S):
+                v = perturb_func(x[b][None], **kw_of(b))
+                v = torch.as_tensor(v).detach().cpu().reshape(-1)
+                if v.numel() != K or not bool(((v == 0) | (v == 1)).all()):
+                    raise ValueError(f"perturb_func must return a [1, {K}] tensor of zeros and ones")
+                zb[s] = v.numpy()
+            out.append(zb)
+        return out
+
+    def feature_permutation(self, waves, feature_mask=None, seed: Optional[int] = None, internal_batch_size: Optional[int] = None):
+        """Captum's FeaturePermutation (restated from Captum 0.7's ``attr/_core/feature_permutation.py``: captum is absent):
+        FeatureAblation with the baseline of each feature taken from another clip of the batch.  ``feature_mask``: None (each
+        sample its own feature) or one integer ``[1, L]`` mask; ``B >= 2`` (Captum's asserts, ValueError).  For feature k a
+        uniform permutation ``perm_k`` of the clips that is not the identity is drawn on the host
+        (``feature_permutation_draws(seed, ...)``; ``seed=None`` draws one from torch's default CPU generator); row ``k * B + b``
+        is ``x[b]`` with the samples of feature k taken from ``x[perm_k[b]]`` (advh_permutation_points, FeatureAblation's
+        perturbation-major order), and ``attr[b, t] = F(x)[b] - F(row k(t), b)`` -- advh_ablation_accumulate in FeatureAblation
+        mode, its arithmetic bit for bit.  The rows run through the forward ``internal_batch_size`` (default 128) at a time."""
+        B, L = _dims(waves)
+        index, K = check_permutation_args(feature_mask, B, L)
+        chunk = check_internal_batch(internal_batch_size)
+        perm = feature_permutation_draws(_check_seed(seed), K, B)
+        x = self._prep(waves)
+        index = index.to(x.device).contiguous()
+        pd = permutation_desc(x, index, torch.from_numpy(perm).to(x.device))
+        ad = ablation_desc(x, x, ABL_FEATURE, K, mask=index)                  # the accumulate reads the mask only
+        return self._ablate(ad, x, K, chunk, "feature permutation",
+                            points=lambda row0, out: permutation_points(pd, row0, out.shape[0], out))
 
     def noise_tunnel(self, waves, attribute, nt_type: str = "smoothgrad", nt_samples: int = 5,
                      nt_samples_batch_size: Optional[int] = None, stdevs: float = 1.0, draw_baseline_from_distrib: bool = False,

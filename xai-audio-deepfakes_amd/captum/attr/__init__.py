@@ -1,8 +1,8 @@
 """``captum.attr``-compatible front ends (captum_saliency.py:3, 116-118, 131-135) over the HIP kernels: the gradient methods
 (Saliency, InputXGradient, IntegratedGradients, GradientShap) on the HIP backward path, the perturbation methods (Occlusion,
-FeatureAblation) and the Shapley methods (ShapleyValueSampling, ShapleyValues, KernelShap) on the HIP forward with the ablated
-or coalition batches built on the device; NoiseTunnel (SmoothGrad, SmoothGrad-squared, VarGrad) around any of those nine, with
-the noisy rows and the moments on the device.
+FeatureAblation, FeaturePermutation), the Shapley methods (ShapleyValueSampling, ShapleyValues, KernelShap) and Lime on the HIP
+forward with the ablated, permuted or coalition batches built on the device; NoiseTunnel (SmoothGrad, SmoothGrad-squared,
+VarGrad) around any of those eleven, with the noisy rows and the moments on the device.
 
 ``Method(model).attribute(inputs, target=None, ...)`` expects ``model`` to be a
 ``captum_saliency.Wav2vec2LogReg`` (or anything exposing ``.hip_attribution()``): the waveform -> logit
@@ -11,6 +11,9 @@ there is no autograd fallback."""
 import torch
 
 from addvisor_hip import attribution as _A
+from addvisor_hip.linear_model import SkLearnLasso
+from ._core.feature_permutation import _permute_feature
+from ._core.lime import default_perturb_func, get_exp_kernel_similarity_function
 
 
 def _engine(model):
@@ -172,8 +175,62 @@ class KernelShap(_Method):
                                                internal_batch_size=ibs, return_input_shape=return_input_shape)
 
 
-_WRAPPABLE = (Saliency, InputXGradient, IntegratedGradients, GradientShap, Occlusion, FeatureAblation, ShapleyValueSampling,
-              ShapleyValues, KernelShap)
+class Lime(_Method):
+    """Captum's Lime: per clip, ``n_samples`` interpretable samples over the features present in the clip (``feature_mask``:
+    None = every sample its own feature, else an integer ``[1, L]`` or ``[B, L]`` tensor; any id, negative included), drawn by
+    ``perturb_func`` (default Bernoulli(0.5), drawn on the host from one seed per call of torch's default CPU generator, so
+    ``torch.manual_seed`` reproduces a result); each sample keeps the clip on the features that are on and ``baselines``
+    (None = 0, a number, ``[1, L]`` or ``[B, L]``) elsewhere, and is weighted by ``similarity_func`` against the clip (default
+    ``get_exp_kernel_similarity_function("cosine", 1.0)``, computed on the device).  ``interpretable_model`` (default
+    ``SkLearnLasso(alpha=0.01)``) is fitted on (samples, logits, weights); every sample of the clip gets its feature's
+    coefficient (``return_input_shape=False``: the ``[1, K]`` coefficients of a single clip)."""
+
+    def __init__(self, forward_func, interpretable_model=None, similarity_func=None, perturb_func=None):
+        super().__init__(forward_func)
+        self.interpretable_model = SkLearnLasso(alpha=0.01) if interpretable_model is None else interpretable_model
+        self.similarity_func = get_exp_kernel_similarity_function() if similarity_func is None else similarity_func
+        self.perturb_func = default_perturb_func if perturb_func is None else perturb_func
+
+    def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None, n_samples=50,
+                  perturbations_per_eval=1, return_input_shape=True, show_progress=False):
+        ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
+        B, L = inputs.shape
+        _A.check_ig_baselines(baselines, B, L)
+        _A.per_clip_feature_indices(feature_mask, B, L)
+        _A.check_n_samples(n_samples)
+        if not return_input_shape and B > 1:
+            raise ValueError("return_input_shape=False returns one clip's coefficients: pass a single clip")
+        perturb = None if self.perturb_func is default_perturb_func else self.perturb_func
+        _A.check_lime_callables(self.similarity_func, perturb, self.interpretable_model)
+        return _engine(self.model).lime(inputs, baselines=baselines, feature_mask=feature_mask, n_samples=n_samples,
+                                        internal_batch_size=ibs, return_input_shape=return_input_shape,
+                                        interpretable_model=self.interpretable_model, similarity_func=self.similarity_func,
+                                        perturb_func=perturb)
+
+
+class FeaturePermutation(_Method):
+    """Captum's FeaturePermutation: each feature of ``feature_mask`` (None = every sample its own feature, else one integer
+    ``[1, L]`` mask) is replaced in every clip by the same samples of another clip of the batch (a permutation of the clips
+    that is not the identity, one per feature), and every sample of the feature gets ``F(x)[b] - F(permuted)[b]``.  Needs at
+    least two clips.  The permutations follow ``torch``'s default CPU generator through one seed per call (``torch.manual_seed``
+    reproduces a result); Captum's own RNG stream is not reproduced.  Only the default ``perm_func`` is supported."""
+
+    def __init__(self, forward_func, perm_func=_permute_feature):
+        super().__init__(forward_func)
+        if perm_func is not _permute_feature:
+            raise ValueError("FeaturePermutation (HIP build) permutes on the device: only the default perm_func is supported")
+        self.perm_func = perm_func
+
+    def attribute(self, inputs, target=None, additional_forward_args=None, feature_mask=None, perturbations_per_eval=1,
+                  show_progress=False):
+        ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
+        B, L = inputs.shape
+        _A.check_permutation_args(feature_mask, B, L)
+        return _engine(self.model).feature_permutation(inputs, feature_mask=feature_mask, internal_batch_size=ibs)
+
+
+_WRAPPABLE = (Saliency, InputXGradient, IntegratedGradients, GradientShap, Occlusion, FeatureAblation, FeaturePermutation,
+              ShapleyValueSampling, ShapleyValues, KernelShap, Lime)
 
 
 class NoiseTunnel:
@@ -190,7 +247,8 @@ class NoiseTunnel:
     def __init__(self, attribution_method):
         if not isinstance(attribution_method, _WRAPPABLE):
             raise TypeError("NoiseTunnel (HIP build) wraps Saliency, InputXGradient, IntegratedGradients, GradientShap, Occlusion, "
-                            f"FeatureAblation, ShapleyValueSampling, ShapleyValues or KernelShap, not {type(attribution_method).__name__}")
+                            "FeatureAblation, FeaturePermutation, ShapleyValueSampling, ShapleyValues, KernelShap or Lime, not "
+                            f"{type(attribution_method).__name__}")
         self.attribution_method = attribution_method
         self.is_delta_supported = isinstance(attribution_method, (IntegratedGradients, GradientShap))
 

@@ -11,6 +11,9 @@ from audioprocessor import AudioProcessor
 from captum.attr import Saliency, InputXGradient, IntegratedGradients, GradientShap, NoiseTunnel  # noqa: F401
 from captum.attr import Occlusion, FeatureAblation  # noqa: F401
 from captum.attr import ShapleyValueSampling, ShapleyValues, KernelShap  # noqa: F401
+from captum.attr import Lime, FeaturePermutation  # noqa: F401
+from captum.attr._core.lime import get_exp_kernel_similarity_function  # noqa: F401
+from captum._utils.models.linear_model import SkLearnLasso, SkLearnRidge, SkLearnLinearRegression  # noqa: F401
 from captum.metrics import infidelity, sensitivity_max, NoisyPerturbation  # noqa: F401
 from classifier_embedder import TorchLogReg  # noqa: F401  (name kept for callers of the reference module)
 
@@ -63,6 +66,13 @@ def _segments(waves, window):
     return (torch.arange(waves.shape[-1], device=waves.device) // window)[None]
 
 
+def _check_batch(method, waves):
+    """``"feature_permutation"`` permutes segments across the clips of the batch: a single clip raises ValueError before any GPU
+    work."""
+    if method == "feature_permutation" and (waves.dim() < 2 or waves.shape[0] < 2):
+        raise ValueError("method='feature_permutation' takes each segment from another clip of the batch: pass two clips or more")
+
+
 def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5, stdevs=0.01):
     """The attribution of ``explain_waves``'s ``method`` (wrapped in NoiseTunnel when ``nt_type`` is set) as a callable
     ``[R, L] -> [R, L]`` on the engine ``att``."""
@@ -70,7 +80,9 @@ def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, n
           "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
           "occlusion": lambda w: att.occlusion(w, window, stride),
           "shapley_value_sampling": lambda w: att.shapley_value_sampling(w, feature_mask=_segments(w, window)),
-          "kernel_shap": lambda w: att.kernel_shap(w, feature_mask=_segments(w, window))}[method]
+          "kernel_shap": lambda w: att.kernel_shap(w, feature_mask=_segments(w, window)),
+          "lime": lambda w: att.lime(w, feature_mask=_segments(w, window)),
+          "feature_permutation": lambda w: att.feature_permutation(w, feature_mask=_segments(w, window))}[method]
     if nt_type is None:
         return fn
     return lambda w: att.noise_tunnel(w, fn, nt_type=nt_type, nt_samples=nt_samples, stdevs=stdevs)
@@ -81,10 +93,13 @@ def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=16
     """Loop body of compute_camptum_saliency_metrics (captum_saliency.py:125-192) for a batch ``[B, L]``:
     attribution -> |attr|/max time mask -> wave*mask, wave*(1-mask) -> three classifier passes.
     ``method="occlusion"`` occludes ``window``-sample windows every ``stride`` samples (default 100 ms / 50 ms at 16 kHz);
-    ``method="shapley_value_sampling"`` / ``"kernel_shap"`` attribute ``window``-sample segments (default n_samples = 25).
+    ``method="shapley_value_sampling"`` / ``"kernel_shap"`` attribute ``window``-sample segments (default n_samples = 25), as do
+    ``"lime"`` (n_samples = 50, the cosine kernel, a Lasso with alpha = 0.01) and ``"feature_permutation"`` (each segment taken
+    from another clip of the batch: it needs two clips or more, ValueError before any GPU work otherwise).
     ``nt_type`` ("smoothgrad", "smoothgrad_sq", "vargrad") wraps the method in NoiseTunnel over ``nt_samples`` noisy copies
     of each clip; ``stdevs`` is the noise's standard deviation in waveform units (Captum's default of 1.0 would drown a
     waveform in [-1, 1]).  Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
+    _check_batch(method, waves)
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
     attr = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs)(x)
@@ -102,6 +117,7 @@ def score_explanations(model, waves, method="input_x_gradient", n_steps=50, wind
     times with ``NoisyPerturbation(stdevs, multiply_by_inputs)`` (``x - stdevs * N(0, 1)``; ``stdevs`` in waveform units, as in
     ``explain_waves``); sensitivity_max re-runs the attribution on ``n_perturb_samples`` copies ``x + U(-perturb_radius,
     perturb_radius)`` and takes the largest relative change in ``norm_ord``."""
+    _check_batch(method, waves)
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
     explain = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs)
