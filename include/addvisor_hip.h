@@ -716,6 +716,13 @@ int advh_conv_taps2d_f16(const advh_taps2d_desc* d, int C, advh_stream_t stream)
  * other C.  advh_conv_taps2d_split_lds_bytes(C) = dynamic LDS per workgroup, -1 for an unsupported C.  */
 int advh_conv_taps2d_split_lds_bytes(int C);
 int advh_conv_taps2d_split(const advh_taps2d_desc* d, int C, int64_t x_lo, int64_t w_lo, int64_t o_lo, advh_stream_t stream);
+/* The 32-channel layer with the U-Net's mask head in its epilogue (d1.block.3 + mask_head, addvisor.py:54-60): instead of storing the
+ * 32-channel map the kernel writes logits[b][h][w] = sum_c y[b,h,w,c] * head_w[c] + head_b and mask = sigmoid(logits), fp32 [B][H][W_]
+ * (logits may be NULL), where y is the split-format value advh_conv_taps2d_split would have stored (same rounding, same range flag)
+ * and the sum runs in advh_unet_head_split's order: the two outputs are bit-identical to that pair of launches.  d->out_h is not
+ * used.  ADVH_EUNSUPPORTED for C != 32, ADVH_EINVAL for a NULL head_w / mask and for what advh_conv_taps2d_split rejects.  */
+int advh_conv_taps2d_split_head(const advh_taps2d_desc* d, int C, int64_t x_lo, int64_t w_lo, const float* head_w, float head_b,
+                                float* mask, float* logits, advh_stream_t stream);
 /* Last decoder stage of the U-Net as ONE line-tile launch: up1 = ConvTranspose2d(64,32,(2,1),stride (2,1)) folded into
  * d1.block.0 = Conv2d(33,32,3,padding 1) + BatchNorm + LeakyReLU (addvisor.py:53-54,78-80).
  *   Xc  coarse map  [B][Hc+2PHc][W_+2PWc][64]  fp16, zero halo (PHc, PWc >= 1)              (y2)
@@ -736,6 +743,15 @@ typedef struct advh_upconv_desc {
 } advh_upconv_desc;
 int advh_upconv21_tile_f16(const advh_upconv_desc* d, advh_stream_t stream);
 int advh_upconv21_tile_lds_bytes(void);
+/* The same stage in the fp32-class mode (csrc/upconv_tile_x3.hip): Xc, Xs, W, out_h are split-format plane pairs, the lo plane xc_lo /
+ * xs_lo / w_lo / o_lo elements behind the hi plane (at least one whole plane, multiples of 8); W per plane as above, [2 row parities][15]
+ * [32][32].  Three MFMAs per fragment pair in the order and K order of the x3 implicit GEMM (gemm.plan_upconv2d): the outputs are
+ * bit-identical to it.  One row parity per workgroup (its weights resident in LDS), tiles of 32 output rows x 16 columns; any Hc >= 1.
+ * Cc = coarse channels, N = output channels: ADVH_EUNSUPPORTED unless (Cc, N) = (64, 32); ADVH_EINVAL for a missing lo plane or a
+ * plane distance that is not a multiple of 8.  advh_upconv21_tile_split_lds_bytes() = dynamic LDS per workgroup.  */
+int advh_upconv21_tile_split_lds_bytes(void);
+int advh_upconv21_tile_split(const advh_upconv_desc* d, int Cc, int N, int64_t xc_lo, int64_t xs_lo, int64_t w_lo, int64_t o_lo,
+                             advh_stream_t stream);
 /* e2.block.0 of the U-Net as a line-tile launch: Conv2d(32, 64, (5,3), stride (2,1), padding (2,1)) + folded BatchNorm +
  * LeakyReLU (addvisor.py:32).  X [B][2Ho+2PHi][W_+2PWi][32] fp16 zero-haloed (PHi >= 2, PWi >= 1);
  * W fp16 [15 taps = kh*3+kw][64 rows][32 ci], row R of a tap = output channel 32 (R>>5) + 8 ((R>>2)&3) + 4 ((R>>4)&1) + (R&3);

@@ -114,6 +114,7 @@ SIGNATURES = {
     "advh_conv_taps2d_f16": (_i, [_p, _i, _p]),
     "advh_conv_taps2d_split_lds_bytes": (_i, [_i]),
     "advh_conv_taps2d_split": (_i, [_p, _i, _i64, _i64, _i64, _p]),
+    "advh_conv_taps2d_split_head": (_i, [_p, _i, _i64, _i64, _p, _f, _p, _p, _p]),
     "advh_upconv21_tile_f16": (_i, [_p, _p]),
     "advh_posconv_tile_f16": (_i, [_p, _p]),
     "advh_conv53s21_tile_f16": (_i, [_p, _p]),
@@ -130,6 +131,8 @@ SIGNATURES = {
     "advh_hifigan_conv_post_split": (_i, [_p, _i64, _p, _f, _p, _i, _i, _i, _i, _i, _p]),
     "advh_unet_head_split": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _f, _p, _p, _p]),
     "advh_upconv21_tile_lds_bytes": (_i, []),
+    "advh_upconv21_tile_split_lds_bytes": (_i, []),
+    "advh_upconv21_tile_split": (_i, [_p, _i, _i, _i64, _i64, _i64, _i64, _p]),
     "advh_bn_stats_split": (_i, [_p, _i64, _p, _p, _p, _p]),
     "advh_bn_apply_split": (_i, [_p, _i64, _p, _p, _f, _p, _i64, _p]),
     "advh_bn_bwd_sums_split": (_i, [_p, _i64, _p, _i64, _p, _p, _f, _p, _p, _p]),

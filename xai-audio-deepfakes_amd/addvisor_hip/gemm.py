@@ -728,6 +728,55 @@ class UpconvTilePlan:
         _lib.check(_lib.lib().advh_upconv21_tile_f16(C.byref(d), stream), "advh_upconv21_tile_f16")
 
 
+def upconv_tile_split_supported(coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor, wc: torch.Tensor, stride, indicator) -> bool:
+    """Geometry of ``advh_upconv21_tile_split``: up1 + d1.block.0 of the U-Net on split-format maps (64 coarse channels, 8-channel
+    skip map carrying the indicator in channel 1, 32 outputs, stride (2, 1)); any height."""
+    return (coarse.split and skip.split and dst.split
+            and tuple(stride) == (2, 1) and tuple(wt.shape) == (64, 32, 2, 1) and tuple(wc.shape) == (32, 33, 3, 3)
+            and coarse.C == 64 and skip.C == 8 and dst.C == 32 and tuple(indicator) == ("skip", 1)
+            and min(coarse.PH, coarse.PW, skip.PH, skip.PW) >= 1
+            and (dst.B, dst.H, dst.W) == (coarse.B, 2 * coarse.H, coarse.W) == (skip.B, skip.H, skip.W))
+
+
+class UpconvSplitTilePlan:
+    """up1 + d1.block.0 as one split-format line-tile launch (csrc/upconv_tile_x3.hip), bit-identical to ``plan_upconv2d``'s x3 GEMM
+    on the same maps: ``compose_upconv_weights`` (fp64) and ``split_planes`` are the single source of the weight planes, in
+    ``plan_upconv2d``'s K order (zero-padded 456 -> 480).  Same ``run`` signature as a GemmPlan."""
+
+    def __init__(self, coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor, bt: torch.Tensor, wc: torch.Tensor,
+                 bc: torch.Tensor, *, slope: float = 0.2, device=None):
+        assert upconv_tile_split_supported(coarse, skip, dst, wt, wc, (2, 1), ("skip", 1))
+        w2, cu0, cu1 = compose_upconv_weights(wt, bt, wc, (2, 1), ("skip", 1))
+        assert (cu0, cu1) == (8, 1) and w2[0].shape == (32, 456)
+        R = np.arange(32)
+        ch = torch.from_numpy(8 * ((R >> 2) & 3) + 4 * ((R >> 4) & 1) + (R & 3))    # MFMA row R carries this output channel
+        full = torch.zeros(2, 32, 480, dtype=torch.float64)
+        for ph in range(2):
+            full[ph, :, :456] = w2[ph]
+        wp = split_planes(full[:, ch].reshape(2, 32, 15, 32).permute(0, 2, 1, 3)).contiguous()     # [2 planes][2 parities][15][32][32]
+        self.w = wp.to(device) if device is not None else wp
+        self.bias = bc.to(torch.float32).contiguous()
+        self.bias = self.bias.to(device) if device is not None else self.bias
+        d = UpconvDesc()
+        d.B, d.Hc, d.W_ = coarse.B, coarse.H, coarse.W
+        d.PHc, d.PWc, d.PHs, d.PWs, d.PHo, d.PWo = coarse.PH, coarse.PW, skip.PH, skip.PW, dst.PH, dst.PW
+        d.act, d.slope = ACT["leaky"], slope
+        self.desc = d
+        self.numels = tuple(2 * f.B * f.Hp * f.Wp * f.C for f in (coarse, skip, dst))
+        self.flops = 2.0 * dst.B * dst.H * dst.W * 32 * (6 * 64 + 9 * 2)
+        self.tile = None
+
+    def run(self, A0: torch.Tensor, A1: torch.Tensor, *, out_h: torch.Tensor, stream: Optional[int] = None):
+        d = self.desc
+        for t, n in zip((A0, A1, out_h), self.numels):
+            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.shape[0] == 2 and t.numel() == n
+        d.Xc, d.Xs, d.W, d.bias, d.out_h = A0.data_ptr(), A1.data_ptr(), self.w.data_ptr(), self.bias.data_ptr(), out_h.data_ptr()
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().advh_upconv21_tile_split(C.byref(d), 64, 32, A0.stride(0), A1.stride(0), self.w.stride(0), out_h.stride(0),
+                                                       stream), "advh_upconv21_tile_split")
+
+
 # ------------------------------------------------------------------------------------------ CPU replay
 def replay_on_cpu(plan: GemmPlan, A0: torch.Tensor, A1: Optional[torch.Tensor], out_numel: int,
                   resid: Optional[torch.Tensor] = None, out_init: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -970,7 +1019,11 @@ def taps2d_split_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor
 
 class Taps2dSplitPlan:
     """One launch of ``advh_conv_taps2d_split``: the fp32-class form of ``Taps2dPlan``, bit-identical to ``plan_conv2d``'s x3 GEMM on
-    the same maps (the weight's split planes are taken from its fp64 / fp32 value exactly as ``GemmPlan`` takes them)."""
+    the same maps (the weight's split planes are taken from its fp64 / fp32 value exactly as ``GemmPlan`` takes them).
+
+    ``attach_head`` (32 channels) turns it into one launch of ``advh_conv_taps2d_split_head``: the U-Net's 1x1 mask head + sigmoid run in
+    the epilogue, ``logits`` / ``mask`` are written and the 32-channel map is not (``run`` then ignores ``out_h``); bit-identical to this
+    plan followed by ``advh_unet_head_split``."""
 
     def __init__(self, src: FMap, dst: FMap, weight: torch.Tensor, bias: Optional[torch.Tensor], *, act: str = "leaky",
                  slope: float = 0.2, device=None):
@@ -987,16 +1040,35 @@ class Taps2dSplitPlan:
         d.act, d.slope = ACT[act], slope
         self.desc = d
         self.flops = 2.0 * dst.B * dst.H * dst.W * Cn * Cn * 9
+        self.head = None
 
-    def run(self, A0: torch.Tensor, A1=None, *, out_h: torch.Tensor, stream: Optional[int] = None):
+    def attach_head(self, head_w: torch.Tensor, head_b: float, mask: torch.Tensor, logits: Optional[torch.Tensor] = None):
+        """``head_w`` fp32 ``[32]``, ``mask`` / ``logits`` fp32 ``[B, H, W]`` on the plan's device; they are written by every ``run``."""
+        d = self.desc
+        assert self.Cn == 32 and head_w.dtype == torch.float32 and head_w.numel() == 32 and head_w.is_contiguous()
+        for t in (mask, logits):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (d.B, d.H, d.W_))
+        self.head = (head_w, float(head_b), mask, logits)
+        self.flops += 2.0 * d.B * d.H * d.W_ * 32
+        return self
+
+    def run(self, A0: torch.Tensor, A1=None, *, out_h: Optional[torch.Tensor] = None, stream: Optional[int] = None):
         d = self.desc
         n = d.B * (d.H + 2 * d.PH) * (d.W_ + 2 * d.PW) * self.Cn
-        for t in (A0, out_h):
+        for t in (A0,) if self.head else (A0, out_h):
             assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.shape[0] == 2 and t.numel() == 2 * n
-        d.X, d.W, d.out_h = A0.data_ptr(), self.w.data_ptr(), out_h.data_ptr()
+        d.X, d.W = A0.data_ptr(), self.w.data_ptr()
         d.bias = self.bias.data_ptr() if self.bias is not None else None
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
+        if self.head:
+            hw, hb, mask, logits = self.head
+            d.out_h = None
+            _lib.check(_lib.lib().advh_conv_taps2d_split_head(C.byref(d), self.Cn, n, self.w.stride(0), hw.data_ptr(), hb, mask.data_ptr(),
+                                                              logits.data_ptr() if logits is not None else None, stream),
+                       "advh_conv_taps2d_split_head")
+            return
+        d.out_h = out_h.data_ptr()
         _lib.check(_lib.lib().advh_conv_taps2d_split(C.byref(d), self.Cn, n, self.w.stride(0), n, stream), "advh_conv_taps2d_split")
 
 

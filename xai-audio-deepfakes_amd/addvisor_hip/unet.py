@@ -53,8 +53,11 @@ class HipUNet:
         ``precision``: "f16" | "f32" (default ``ADDVISOR_PRECISION``, i.e. f32): "f32" is the fp32-class mode -- every map a
         split-format plane pair, every convolution three MFMAs per product (``advh_gemm_desc.split``), weights folded in
         fp64 -- whose ``mask > 0.5`` index set reproduces the reference's fp32 CPU result (addvisor.py:57-60; asserted
-        against tests/golden/unet.npz).  In that mode ``line_tile`` covers the 3x3 32- / 64-channel layers only
-        (``advh_conv_taps2d_split``, bit-identical to the implicit GEMM); the other line-tile kernels are fp16-only."""
+        against tests/golden/unet.npz).  In that mode ``line_tile`` covers the 3x3 32- / 64-channel layers
+        (``advh_conv_taps2d_split``) and, with ``fuse_up``, up1 + d1.block.0 (``advh_upconv21_tile_split``), all bit-identical to
+        the implicit GEMM; the last layer, ``d1.block.3``, runs the 1x1 mask head in its epilogue
+        (``advh_conv_taps2d_split_head``, bit-identical to ``advh_unet_head_split``): the map ``y1`` is then neither written nor
+        allocated.  The other line-tile kernels are fp16-only."""
         _lib.init()
         from .embedder import default_precision
         self.precision = precision or default_precision()
@@ -87,6 +90,27 @@ class HipUNet:
             return G.Taps2dPlan(fs[0], m[dst], w, b, slope=SLOPE, device=self.dev)
         return None
 
+    @property
+    def _fused_head(self) -> bool:
+        """fp32-class mode with line tiles: ``d1.block.3`` carries the mask head, ``y1`` has no storage."""
+        return self.split and self.line_tile
+
+    def _y1(self, B: int, H: int, W: int) -> G.FMap:
+        y1 = G.FMap(B, H, W, 32, 1, 1, split=self.split)
+        return y1 if self._fused_head else y1.alloc(self.dev)
+
+    def _finish(self, key, m, steps) -> dict:
+        B, H, W = key
+        ws = dict(maps=m, steps=steps, mask=torch.empty(B, H, W, dtype=torch.float32, device=self.dev),
+                  logits=torch.empty(B, H, W, dtype=torch.float32, device=self.dev))
+        ws["flops"] = reference_flops(B, H, W)                # the reference formulation's count, not the fused launches'
+        if self._fused_head:
+            last = steps[-1][0]
+            assert isinstance(last, G.Taps2dSplitPlan), "d1.block.3 is a 3x3 32-channel same-geometry layer"
+            last.attach_head(self.head_w, self.head_b, ws["mask"], ws["logits"])
+        self._ws[key] = ws
+        return ws
+
     def _workspace(self, B: int, H: int, W: int) -> dict:
         key = (B, H, W)
         if key in self._ws:
@@ -106,7 +130,7 @@ class HipUNet:
             u4=F(H // 8, W // 2, 256, 1, 1), y4a=F(H // 8, W // 2, 256, 1, 1), y4=F(H // 8, W // 2, 256, 0, 0),
             u3=F(H // 4, W, 128, 1, 1), y3a=F(H // 4, W, 128, 1, 1), y3=F(H // 4, W, 128, 0, 0),
             u2=F(H // 2, W, 64, 1, 1), y2a=F(H // 2, W, 64, 1, 1), y2=F(H // 2, W, 64, 1, 1),
-            u1=F(H, W, 40, 1, 1), y1a=F(H, W, 32, 1, 1), y1=F(H, W, 32, 1, 1),
+            u1=F(H, W, 40, 1, 1), y1a=F(H, W, 32, 1, 1), y1=self._y1(B, H, W),
         )
         steps = []
 
@@ -143,11 +167,7 @@ class HipUNet:
         block(["u2", "x1"], "y2a", "y2", "d2")
         up("y2", "u1", "up1", (2, 1))
         block(["u1"], "y1a", "y1", "d1")
-        ws = dict(maps=m, steps=steps, mask=torch.empty(B, H, W, dtype=torch.float32, device=dev),
-                  logits=torch.empty(B, H, W, dtype=torch.float32, device=dev))
-        ws["flops"] = reference_flops(B, H, W)
-        self._ws[key] = ws
-        return ws
+        return self._finish(key, m, steps)
 
     def _workspace_fused(self, B: int, H: int, W: int) -> dict:
         """Same network with up4+d4, up3+d3, up2+d2, up1+d1 as fused launches: the maps u4..u1 do not exist.  The coarse
@@ -165,7 +185,7 @@ class HipUNet:
             y4a=F(H // 8, W // 2, 256, 1, 1), y4=G.add_indicator(F(H // 8, W // 2, 320, 1, 1), 256),
             y3a=F(H // 4, W, 128, 1, 1), y3=G.add_indicator(F(H // 4, W, 192, 1, 1), 128),
             y2a=F(H // 2, W, 64, 1, 1), y2=F(H // 2, W, 64, 1, 1),
-            xin=G.add_indicator(F(H, W, 8, 1, 1), 1), y1a=F(H, W, 32, 1, 1), y1=F(H, W, 32, 1, 1),
+            xin=G.add_indicator(F(H, W, 8, 1, 1), 1), y1a=F(H, W, 32, 1, 1), y1=self._y1(B, H, W),
         )
         steps = []
 
@@ -187,6 +207,8 @@ class HipUNet:
             wt, bt = sd[up_name + ".weight"].to(self.wdtype), sd[up_name + ".bias"].to(self.wdtype)
             if self.line_tile and not self.split and G.upconv_tile_supported(m[coarse], m[skip], m[mid], wt, wc, stride, indicator):
                 plan = G.UpconvTilePlan(m[coarse], m[skip], m[mid], wt, bt, wc, bc, slope=SLOPE, device=dev)
+            elif self.line_tile and G.upconv_tile_split_supported(m[coarse], m[skip], m[mid], wt, wc, stride, indicator):
+                plan = G.UpconvSplitTilePlan(m[coarse], m[skip], m[mid], wt, bt, wc, bc, slope=SLOPE, device=dev)
             else:
                 plan = G.plan_upconv2d(m[coarse], m[skip], m[mid], wt, bt, wc, bc, stride=stride, coarse_C=coarse_C,
                                        skip_C=skip_C, indicator=indicator, slope=SLOPE, device=dev)
@@ -203,11 +225,7 @@ class HipUNet:
         up_block("y4", "x2", "y3a", "y3", "up3", "d3", (2, 2), 256, 64, ("coarse", 256))
         up_block("y3", "x1", "y2a", "y2", "up2", "d2", (2, 1), 128, 32, ("coarse", 128))
         up_block("y2", "xin", "y1a", "y1", "up1", "d1", (2, 1), 64, 1, ("skip", 1))
-        ws = dict(maps=m, steps=steps, mask=torch.empty(B, H, W, dtype=torch.float32, device=dev),
-                  logits=torch.empty(B, H, W, dtype=torch.float32, device=dev))
-        ws["flops"] = reference_flops(B, H, W)                # the reference formulation's count, not the fused launches'
-        self._ws[(B, H, W)] = ws
-        return ws
+        return self._finish((B, H, W), m, steps)
 
     def flops(self, B: int, H: int, W: int) -> float:
         return self._workspace(B, H, W)["flops"]
@@ -241,7 +259,9 @@ class HipUNet:
             a1 = m[srcs[1]].t if len(srcs) > 1 else None
             plan.run(a0, a1, out_h=m[dst].t)
         y1 = m["y1"]
-        if self.split:
+        if self._fused_head:
+            pass                                               # mask and logits came out of d1.block.3's epilogue
+        elif self.split:
             _lib.check(lib.advh_unet_head_split(y1.t.data_ptr(), y1.t.stride(0), B, H, W, y1.PH, y1.PW, self.head_w.data_ptr(),
                                                 self.head_b, ws["mask"].data_ptr(), ws["logits"].data_ptr(), st), "advh_unet_head_split")
         else:
