@@ -767,6 +767,15 @@ typedef struct advh_convs21_desc {
 } advh_convs21_desc;
 int advh_conv53s21_tile_f16(const advh_convs21_desc* d, advh_stream_t stream);
 int advh_conv53s21_tile_lds_bytes(void);
+/* The same layer in the fp32-class mode (csrc/conv_s21_tile_x3.hip): X, W, out_h are split-format plane pairs, the lo plane x_lo / w_lo /
+ * o_lo elements behind the hi plane (at least one whole plane, multiples of 8).  W per plane [8 k-blocks][64 rows][64]: row R as above,
+ * column kk of k-block kb = element 64 kb + kk of the K order (tap kh*3 + kw: 32 channels) x 15, zero-padded 480 -> 512.  Three MFMAs
+ * per fragment pair in the order and K order of the x3 implicit GEMM (gemm.plan_conv2d): the outputs are bit-identical to it.  16 x 16
+ * output tiles, the weights streamed k-block by k-block through an LDS ring; any Ho >= 1; X and out_h distinct.  Ci = input channels,
+ * N = output channels: ADVH_EUNSUPPORTED unless (Ci, N) = (32, 64); ADVH_EINVAL for a missing lo plane or a plane distance that is not
+ * a multiple of 8.  advh_conv53s21_tile_split_lds_bytes() = dynamic LDS per workgroup.  */
+int advh_conv53s21_tile_split_lds_bytes(void);
+int advh_conv53s21_tile_split(const advh_convs21_desc* d, int Ci, int N, int64_t x_lo, int64_t w_lo, int64_t o_lo, advh_stream_t stream);
 int advh_conv_taps_tile(int C, int ntap, int span);       /* positions per workgroup tile (128/192/256); 0 = does not fit */
 int advh_conv_taps_lds_bytes(int C, int ntap, int span);  /* weights + two line buffers; -1 = does not fit           */
 int advh_conv_taps_f16(const advh_taps_desc* d, int C, advh_stream_t stream);

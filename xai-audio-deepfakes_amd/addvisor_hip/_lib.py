@@ -119,6 +119,8 @@ SIGNATURES = {
     "advh_posconv_tile_f16": (_i, [_p, _p]),
     "advh_conv53s21_tile_f16": (_i, [_p, _p]),
     "advh_conv53s21_tile_lds_bytes": (_i, []),
+    "advh_conv53s21_tile_split_lds_bytes": (_i, []),
+    "advh_conv53s21_tile_split": (_i, [_p, _i, _i, _i64, _i64, _i64, _p]),
     "advh_posconv_tile_lds_bytes": (_i, [_i, _i]),
     "advh_w2v2_frontend_split": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "advh_layernorm_split": (_i, [_p, _i, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _i, _i, _f, _i, _p]),

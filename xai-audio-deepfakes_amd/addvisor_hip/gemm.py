@@ -468,10 +468,15 @@ def plan_conv1d_cl(B: int, P_in: int, P_out: int, L_out: int, weight: torch.Tens
 
 def plan_conv2d(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, bias: Optional[torch.Tensor], *,
                 stride=(1, 1), padding=(1, 1), dilation=(1, 1), act: str = "leaky", slope: float = 0.2,
-                dst_c0: int = 0, device=None) -> GemmPlan:
+                dst_c0: int = 0, device=None, interior_only: bool = False) -> GemmPlan:
     """nn.Conv2d on zero-haloed NHWC maps (addvisor.py:12-60); ``srcs`` are concatenated along channels
     by pointer (torch.cat of addvisor.py:70-80).  Enumerates the padded OUTPUT grid and writes its halo
-    as zeros, so ``dst`` is complete after one launch."""
+    as zeros, so ``dst`` is complete after one launch.
+
+    ``interior_only``: enumerate ``dst``'s interior only (``M = B * H * W``, as ``plan_upconv2d`` does): no halo row goes
+    through the K loop and no halo element is written, so ``dst``'s halo must already be zero and stay so (a map from
+    ``FMap.alloc`` whose only producer is this plan).  K order, weights, tile and epilogue are those of the padded
+    form: every interior value is bit-identical to it."""
     Cout, Cin, KH, KW = weight.shape
     assert sum(s.C for s in srcs) == Cin and len(srcs) <= 2
     sh, sw = stride
@@ -490,16 +495,21 @@ def plan_conv2d(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, bias: Opt
         kt = (taps[:, None] * cc + np.arange(cc)[None, :]).reshape(-1).astype(np.int64) | (s << 31)
         ktabs.append(kt)
         ws.append(weight[:, c_lo:c_lo + f.C].permute(0, 2, 3, 1).reshape(Cout, KH * KW * f.C))
-        c0 = ((-sh * dst.PH + f.PH - ph) * f.Wp + (-sw * dst.PW + f.PW - pw)) * cc
+        # row (0, 0) of the enumeration is dst's first interior pixel, or the corner of its padded grid
+        oh, ow = (0, 0) if interior_only else (dst.PH, dst.PW)
+        c0 = ((-sh * oh + f.PH - ph) * f.Wp + (-sw * ow + f.PW - pw)) * cc
         sources.append(Source(f.Hp * f.Wp * cc, sh * f.Wp * cc, sw * cc, c0))
         c_lo += f.C
     Ct = dst.C
     split = dst.split
     assert all(f.split == split for f in srcs)
-    return GemmPlan(M=B * dst.Hp * dst.Wp, N=Cout, w2=torch.cat(ws, 1)[None] if split else torch.cat(ws, 1)[None].float(), ktab=np.concatenate(ktabs), split=split,
-                    sources=sources, Hg=dst.Hp, Wg=dst.Wp,
-                    window=(dst.PH, dst.PH + dst.H, dst.PW, dst.PW + dst.W), halo_zero=True,
-                    out=(dst.Hp * dst.Wp * Ct, dst.Wp * Ct, Ct, dst_c0), bias=bias, act=act, slope=slope,
+    if interior_only:
+        Hg, Wg, window, o_c0 = dst.H, dst.W, (0, dst.H, 0, dst.W), dst_c0 + (dst.PH * dst.Wp + dst.PW) * Ct
+    else:
+        Hg, Wg, window, o_c0 = dst.Hp, dst.Wp, (dst.PH, dst.PH + dst.H, dst.PW, dst.PW + dst.W), dst_c0
+    return GemmPlan(M=B * Hg * Wg, N=Cout, w2=torch.cat(ws, 1)[None] if split else torch.cat(ws, 1)[None].float(), ktab=np.concatenate(ktabs), split=split,
+                    sources=sources, Hg=Hg, Wg=Wg, window=window, halo_zero=not interior_only,
+                    out=(dst.Hp * dst.Wp * Ct, dst.Wp * Ct, Ct, o_c0), bias=bias, act=act, slope=slope,
                     device=device)
 
 
@@ -674,6 +684,48 @@ class ConvS21TilePlan:
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
         _lib.check(_lib.lib().advh_conv53s21_tile_f16(C.byref(d), stream), "advh_conv53s21_tile_f16")
+
+
+def conv_s21_split_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, stride=(1, 1), padding=(1, 1),
+                             dilation=(1, 1)) -> bool:
+    """Geometry of ``advh_conv53s21_tile_split``: e2.block.0 of the U-Net on split-format maps; any height and width."""
+    return (conv_s21_supported(srcs, dst, weight, stride, padding, dilation) and srcs[0].split and dst.split
+            and srcs[0].B == dst.B)
+
+
+class ConvS21SplitTilePlan:
+    """e2.block.0 as one split-format line-tile launch (csrc/conv_s21_tile_x3.hip), bit-identical to ``plan_conv2d``'s x3 GEMM on the
+    same maps: the weight planes are ``split_planes`` of the same (fp64) values in ``plan_conv2d``'s K order (tap kh * 3 + kw, then
+    channel; zero-padded 480 -> 512), cut into the GEMM's eight 64-deep k-blocks.  Only ``dst``'s interior is written; its halo
+    must already be zero.  Same ``run`` signature as a GemmPlan."""
+
+    def __init__(self, src: FMap, dst: FMap, weight: torch.Tensor, bias: torch.Tensor, *, slope: float = 0.2, device=None):
+        assert conv_s21_split_supported([src], dst, weight, (2, 1), (2, 1))
+        ch = torch.from_numpy(packed_row_channel(64))                          # MFMA row R carries this output channel
+        full = torch.zeros(64, 512, dtype=torch.float64)
+        full[:, :480] = weight.permute(0, 2, 3, 1).reshape(64, 480).double()
+        wp = split_planes(full[ch].reshape(64, 8, 64).permute(1, 0, 2)).contiguous()       # [2 planes][8 k-blocks][64][64]
+        self.w = wp.to(device) if device is not None else wp
+        self.bias = bias.to(torch.float32).contiguous()
+        self.bias = self.bias.to(device) if device is not None else self.bias
+        d = ConvS21Desc()
+        d.B, d.Ho, d.W_ = dst.B, dst.H, dst.W
+        d.PHi, d.PWi, d.PHo, d.PWo = src.PH, src.PW, dst.PH, dst.PW
+        d.act, d.slope = ACT["leaky"], slope
+        self.desc = d
+        self.numels = tuple(2 * f.B * f.Hp * f.Wp * f.C for f in (src, dst))
+        self.flops = 2.0 * dst.B * dst.H * dst.W * 64 * 32 * 15
+        self.tile = None
+
+    def run(self, A0: torch.Tensor, A1=None, *, out_h: torch.Tensor, stream: Optional[int] = None):
+        d = self.desc
+        for t, n in zip((A0, out_h), self.numels):
+            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.shape[0] == 2 and t.numel() == n
+        d.X, d.W, d.bias, d.out_h = A0.data_ptr(), self.w.data_ptr(), self.bias.data_ptr(), out_h.data_ptr()
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().advh_conv53s21_tile_split(C.byref(d), 32, 64, A0.stride(0), self.w.stride(0), out_h.stride(0), stream),
+                   "advh_conv53s21_tile_split")
 
 
 class UpconvDesc(C.Structure):

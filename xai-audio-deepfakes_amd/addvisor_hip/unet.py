@@ -54,10 +54,17 @@ class HipUNet:
         split-format plane pair, every convolution three MFMAs per product (``advh_gemm_desc.split``), weights folded in
         fp64 -- whose ``mask > 0.5`` index set reproduces the reference's fp32 CPU result (addvisor.py:57-60; asserted
         against tests/golden/unet.npz).  In that mode ``line_tile`` covers the 3x3 32- / 64-channel layers
-        (``advh_conv_taps2d_split``) and, with ``fuse_up``, up1 + d1.block.0 (``advh_upconv21_tile_split``), all bit-identical to
-        the implicit GEMM; the last layer, ``d1.block.3``, runs the 1x1 mask head in its epilogue
+        (``advh_conv_taps2d_split``) and, with ``fuse_up``, e2.block.0 (``advh_conv53s21_tile_split``) and up1 + d1.block.0
+        (``advh_upconv21_tile_split``), all bit-identical to the implicit GEMM; the last layer, ``d1.block.3``, runs the 1x1 mask head in its epilogue
         (``advh_conv_taps2d_split_head``, bit-identical to ``advh_unet_head_split``): the map ``y1`` is then neither written nor
-        allocated.  The other line-tile kernels are fp16-only."""
+        allocated.  The other line-tile kernels are fp16-only.
+
+        Every convolution that stays on the implicit GEMM is planned ``interior_only`` (``gemm.plan_conv2d``): no launch
+        computes or writes a halo pixel.  This rests on one invariant: every map comes from ``FMap.alloc`` (``torch.zeros``),
+        has exactly one producer, and no producer stores outside the interior -- the GEMM plans (interior window, no halo
+        zeroing), the line-tile kernels (their epilogues skip ``gy >= H || gx >= W`` and offset by the halo), the stem /
+        pack kernels and ``add_indicator`` (an interior view) all keep to it, so the halos stay the zeros they were
+        allocated as, forward after forward."""
         _lib.init()
         from .embedder import default_precision
         self.precision = precision or default_precision()
@@ -141,7 +148,7 @@ class HipUNet:
                 w = torch.cat([w, w.new_zeros(w.shape[0], cin - w.shape[1], *w.shape[2:])], 1)
             plan = self._line_tile_plan(srcs, dst, m, w, b, kw)
             if plan is None:
-                plan = G.plan_conv2d([m[s] for s in srcs], m[dst], w, b, slope=SLOPE, device=dev, **kw)
+                plan = G.plan_conv2d([m[s] for s in srcs], m[dst], w, b, slope=SLOPE, device=dev, interior_only=True, **kw)
             steps.append((plan, srcs, dst))
 
         def block(srcs, mid, dst, name, **first):              # ConvBlock, addvisor.py:12-25
@@ -194,8 +201,10 @@ class HipUNet:
             plan = self._line_tile_plan(srcs, dst, m, w, b, kw)
             if plan is None and self.line_tile and not self.split and G.conv_s21_supported([m[s] for s in srcs], m[dst], w, **kw):
                 plan = G.ConvS21TilePlan(m[srcs[0]], m[dst], w, b, slope=SLOPE, device=dev)
+            if plan is None and self.line_tile and self.split and G.conv_s21_split_supported([m[s] for s in srcs], m[dst], w, **kw):
+                plan = G.ConvS21SplitTilePlan(m[srcs[0]], m[dst], w, b, slope=SLOPE, device=dev)
             if plan is None:
-                plan = G.plan_conv2d([m[s] for s in srcs], m[dst], w, b, slope=SLOPE, device=dev, **kw)
+                plan = G.plan_conv2d([m[s] for s in srcs], m[dst], w, b, slope=SLOPE, device=dev, interior_only=True, **kw)
             steps.append((plan, srcs, dst))
 
         def block(srcs, mid, dst, name, **first):
