@@ -31,24 +31,16 @@ for plan, srcs, dst in ws["steps"]:
     e1.record(); e1.synchronize()
     ms = e0.elapsed_time(e1) / 5
     tot += ms
-    kind = ("taps2d" if isinstance(plan, G.Taps2dPlan) else "taps2d_x3+head" if getattr(plan, "head", None) else "taps2d_x3" if isinstance(plan, G.Taps2dSplitPlan)
-            else "upconv21" if isinstance(plan, G.UpconvTilePlan) else "upconv21_x3" if isinstance(plan, G.UpconvSplitTilePlan)
-            else "conv53s21" if isinstance(plan, G.ConvS21TilePlan) else "conv53s21_x3" if isinstance(plan, G.ConvS21SplitTilePlan)
-            else G.TILE_NAMES[plan.tile] + ("*" if isinstance(plan, G.PlanGroup) else ""))
+    kind = getattr(plan, "kind", None) or G.TILE_NAMES[plan.tile] + ("*" if isinstance(plan, G.PlanGroup) else "")
+    kind += "+head" if getattr(plan, "head", None) else ""
     print(f"{'+'.join(srcs):8s} -> {dst:4s} {kind:14s} {ms*1e3:8.1f} us  {plan.flops/ms/1e9:7.1f} TFLOP/s  ({plan.flops/1e9:6.1f} GF)")
 print(f"total GEMM-shaped layers {tot:.3f} ms")
 if AB:
-    new_conv2d, new_s21 = G.plan_conv2d, G.conv_s21_split_supported
-
     def build(padded):
         """The network with e2.block.0 on the implicit GEMM and the GEMM plans padded (the previous form) or interior-only."""
-        G.plan_conv2d = (lambda *a, **k: new_conv2d(*a, **{**k, "interior_only": False})) if padded else new_conv2d
-        G.conv_s21_split_supported = lambda *a, **k: False
-        try:
-            n = HipUNet(syn.unet_weights(), dev, fuse_up=net.fuse_up, precision=net.precision)
-            n.forward(mag); torch.cuda.synchronize()
-        finally:
-            G.plan_conv2d, G.conv_s21_split_supported = new_conv2d, new_s21
+        n = HipUNet(syn.unet_weights(), dev, fuse_up=net.fuse_up, precision=net.precision)
+        n.conv_choice.update(s21_tile=False, interior_only=not padded)
+        n.forward(mag); torch.cuda.synchronize()
         return n, n._workspace(B, 512, 196)
 
     old, wo = build(True)

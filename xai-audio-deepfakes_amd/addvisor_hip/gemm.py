@@ -642,6 +642,10 @@ def plan_upconv2d(coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor, bt: tor
     return PlanGroup(plans, flops)
 
 
+def _to(device, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return t if t is None or device is None else t.to(device)
+
+
 class ConvS21Desc(C.Structure):
     _fields_ = [("X", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("out_h", C.c_void_p), ("B", C.c_int),
                 ("Ho", C.c_int), ("W_", C.c_int), ("PHi", C.c_int), ("PWi", C.c_int), ("PHo", C.c_int), ("PWo", C.c_int),
@@ -656,36 +660,6 @@ def conv_s21_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, st
             and srcs[0].H == 2 * dst.H and srcs[0].W == dst.W)
 
 
-class ConvS21TilePlan:
-    """e2.block.0 as one LDS line-tile launch (csrc/conv_s21_tile.hip); same ``run`` signature as a GemmPlan."""
-
-    def __init__(self, src: FMap, dst: FMap, weight: torch.Tensor, bias: torch.Tensor, *, slope: float = 0.2, device=None):
-        assert conv_s21_supported([src], dst, weight, (2, 1), (2, 1))
-        R = np.arange(64)
-        ch = 32 * (R >> 5) + 8 * ((R >> 2) & 3) + 4 * ((R >> 4) & 1) + (R & 3)      # MFMA row R carries this output channel
-        wp = weight.float()[torch.from_numpy(ch)].permute(2, 3, 0, 1).reshape(15, 64, 32).to(torch.float16).contiguous()
-        self.w = wp.to(device) if device is not None else wp
-        self.bias = bias.to(torch.float32).contiguous()
-        self.bias = self.bias.to(device) if device is not None else self.bias
-        d = ConvS21Desc()
-        d.B, d.Ho, d.W_ = dst.B, dst.H, dst.W
-        d.PHi, d.PWi, d.PHo, d.PWo = src.PH, src.PW, dst.PH, dst.PW
-        d.act, d.slope = ACT["leaky"], slope
-        self.desc = d
-        self.numels = (src.B * src.Hp * src.Wp * 32, dst.B * dst.Hp * dst.Wp * 64)
-        self.flops = 2.0 * dst.B * dst.H * dst.W * 64 * 32 * 15
-        self.tile = None
-
-    def run(self, A0: torch.Tensor, A1=None, *, out_h: torch.Tensor, stream: Optional[int] = None):
-        d = self.desc
-        for t, n in zip((A0, out_h), self.numels):
-            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.numel() == n
-        d.X, d.W, d.bias, d.out_h = A0.data_ptr(), self.w.data_ptr(), self.bias.data_ptr(), out_h.data_ptr()
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().advh_conv53s21_tile_f16(C.byref(d), stream), "advh_conv53s21_tile_f16")
-
-
 def conv_s21_split_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, stride=(1, 1), padding=(1, 1),
                              dilation=(1, 1)) -> bool:
     """Geometry of ``advh_conv53s21_tile_split``: e2.block.0 of the U-Net on split-format maps; any height and width."""
@@ -693,37 +667,60 @@ def conv_s21_split_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tens
             and srcs[0].B == dst.B)
 
 
-class ConvS21SplitTilePlan:
-    """e2.block.0 as one split-format line-tile launch (csrc/conv_s21_tile_x3.hip), bit-identical to ``plan_conv2d``'s x3 GEMM on the
-    same maps: the weight planes are ``split_planes`` of the same (fp64) values in ``plan_conv2d``'s K order (tap kh * 3 + kw, then
-    channel; zero-padded 480 -> 512), cut into the GEMM's eight 64-deep k-blocks.  Only ``dst``'s interior is written; its halo
-    must already be zero.  Same ``run`` signature as a GemmPlan."""
+class _ConvS21Tile:
+    """e2.block.0 as one LDS line-tile launch; same ``run`` signature as a GemmPlan.  Only ``dst``'s interior is written; its halo
+    must already be zero.  A variant states ``kind``, ``planes`` (tensors are ``planes`` x the map), ``supported``, ``pack`` (the
+    weight operand from its ``[64 MFMA rows, 480]`` matrix in ``plan_conv2d``'s K order: tap kh * 3 + kw, then channel) and ``launch``."""
+    tile = None
 
     def __init__(self, src: FMap, dst: FMap, weight: torch.Tensor, bias: torch.Tensor, *, slope: float = 0.2, device=None):
-        assert conv_s21_split_supported([src], dst, weight, (2, 1), (2, 1))
+        assert self.supported([src], dst, weight, (2, 1), (2, 1))
         ch = torch.from_numpy(packed_row_channel(64))                          # MFMA row R carries this output channel
-        full = torch.zeros(64, 512, dtype=torch.float64)
-        full[:, :480] = weight.permute(0, 2, 3, 1).reshape(64, 480).double()
-        wp = split_planes(full[ch].reshape(64, 8, 64).permute(1, 0, 2)).contiguous()       # [2 planes][8 k-blocks][64][64]
-        self.w = wp.to(device) if device is not None else wp
-        self.bias = bias.to(torch.float32).contiguous()
-        self.bias = self.bias.to(device) if device is not None else self.bias
+        self.w = _to(device, self.pack(weight.permute(0, 2, 3, 1).reshape(64, 480)[ch]).contiguous())
+        self.bias = _to(device, bias.to(torch.float32).contiguous())
         d = ConvS21Desc()
         d.B, d.Ho, d.W_ = dst.B, dst.H, dst.W
         d.PHi, d.PWi, d.PHo, d.PWo = src.PH, src.PW, dst.PH, dst.PW
         d.act, d.slope = ACT["leaky"], slope
         self.desc = d
-        self.numels = tuple(2 * f.B * f.Hp * f.Wp * f.C for f in (src, dst))
+        self.numels = tuple(self.planes * f.B * f.Hp * f.Wp * f.C for f in (src, dst))
         self.flops = 2.0 * dst.B * dst.H * dst.W * 64 * 32 * 15
-        self.tile = None
 
     def run(self, A0: torch.Tensor, A1=None, *, out_h: torch.Tensor, stream: Optional[int] = None):
         d = self.desc
         for t, n in zip((A0, out_h), self.numels):
-            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.shape[0] == 2 and t.numel() == n
+            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.numel() == n and (t.shape[0] == 2 or self.planes == 1)
         d.X, d.W, d.bias, d.out_h = A0.data_ptr(), self.w.data_ptr(), self.bias.data_ptr(), out_h.data_ptr()
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
+        self.launch(d, A0, out_h, stream)
+
+
+class ConvS21TilePlan(_ConvS21Tile):
+    """``advh_conv53s21_tile_f16`` (csrc/conv_s21_tile.hip): fp16 weights ``[15 taps][64][32]``."""
+    kind, planes, supported = "conv53s21", 1, staticmethod(conv_s21_supported)
+
+    @staticmethod
+    def pack(rows):
+        return rows.float().reshape(64, 15, 32).permute(1, 0, 2).to(torch.float16)
+
+    def launch(self, d, A0, out_h, stream):
+        _lib.check(_lib.lib().advh_conv53s21_tile_f16(C.byref(d), stream), "advh_conv53s21_tile_f16")
+
+
+class ConvS21SplitTilePlan(_ConvS21Tile):
+    """``advh_conv53s21_tile_split`` (csrc/conv_s21_tile_x3.hip), bit-identical to ``plan_conv2d``'s x3 GEMM on the same maps: the
+    weight planes are ``split_planes`` of the same (fp64) values, zero-padded 480 -> 512 and cut into the GEMM's eight 64-deep
+    k-blocks: ``[2 planes][8 k-blocks][64][64]``."""
+    kind, planes, supported = "conv53s21_x3", 2, staticmethod(conv_s21_split_supported)
+
+    @staticmethod
+    def pack(rows):
+        full = torch.zeros(64, 512, dtype=torch.float64)
+        full[:, :480] = rows.double()
+        return split_planes(full.reshape(64, 8, 64).permute(1, 0, 2))
+
+    def launch(self, d, A0, out_h, stream):
         _lib.check(_lib.lib().advh_conv53s21_tile_split(C.byref(d), 32, 64, A0.stride(0), self.w.stride(0), out_h.stride(0), stream),
                    "advh_conv53s21_tile_split")
 
@@ -742,44 +739,6 @@ def upconv_tile_supported(coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor,
             and min(coarse.PH, coarse.PW, skip.PH, skip.PW) >= 1)
 
 
-class UpconvTilePlan:
-    """up1 + d1.block.0 as one LDS line-tile launch (csrc/upconv_tile.hip); same ``run`` signature as a GemmPlan."""
-
-    def __init__(self, coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor, bt: torch.Tensor, wc: torch.Tensor,
-                 bc: torch.Tensor, *, slope: float = 0.2, device=None):
-        assert upconv_tile_supported(coarse, skip, dst, wt, wc, (2, 1), ("skip", 1))
-        w2, cu0, cu1 = compose_upconv_weights(wt, bt, wc, (2, 1), ("skip", 1))
-        assert (cu0, cu1) == (8, 1) and w2[0].shape == (32, 456)
-        R = np.arange(32)
-        ch = 8 * ((R >> 2) & 3) + 4 * ((R >> 4) & 1) + (R & 3)           # MFMA row R carries this output channel
-        wp = torch.zeros(2, 15, 32, 32, dtype=torch.float16)
-        for ph in range(2):
-            full = torch.zeros(32, 480, dtype=torch.float64)
-            full[:, :456] = w2[ph]
-            wp[ph] = full[torch.from_numpy(ch)].reshape(32, 15, 32).permute(1, 0, 2).to(torch.float16)
-        self.w = wp.contiguous().to(device) if device is not None else wp.contiguous()
-        self.bias = bc.to(torch.float32).contiguous()
-        self.bias = self.bias.to(device) if device is not None else self.bias
-        d = UpconvDesc()
-        d.B, d.Hc, d.W_ = coarse.B, coarse.H, coarse.W
-        d.PHc, d.PWc, d.PHs, d.PWs, d.PHo, d.PWo = coarse.PH, coarse.PW, skip.PH, skip.PW, dst.PH, dst.PW
-        d.act, d.slope = ACT["leaky"], slope
-        self.desc = d
-        self.numels = (coarse.t.numel() if coarse.t is not None else 0, skip.t.numel() if skip.t is not None else 0,
-                       dst.t.numel() if dst.t is not None else 0)
-        self.flops = 2.0 * dst.B * dst.H * dst.W * 32 * (6 * 64 + 9 * 2)
-        self.tile = None
-
-    def run(self, A0: torch.Tensor, A1: torch.Tensor, *, out_h: torch.Tensor, stream: Optional[int] = None):
-        d = self.desc
-        for t, n in zip((A0, A1, out_h), self.numels):
-            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and (n == 0 or t.numel() == n)
-        d.Xc, d.Xs, d.W, d.bias, d.out_h = A0.data_ptr(), A1.data_ptr(), self.w.data_ptr(), self.bias.data_ptr(), out_h.data_ptr()
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().advh_upconv21_tile_f16(C.byref(d), stream), "advh_upconv21_tile_f16")
-
-
 def upconv_tile_split_supported(coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor, wc: torch.Tensor, stride, indicator) -> bool:
     """Geometry of ``advh_upconv21_tile_split``: up1 + d1.block.0 of the U-Net on split-format maps (64 coarse channels, 8-channel
     skip map carrying the indicator in channel 1, 32 outputs, stride (2, 1)); any height."""
@@ -790,41 +749,58 @@ def upconv_tile_split_supported(coarse: FMap, skip: FMap, dst: FMap, wt: torch.T
             and (dst.B, dst.H, dst.W) == (coarse.B, 2 * coarse.H, coarse.W) == (skip.B, skip.H, skip.W))
 
 
-class UpconvSplitTilePlan:
-    """up1 + d1.block.0 as one split-format line-tile launch (csrc/upconv_tile_x3.hip), bit-identical to ``plan_upconv2d``'s x3 GEMM
-    on the same maps: ``compose_upconv_weights`` (fp64) and ``split_planes`` are the single source of the weight planes, in
-    ``plan_upconv2d``'s K order (zero-padded 456 -> 480).  Same ``run`` signature as a GemmPlan."""
+class _UpconvTile:
+    """up1 + d1.block.0 as one LDS line-tile launch; same ``run`` signature as a GemmPlan.  ``compose_upconv_weights`` (fp64) is the
+    single source of the weight, ``[2 row parities][15 k-steps][32 MFMA rows][32]`` in ``plan_upconv2d``'s K order (zero-padded
+    456 -> 480).  A variant states ``kind``, ``planes``, ``supported``, ``round`` (that weight to fp16 operands) and ``launch``."""
+    tile = None
 
     def __init__(self, coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor, bt: torch.Tensor, wc: torch.Tensor,
                  bc: torch.Tensor, *, slope: float = 0.2, device=None):
-        assert upconv_tile_split_supported(coarse, skip, dst, wt, wc, (2, 1), ("skip", 1))
+        assert self.supported(coarse, skip, dst, wt, wc, (2, 1), ("skip", 1))
         w2, cu0, cu1 = compose_upconv_weights(wt, bt, wc, (2, 1), ("skip", 1))
         assert (cu0, cu1) == (8, 1) and w2[0].shape == (32, 456)
-        R = np.arange(32)
-        ch = torch.from_numpy(8 * ((R >> 2) & 3) + 4 * ((R >> 4) & 1) + (R & 3))    # MFMA row R carries this output channel
+        ch = torch.from_numpy(packed_row_channel(32))                          # MFMA row R carries this output channel
         full = torch.zeros(2, 32, 480, dtype=torch.float64)
         for ph in range(2):
             full[ph, :, :456] = w2[ph]
-        wp = split_planes(full[:, ch].reshape(2, 32, 15, 32).permute(0, 2, 1, 3)).contiguous()     # [2 planes][2 parities][15][32][32]
-        self.w = wp.to(device) if device is not None else wp
-        self.bias = bc.to(torch.float32).contiguous()
-        self.bias = self.bias.to(device) if device is not None else self.bias
+        self.w = _to(device, self.round(full[:, ch].reshape(2, 32, 15, 32).permute(0, 2, 1, 3)).contiguous())
+        self.bias = _to(device, bc.to(torch.float32).contiguous())
         d = UpconvDesc()
         d.B, d.Hc, d.W_ = coarse.B, coarse.H, coarse.W
         d.PHc, d.PWc, d.PHs, d.PWs, d.PHo, d.PWo = coarse.PH, coarse.PW, skip.PH, skip.PW, dst.PH, dst.PW
         d.act, d.slope = ACT["leaky"], slope
         self.desc = d
-        self.numels = tuple(2 * f.B * f.Hp * f.Wp * f.C for f in (coarse, skip, dst))
+        self.numels = tuple(self.planes * f.B * f.Hp * f.Wp * f.C for f in (coarse, skip, dst))
         self.flops = 2.0 * dst.B * dst.H * dst.W * 32 * (6 * 64 + 9 * 2)
-        self.tile = None
 
     def run(self, A0: torch.Tensor, A1: torch.Tensor, *, out_h: torch.Tensor, stream: Optional[int] = None):
         d = self.desc
         for t, n in zip((A0, A1, out_h), self.numels):
-            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.shape[0] == 2 and t.numel() == n
+            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.numel() == n and (t.shape[0] == 2 or self.planes == 1)
         d.Xc, d.Xs, d.W, d.bias, d.out_h = A0.data_ptr(), A1.data_ptr(), self.w.data_ptr(), self.bias.data_ptr(), out_h.data_ptr()
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
+        self.launch(d, A0, A1, out_h, stream)
+
+
+class UpconvTilePlan(_UpconvTile):
+    """``advh_upconv21_tile_f16`` (csrc/upconv_tile.hip)."""
+    kind, planes, supported = "upconv21", 1, staticmethod(upconv_tile_supported)
+
+    @staticmethod
+    def round(w):
+        return w.to(torch.float16)
+
+    def launch(self, d, A0, A1, out_h, stream):
+        _lib.check(_lib.lib().advh_upconv21_tile_f16(C.byref(d), stream), "advh_upconv21_tile_f16")
+
+
+class UpconvSplitTilePlan(_UpconvTile):
+    """``advh_upconv21_tile_split`` (csrc/upconv_tile_x3.hip), bit-identical to ``plan_upconv2d``'s x3 GEMM on the same maps."""
+    kind, planes, supported, round = "upconv21_x3", 2, staticmethod(upconv_tile_split_supported), staticmethod(split_planes)
+
+    def launch(self, d, A0, A1, out_h, stream):
         _lib.check(_lib.lib().advh_upconv21_tile_split(C.byref(d), 64, 32, A0.stride(0), A1.stride(0), self.w.stride(0), out_h.stride(0),
                                                        stream), "advh_upconv21_tile_split")
 
@@ -1031,37 +1007,6 @@ def taps2d_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, stri
             and (s.B, s.H, s.W, s.PH, s.PW) == (dst.B, dst.H, dst.W, dst.PH, dst.PW))
 
 
-class Taps2dPlan:
-    """One launch of ``advh_conv_taps2d_f16`` (same call shape as ``GemmPlan.run`` for the U-Net step list)."""
-
-    def __init__(self, src: FMap, dst: FMap, weight: torch.Tensor, bias: Optional[torch.Tensor], *, act: str = "leaky",
-                 slope: float = 0.2, device=None):
-        assert taps2d_supported([src], dst, weight)
-        Cn = weight.shape[0]
-        self.Cn = Cn
-        self.w = weight.permute(2, 3, 0, 1).reshape(9, Cn, Cn).to(torch.float16).contiguous()      # [kh*3+kw][co][ci]
-        self.bias = None if bias is None else bias.to(torch.float32).contiguous()
-        if device is not None:
-            self.w = self.w.to(device)
-            self.bias = None if self.bias is None else self.bias.to(device)
-        d = Taps2dDesc()
-        d.B, d.H, d.W_, d.PH, d.PW = dst.B, dst.H, dst.W, dst.PH, dst.PW
-        d.act, d.slope = ACT[act], slope
-        self.desc = d
-        self.flops = 2.0 * dst.B * dst.H * dst.W * Cn * Cn * 9
-
-    def run(self, A0: torch.Tensor, A1=None, *, out_h: torch.Tensor, stream: Optional[int] = None):
-        d = self.desc
-        n = d.B * (d.H + 2 * d.PH) * (d.W_ + 2 * d.PW) * self.Cn
-        for t in (A0, out_h):
-            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.numel() == n
-        d.X, d.W, d.out_h = A0.data_ptr(), self.w.data_ptr(), out_h.data_ptr()
-        d.bias = self.bias.data_ptr() if self.bias is not None else None
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().advh_conv_taps2d_f16(C.byref(d), self.Cn, stream), "advh_conv_taps2d_f16")
-
-
 def taps2d_split_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, stride=(1, 1), padding=(1, 1),
                            dilation=(1, 1)) -> bool:
     """The layers of ``taps2d_supported`` on split-format maps: the ones ``advh_conv_taps2d_split`` takes."""
@@ -1069,30 +1014,57 @@ def taps2d_split_supported(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor
             and taps2d_supported(srcs, dst, weight, stride=stride, padding=padding, dilation=dilation))
 
 
-class Taps2dSplitPlan:
-    """One launch of ``advh_conv_taps2d_split``: the fp32-class form of ``Taps2dPlan``, bit-identical to ``plan_conv2d``'s x3 GEMM on
-    the same maps (the weight's split planes are taken from its fp64 / fp32 value exactly as ``GemmPlan`` takes them).
-
-    ``attach_head`` (32 channels) turns it into one launch of ``advh_conv_taps2d_split_head``: the U-Net's 1x1 mask head + sigmoid run in
-    the epilogue, ``logits`` / ``mask`` are written and the 32-channel map is not (``run`` then ignores ``out_h``); bit-identical to this
-    plan followed by ``advh_unet_head_split``."""
+class _Taps2d:
+    """A 3x3 same-geometry layer as one LDS line-tile launch (same call shape as ``GemmPlan.run`` for the U-Net step list); weights
+    ``[kh*3+kw][co][ci]``.  A variant states ``kind``, ``planes``, ``supported``, ``round`` (that weight to fp16 operands) and ``launch``."""
+    head = None                  # only the split form can carry the mask head (``Taps2dSplitPlan.attach_head``)
 
     def __init__(self, src: FMap, dst: FMap, weight: torch.Tensor, bias: Optional[torch.Tensor], *, act: str = "leaky",
                  slope: float = 0.2, device=None):
-        assert taps2d_split_supported([src], dst, weight)
-        Cn = weight.shape[0]
-        self.Cn = Cn
-        self.w = split_planes(weight.permute(2, 3, 0, 1).reshape(9, Cn, Cn)).contiguous()      # [2][kh*3+kw][co][ci]
-        self.bias = None if bias is None else bias.to(torch.float32).contiguous()
-        if device is not None:
-            self.w = self.w.to(device)
-            self.bias = None if self.bias is None else self.bias.to(device)
+        assert self.supported([src], dst, weight)
+        Cn = self.Cn = weight.shape[0]
+        self.w = _to(device, self.round(weight.permute(2, 3, 0, 1).reshape(9, Cn, Cn)).contiguous())
+        self.bias = _to(device, None if bias is None else bias.to(torch.float32).contiguous())
         d = Taps2dDesc()
         d.B, d.H, d.W_, d.PH, d.PW = dst.B, dst.H, dst.W, dst.PH, dst.PW
         d.act, d.slope = ACT[act], slope
         self.desc = d
+        self.pitch = dst.B * dst.Hp * dst.Wp * Cn              # elements of one plane of either map
+        self.numel = self.planes * self.pitch
         self.flops = 2.0 * dst.B * dst.H * dst.W * Cn * Cn * 9
-        self.head = None
+
+    def run(self, A0: torch.Tensor, A1=None, *, out_h: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+        d = self.desc
+        for t in (A0,) if self.head else (A0, out_h):         # with the head attached ``out_h`` is ignored: the map is not written
+            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.numel() == self.numel and (t.shape[0] == 2 or self.planes == 1)
+        d.X, d.W = A0.data_ptr(), self.w.data_ptr()
+        d.bias = self.bias.data_ptr() if self.bias is not None else None
+        d.out_h = None if self.head else out_h.data_ptr()
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        self.launch(d, stream)
+
+
+class Taps2dPlan(_Taps2d):
+    """``advh_conv_taps2d_f16``."""
+    kind, planes, supported = "taps2d", 1, staticmethod(taps2d_supported)
+
+    @staticmethod
+    def round(w):
+        return w.to(torch.float16)
+
+    def launch(self, d, stream):
+        _lib.check(_lib.lib().advh_conv_taps2d_f16(C.byref(d), self.Cn, stream), "advh_conv_taps2d_f16")
+
+
+class Taps2dSplitPlan(_Taps2d):
+    """``advh_conv_taps2d_split``: the fp32-class form of ``Taps2dPlan``, bit-identical to ``plan_conv2d``'s x3 GEMM on the same maps
+    (the weight's split planes are taken from its fp64 / fp32 value exactly as ``GemmPlan`` takes them).
+
+    ``attach_head`` (32 channels) turns it into one launch of ``advh_conv_taps2d_split_head``: the U-Net's 1x1 mask head + sigmoid run in
+    the epilogue, ``logits`` / ``mask`` are written and the 32-channel map is not (``run`` then ignores ``out_h``); bit-identical to this
+    plan followed by ``advh_unet_head_split``."""
+    kind, planes, supported, round = "taps2d_x3", 2, staticmethod(taps2d_split_supported), staticmethod(split_planes)
 
     def attach_head(self, head_w: torch.Tensor, head_b: float, mask: torch.Tensor, logits: Optional[torch.Tensor] = None):
         """``head_w`` fp32 ``[32]``, ``mask`` / ``logits`` fp32 ``[B, H, W]`` on the plan's device; they are written by every ``run``."""
@@ -1104,24 +1076,46 @@ class Taps2dSplitPlan:
         self.flops += 2.0 * d.B * d.H * d.W_ * 32
         return self
 
-    def run(self, A0: torch.Tensor, A1=None, *, out_h: Optional[torch.Tensor] = None, stream: Optional[int] = None):
-        d = self.desc
-        n = d.B * (d.H + 2 * d.PH) * (d.W_ + 2 * d.PW) * self.Cn
-        for t in (A0,) if self.head else (A0, out_h):
-            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.shape[0] == 2 and t.numel() == 2 * n
-        d.X, d.W = A0.data_ptr(), self.w.data_ptr()
-        d.bias = self.bias.data_ptr() if self.bias is not None else None
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
+    def launch(self, d, stream):
+        n = self.pitch                                         # the lo plane of a map lies one plane behind its hi plane
         if self.head:
             hw, hb, mask, logits = self.head
-            d.out_h = None
             _lib.check(_lib.lib().advh_conv_taps2d_split_head(C.byref(d), self.Cn, n, self.w.stride(0), hw.data_ptr(), hb, mask.data_ptr(),
                                                               logits.data_ptr() if logits is not None else None, stream),
                        "advh_conv_taps2d_split_head")
-            return
-        d.out_h = out_h.data_ptr()
-        _lib.check(_lib.lib().advh_conv_taps2d_split(C.byref(d), self.Cn, n, self.w.stride(0), n, stream), "advh_conv_taps2d_split")
+        else:
+            _lib.check(_lib.lib().advh_conv_taps2d_split(C.byref(d), self.Cn, n, self.w.stride(0), n, stream), "advh_conv_taps2d_split")
+
+
+# ------------------------------------------------------------------------------------ which kernel a U-Net layer gets
+def select_conv2d(srcs: Sequence[FMap], dst: FMap, weight: torch.Tensor, bias: Optional[torch.Tensor], *, line_tile: bool,
+                  s21_tile: bool = True, interior_only: bool = True, stride=(1, 1), padding=(1, 1), dilation=(1, 1),
+                  slope: float = 0.2, device=None):
+    """The plan of one inference U-Net convolution (the maps need no storage).  With ``line_tile``: the 3x3 same-geometry tile of a
+    32- / 64-channel layer, else -- if ``s21_tile`` -- e2.block.0's tile, each in the form of the maps' format (fp16 or split).  Every
+    other layer runs the implicit GEMM (``plan_conv2d``, interior rows only unless ``interior_only=False``).
+
+    ``s21_tile=False`` keeps e2.block.0 on the GEMM whatever ``line_tile`` says.  ``HipUNet`` passes ``s21_tile=fuse_up``: that tile is
+    dispatched on the network with fused up-convolutions only; the unfused network keeps the GEMM there."""
+    geom = dict(stride=stride, padding=padding, dilation=dilation)
+    if line_tile:
+        taps, s21 = (Taps2dSplitPlan, ConvS21SplitTilePlan) if dst.split else (Taps2dPlan, ConvS21TilePlan)
+        if taps.supported(srcs, dst, weight, **geom):
+            return taps(srcs[0], dst, weight, bias, slope=slope, device=device)
+        if s21_tile and s21.supported(srcs, dst, weight, **geom):
+            return s21(srcs[0], dst, weight, bias, slope=slope, device=device)
+    return plan_conv2d(srcs, dst, weight, bias, slope=slope, device=device, interior_only=interior_only, **geom)
+
+
+def select_upconv2d(coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor, bt: torch.Tensor, wc: torch.Tensor, bc: torch.Tensor, *,
+                    line_tile: bool, stride, coarse_C: int, skip_C: int, indicator: Tuple[str, int], slope: float = 0.2, device=None):
+    """The plan of one fused up-convolution of the inference U-Net (``plan_upconv2d``'s arguments; the maps need no storage): with
+    ``line_tile`` up1 + d1.block.0's tile in the form of the maps' format, else -- and for every other stage -- the implicit GEMM."""
+    tile = UpconvSplitTilePlan if dst.split else UpconvTilePlan
+    if line_tile and tile.supported(coarse, skip, dst, wt, wc, stride, indicator):
+        return tile(coarse, skip, dst, wt, bt, wc, bc, slope=slope, device=device)
+    return plan_upconv2d(coarse, skip, dst, wt, bt, wc, bc, stride=stride, coarse_C=coarse_C, skip_C=skip_C, indicator=indicator,
+                         slope=slope, device=device)
 
 
 class ResblockDesc(C.Structure):

@@ -47,17 +47,17 @@ class HipUNet:
 
     def __init__(self, sd: Dict[str, torch.Tensor], device, line_tile: Optional[bool] = None, fuse_up: Optional[bool] = None,
                  precision: Optional[str] = None):
-        """``line_tile``: run the 3x3 32- / 64-channel same-geometry layers on the weights-in-LDS kernel
-        (``advh_conv_taps2d_f16``) instead of the implicit GEMM.  ``fuse_up``: fold every ConvTranspose2d into the
-        convolution that follows it (``gemm.plan_upconv2d``) so the up-sampled maps are never written.
+        """``line_tile``: run the layers that have an LDS line-tile kernel on it instead of the implicit GEMM; which layers those are
+        is decided in one place, ``gemm.select_conv2d`` / ``gemm.select_upconv2d`` (the 3x3 32- / 64-channel same-geometry layers
+        and, with ``fuse_up``, e2.block.0 and up1 + d1.block.0; fp16 and split-format kernels, the latter bit-identical to the
+        implicit GEMM).  ``fuse_up``: fold every ConvTranspose2d into the convolution that follows it (``gemm.plan_upconv2d``) so
+        the up-sampled maps are never written.
         ``precision``: "f16" | "f32" (default ``ADDVISOR_PRECISION``, i.e. f32): "f32" is the fp32-class mode -- every map a
         split-format plane pair, every convolution three MFMAs per product (``advh_gemm_desc.split``), weights folded in
         fp64 -- whose ``mask > 0.5`` index set reproduces the reference's fp32 CPU result (addvisor.py:57-60; asserted
-        against tests/golden/unet.npz).  In that mode ``line_tile`` covers the 3x3 32- / 64-channel layers
-        (``advh_conv_taps2d_split``) and, with ``fuse_up``, e2.block.0 (``advh_conv53s21_tile_split``) and up1 + d1.block.0
-        (``advh_upconv21_tile_split``), all bit-identical to the implicit GEMM; the last layer, ``d1.block.3``, runs the 1x1 mask head in its epilogue
-        (``advh_conv_taps2d_split_head``, bit-identical to ``advh_unet_head_split``): the map ``y1`` is then neither written nor
-        allocated.  The other line-tile kernels are fp16-only.
+        against tests/golden/unet.npz).  In that mode with ``line_tile`` the last layer, ``d1.block.3``, runs the 1x1 mask head in
+        its epilogue (``advh_conv_taps2d_split_head``, bit-identical to ``advh_unet_head_split``): the map ``y1`` is then neither
+        written nor allocated.
 
         Every convolution that stays on the implicit GEMM is planned ``interior_only`` (``gemm.plan_conv2d``): no launch
         computes or writes a halo pixel.  This rests on one invariant: every map comes from ``FMap.alloc`` (``torch.zeros``),
@@ -83,82 +83,72 @@ class HipUNet:
         self.stem_b = b.float().contiguous().to(device)
         self.head_w = self.sd["mask_head.0.weight"].float().reshape(32).contiguous().to(device)
         self.head_b = float(self.sd["mask_head.0.bias"].float().reshape(-1)[0])
+        # ``gemm.select_conv2d``'s arguments next to ``line_tile``: e2.block.0 takes its line tile on the fused network only
+        # (tools/bench_unet_layers.py --ab changes them before the first forward to build the earlier forms)
+        self.conv_choice = dict(s21_tile=fuse_up)
         self._ws: Dict[Tuple[int, int, int], dict] = {}
-
-    def _line_tile_plan(self, srcs, dst, m, w, b, kw):
-        """The 3x3 same-geometry line-tile plan of a convolution (fp16 or split-format kernel), or None."""
-        if not self.line_tile:
-            return None
-        fs = [m[s] for s in srcs]
-        if self.split:
-            if G.taps2d_split_supported(fs, m[dst], w, **kw):
-                return G.Taps2dSplitPlan(fs[0], m[dst], w, b, slope=SLOPE, device=self.dev)
-        elif G.taps2d_supported(fs, m[dst], w, **kw):
-            return G.Taps2dPlan(fs[0], m[dst], w, b, slope=SLOPE, device=self.dev)
-        return None
 
     @property
     def _fused_head(self) -> bool:
         """fp32-class mode with line tiles: ``d1.block.3`` carries the mask head, ``y1`` has no storage."""
         return self.split and self.line_tile
 
-    def _y1(self, B: int, H: int, W: int) -> G.FMap:
-        y1 = G.FMap(B, H, W, 32, 1, 1, split=self.split)
-        return y1 if self._fused_head else y1.alloc(self.dev)
-
-    def _finish(self, key, m, steps) -> dict:
-        B, H, W = key
-        ws = dict(maps=m, steps=steps, mask=torch.empty(B, H, W, dtype=torch.float32, device=self.dev),
-                  logits=torch.empty(B, H, W, dtype=torch.float32, device=self.dev))
-        ws["flops"] = reference_flops(B, H, W)                # the reference formulation's count, not the fused launches'
-        if self._fused_head:
-            last = steps[-1][0]
-            assert isinstance(last, G.Taps2dSplitPlan), "d1.block.3 is a 3x3 32-channel same-geometry layer"
-            last.attach_head(self.head_w, self.head_b, ws["mask"], ws["logits"])
-        self._ws[key] = ws
-        return ws
-
     def _workspace(self, B: int, H: int, W: int) -> dict:
+        """Maps and launches of one input shape.  With ``fuse_up`` the stages up4+d4 .. up1+d1 are fused launches and the up-sampled
+        maps u4..u1 do not exist; the coarse maps b2 / y4 / y3 then carry one extra 8-channel chunk whose first channel is the
+        in-image indicator (and unused channels up to the next multiple of 64, so every pixel starts on a 128-byte line), and for
+        d1 the indicator rides in the 8-channel spectrogram map ``xin`` = (x, 1, 0, ...) that ``advh_unet_pack_x`` fills."""
         key = (B, H, W)
         if key in self._ws:
             return self._ws[key]
         if H % 16 or W % 4:
             raise ValueError("U-Net input needs H % 16 == 0 and W % 4 == 0 (SURVEY.md D2)")
-        dev, sd = self.dev, self.sd
+        dev, sd, fused = self.dev, self.sd, self.fuse_up
         F = lambda h, w, c, ph, pw: G.FMap(B, h, w, c, ph, pw, split=self.split).alloc(dev)
-        if self.fuse_up:
-            return self._workspace_fused(B, H, W)
+        coarse_map = lambda h, w, c: G.add_indicator(F(h, w, c + 64, 1, 1), c) if fused else F(h, w, c, 0, 0)
+        up_map = lambda h, w, c: None if fused else F(h, w, c, 1, 1)
         m = dict(
             x1a=F(H // 2, W, 32, 2, 1), x1=F(H // 2, W, 32, 2, 1),
             x2a=F(H // 4, W, 64, 1, 1), x2=F(H // 4, W, 64, 1, 1),
             x3a=F(H // 8, W // 2, 128, 1, 1), x3=F(H // 8, W // 2, 128, 1, 1),
             x4a=F(H // 16, W // 4, 256, 1, 1), x4=F(H // 16, W // 4, 256, 2, 2),
-            b1=F(H // 16, W // 4, 512, 4, 4), b2=F(H // 16, W // 4, 512, 0, 0),
-            u4=F(H // 8, W // 2, 256, 1, 1), y4a=F(H // 8, W // 2, 256, 1, 1), y4=F(H // 8, W // 2, 256, 0, 0),
-            u3=F(H // 4, W, 128, 1, 1), y3a=F(H // 4, W, 128, 1, 1), y3=F(H // 4, W, 128, 0, 0),
-            u2=F(H // 2, W, 64, 1, 1), y2a=F(H // 2, W, 64, 1, 1), y2=F(H // 2, W, 64, 1, 1),
-            u1=F(H, W, 40, 1, 1), y1a=F(H, W, 32, 1, 1), y1=self._y1(B, H, W),
+            b1=F(H // 16, W // 4, 512, 4, 4), b2=coarse_map(H // 16, W // 4, 512),
+            u4=up_map(H // 8, W // 2, 256), y4a=F(H // 8, W // 2, 256, 1, 1), y4=coarse_map(H // 8, W // 2, 256),
+            u3=up_map(H // 4, W, 128), y3a=F(H // 4, W, 128, 1, 1), y3=coarse_map(H // 4, W, 128),
+            u2=up_map(H // 2, W, 64), y2a=F(H // 2, W, 64, 1, 1), y2=F(H // 2, W, 64, 1, 1),
+            u1=up_map(H, W, 40), xin=G.add_indicator(F(H, W, 8, 1, 1), 1) if fused else None,
+            y1a=F(H, W, 32, 1, 1), y1=G.FMap(B, H, W, 32, 1, 1, split=self.split),
         )
+        m = {k: f for k, f in m.items() if f is not None}
+        if not self._fused_head:
+            m["y1"].alloc(dev)
         steps = []
 
         def conv(srcs, dst, conv_name, bn_name, **kw):
             w, b = _fold_bn(sd, conv_name, bn_name, self.wdtype)
             cin = sum(m[s].C for s in srcs)
-            if cin != w.shape[1]:                              # d1: 33 real channels live in a 40-wide map
+            if cin != w.shape[1]:                              # unfused d1: 33 real channels live in a 40-wide map
                 w = torch.cat([w, w.new_zeros(w.shape[0], cin - w.shape[1], *w.shape[2:])], 1)
-            plan = self._line_tile_plan(srcs, dst, m, w, b, kw)
-            if plan is None:
-                plan = G.plan_conv2d([m[s] for s in srcs], m[dst], w, b, slope=SLOPE, device=dev, interior_only=True, **kw)
+            plan = G.select_conv2d([m[s] for s in srcs], m[dst], w, b, line_tile=self.line_tile, slope=SLOPE, device=dev,
+                                   **self.conv_choice, **kw)
             steps.append((plan, srcs, dst))
 
         def block(srcs, mid, dst, name, **first):              # ConvBlock, addvisor.py:12-25
             conv(srcs, mid, f"{name}.block.0", f"{name}.block.1", **first)
             conv([mid], dst, f"{name}.block.3", f"{name}.block.4")
 
-        def up(src, dst, name, stride):
-            plan = G.plan_convT2d(m[src], m[dst], sd[name + ".weight"].to(self.wdtype), sd[name + ".bias"].float(),
-                                  stride=stride, device=dev)
-            steps.append((plan, [src], dst))
+        def stage(coarse, u, skip, mid, dst, up_name, name, stride, coarse_C, skip_C, indicator):
+            """One decoder stage: ConvTranspose2d ``up_name`` into ``u``, then ConvBlock ``name`` on cat(u, skip) -- or, fused, the
+            transposed convolution and ``name.block.0`` as one launch on (coarse, skip)."""
+            wt, bt = sd[up_name + ".weight"].to(self.wdtype), sd[up_name + ".bias"].to(self.wdtype)
+            if not fused:
+                steps.append((G.plan_convT2d(m[coarse], m[u], wt, bt, stride=stride, device=dev), [coarse], u))
+                return block([u, skip] if skip in m else [u], mid, dst, name)    # without ``xin`` the spectrogram is packed into u1
+            wc, bc = _fold_bn(sd, f"{name}.block.0", f"{name}.block.1", self.wdtype)
+            plan = G.select_upconv2d(m[coarse], m[skip], m[mid], wt, bt, wc, bc, line_tile=self.line_tile, stride=stride,
+                                     coarse_C=coarse_C, skip_C=skip_C, indicator=indicator, slope=SLOPE, device=dev)
+            steps.append((plan, [coarse, skip], mid))
+            conv([mid], dst, f"{name}.block.3", f"{name}.block.4")
 
         conv(["x1a"], "x1", "e1.block.3", "e1.block.4")        # e1.block.0 is the direct stem kernel
         block(["x1"], "x2a", "x2", "e2", stride=(2, 1), padding=(2, 1))
@@ -166,75 +156,19 @@ class HipUNet:
         block(["x3"], "x4a", "x4", "e4", stride=(2, 2))
         conv(["x4"], "b1", "bottleneck.0", "bottleneck.1", padding=(2, 2), dilation=(2, 2))
         conv(["b1"], "b2", "bottleneck.3", "bottleneck.4", padding=(4, 4), dilation=(4, 4))
-        up("b2", "u4", "up4", (2, 2))
-        block(["u4", "x3"], "y4a", "y4", "d4")
-        up("y4", "u3", "up3", (2, 2))
-        block(["u3", "x2"], "y3a", "y3", "d3")
-        up("y3", "u2", "up2", (2, 1))
-        block(["u2", "x1"], "y2a", "y2", "d2")
-        up("y2", "u1", "up1", (2, 1))
-        block(["u1"], "y1a", "y1", "d1")
-        return self._finish(key, m, steps)
-
-    def _workspace_fused(self, B: int, H: int, W: int) -> dict:
-        """Same network with up4+d4, up3+d3, up2+d2, up1+d1 as fused launches: the maps u4..u1 do not exist.  The coarse
-        maps b2 / y4 / y3 carry one extra 8-channel chunk whose first channel is the in-image indicator (and unused
-        channels up to the next multiple of 64, so every pixel starts on a 128-byte line); for d1 the
-        indicator rides in the 8-channel spectrogram map ``xin`` = (x, 1, 0, ...) that ``advh_unet_pack_x`` fills."""
-        dev, sd = self.dev, self.sd
-        F = lambda h, w, c, ph, pw: G.FMap(B, h, w, c, ph, pw, split=self.split).alloc(dev)
-        m = dict(
-            x1a=F(H // 2, W, 32, 2, 1), x1=F(H // 2, W, 32, 2, 1),
-            x2a=F(H // 4, W, 64, 1, 1), x2=F(H // 4, W, 64, 1, 1),
-            x3a=F(H // 8, W // 2, 128, 1, 1), x3=F(H // 8, W // 2, 128, 1, 1),
-            x4a=F(H // 16, W // 4, 256, 1, 1), x4=F(H // 16, W // 4, 256, 2, 2),
-            b1=F(H // 16, W // 4, 512, 4, 4), b2=G.add_indicator(F(H // 16, W // 4, 576, 1, 1), 512),
-            y4a=F(H // 8, W // 2, 256, 1, 1), y4=G.add_indicator(F(H // 8, W // 2, 320, 1, 1), 256),
-            y3a=F(H // 4, W, 128, 1, 1), y3=G.add_indicator(F(H // 4, W, 192, 1, 1), 128),
-            y2a=F(H // 2, W, 64, 1, 1), y2=F(H // 2, W, 64, 1, 1),
-            xin=G.add_indicator(F(H, W, 8, 1, 1), 1), y1a=F(H, W, 32, 1, 1), y1=self._y1(B, H, W),
-        )
-        steps = []
-
-        def conv(srcs, dst, conv_name, bn_name, **kw):
-            w, b = _fold_bn(sd, conv_name, bn_name, self.wdtype)
-            plan = self._line_tile_plan(srcs, dst, m, w, b, kw)
-            if plan is None and self.line_tile and not self.split and G.conv_s21_supported([m[s] for s in srcs], m[dst], w, **kw):
-                plan = G.ConvS21TilePlan(m[srcs[0]], m[dst], w, b, slope=SLOPE, device=dev)
-            if plan is None and self.line_tile and self.split and G.conv_s21_split_supported([m[s] for s in srcs], m[dst], w, **kw):
-                plan = G.ConvS21SplitTilePlan(m[srcs[0]], m[dst], w, b, slope=SLOPE, device=dev)
-            if plan is None:
-                plan = G.plan_conv2d([m[s] for s in srcs], m[dst], w, b, slope=SLOPE, device=dev, interior_only=True, **kw)
-            steps.append((plan, srcs, dst))
-
-        def block(srcs, mid, dst, name, **first):
-            conv(srcs, mid, f"{name}.block.0", f"{name}.block.1", **first)
-            conv([mid], dst, f"{name}.block.3", f"{name}.block.4")
-
-        def up_block(coarse, skip, mid, dst, up_name, name, stride, coarse_C, skip_C, indicator):
-            wc, bc = _fold_bn(sd, f"{name}.block.0", f"{name}.block.1", self.wdtype)
-            wt, bt = sd[up_name + ".weight"].to(self.wdtype), sd[up_name + ".bias"].to(self.wdtype)
-            if self.line_tile and not self.split and G.upconv_tile_supported(m[coarse], m[skip], m[mid], wt, wc, stride, indicator):
-                plan = G.UpconvTilePlan(m[coarse], m[skip], m[mid], wt, bt, wc, bc, slope=SLOPE, device=dev)
-            elif self.line_tile and G.upconv_tile_split_supported(m[coarse], m[skip], m[mid], wt, wc, stride, indicator):
-                plan = G.UpconvSplitTilePlan(m[coarse], m[skip], m[mid], wt, bt, wc, bc, slope=SLOPE, device=dev)
-            else:
-                plan = G.plan_upconv2d(m[coarse], m[skip], m[mid], wt, bt, wc, bc, stride=stride, coarse_C=coarse_C,
-                                       skip_C=skip_C, indicator=indicator, slope=SLOPE, device=dev)
-            steps.append((plan, [coarse, skip], mid))
-            conv([mid], dst, f"{name}.block.3", f"{name}.block.4")
-
-        conv(["x1a"], "x1", "e1.block.3", "e1.block.4")
-        block(["x1"], "x2a", "x2", "e2", stride=(2, 1), padding=(2, 1))
-        block(["x2"], "x3a", "x3", "e3", stride=(2, 2))
-        block(["x3"], "x4a", "x4", "e4", stride=(2, 2))
-        conv(["x4"], "b1", "bottleneck.0", "bottleneck.1", padding=(2, 2), dilation=(2, 2))
-        conv(["b1"], "b2", "bottleneck.3", "bottleneck.4", padding=(4, 4), dilation=(4, 4))
-        up_block("b2", "x3", "y4a", "y4", "up4", "d4", (2, 2), 512, 128, ("coarse", 512))
-        up_block("y4", "x2", "y3a", "y3", "up3", "d3", (2, 2), 256, 64, ("coarse", 256))
-        up_block("y3", "x1", "y2a", "y2", "up2", "d2", (2, 1), 128, 32, ("coarse", 128))
-        up_block("y2", "xin", "y1a", "y1", "up1", "d1", (2, 1), 64, 1, ("skip", 1))
-        return self._finish((B, H, W), m, steps)
+        stage("b2", "u4", "x3", "y4a", "y4", "up4", "d4", (2, 2), 512, 128, ("coarse", 512))
+        stage("y4", "u3", "x2", "y3a", "y3", "up3", "d3", (2, 2), 256, 64, ("coarse", 256))
+        stage("y3", "u2", "x1", "y2a", "y2", "up2", "d2", (2, 1), 128, 32, ("coarse", 128))
+        stage("y2", "u1", "xin", "y1a", "y1", "up1", "d1", (2, 1), 64, 1, ("skip", 1))
+        ws = dict(maps=m, steps=steps, mask=torch.empty(B, H, W, dtype=torch.float32, device=dev),
+                  logits=torch.empty(B, H, W, dtype=torch.float32, device=dev))
+        ws["flops"] = reference_flops(B, H, W)                # the reference formulation's count, not the fused launches'
+        if self._fused_head:
+            last = steps[-1][0]
+            assert isinstance(last, G.Taps2dSplitPlan), "d1.block.3 is a 3x3 32-channel same-geometry layer"
+            last.attach_head(self.head_w, self.head_b, ws["mask"], ws["logits"])
+        self._ws[key] = ws
+        return ws
 
     def flops(self, B: int, H: int, W: int) -> float:
         return self._workspace(B, H, W)["flops"]
