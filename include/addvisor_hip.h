@@ -408,6 +408,39 @@ int advh_philox_normal(uint64_t seed, int64_t row0, int rows, int64_t n, int raw
 int advh_nt_fold(const float* attr, int B, int p, int64_t n, double* sum, double* sumsq, advh_stream_t stream);
 int advh_nt_finalize(const double* sum, const double* sumsq, int B, int64_t n, int S, int nt_type, float* out, advh_stream_t stream);
 
+/* Layer attributions (csrc/attribution_layer.hip): Captum's LayerActivation, LayerGradientXActivation,
+ * LayerIntegratedGradients, LayerConductance and InternalInfluence at hidden_states[l] of the encoder, restated (captum is
+ * absent).  The encoder chain is started at a layer (EmbedderGrad.forward_from) and its backward stopped at one
+ * (EmbedderGrad.backward(to_layer=l)); these kernels are the two ends.  All rows [.][n] fp32, contiguous.  One thread per
+ * element, every product, difference and sum rounded on its own, sums in increasing step order, row sums a fixed-shape tree in
+ * one workgroup, no atomics: equal inputs give equal bits for every chunking.
+ *
+ * advh_layer_inject : resid[r] = src[r] ([rows][n], rows = clips * T, n = H: the residual stream at the layer) and, if op != NULL,
+ *     the GEMM operand copy of the same fp32 values the post-LN layer reads: one fp16 plane (split = 0) or the split format's
+ *     hi plane at op and lo plane op_lo elements behind (split = 1; op_lo >= rows * n).  The split conversion honours the
+ *     format's contract (csrc/device_math.h): |x| > 65504 saturates and raises the sticky range flag (advh_split_overflow),
+ *     NaN stays NaN planes and leaves it clear.  Serves every Layer* class (captum.attr.LayerIntegratedGradients' path points).
+ * advh_layer_tap : out[r] = g[r] * inv_scale (act == NULL: the layer gradient dF/dh_l, g the residual-stream gradient and
+ *     inv_scale = 1 / loss_scale) or g[r] * inv_scale * act[r] (captum.attr.LayerGradientXActivation); row_sum != NULL also
+ *     writes row_sum[r] = sum_j of those values (per-clip sums for deltas with rows = clips, per-frame relevance with
+ *     rows = clips * T).  out may be NULL when row_sum is given.
+ * advh_layer_conductance_accumulate (captum.attr.LayerConductance): one step-major chunk of `steps` consecutive path points,
+ *     act [steps][B][n] = h_l of each point and grad [ngrad][B][n] = dF/dh_l of the first ngrad of them (the last point of the
+ *     path needs no gradient; grad may be NULL when ngrad = 0).  Element (b, j) walks the points k in order:
+ *     total[b] += pg * (act[k][b] - pa) (skipped for the path's first point: first = 1 and k = 0), then pa = act[k][b] and, for
+ *     k < ngrad, pg = grad[k][b]; (pg, pa) start from and end in prev_grad / prev_act [B][n], which carry the pair that straddles
+ *     a chunk boundary (not read when first = 1).  Over the whole path: total[b] = sum_k grad[k][b] * (act[k+1][b] - act[k][b]).
+ * The activation-space path points of LayerIntegratedGradients and the weighted gradient sums of it and of
+ * captum.attr.InternalInfluence are advh_attr_path_points / advh_attr_path_accumulate with n = T * H.
+ * NaN / inf propagate into the results (the caller's finiteness check reports them).  Null pointers (op, act of the tap, out or
+ * row_sum -- not both -- and grad with ngrad = 0 excepted), rows, B, n or steps <= 0, ngrad outside [0, steps], a flag outside
+ * {0, 1}, a non-finite inv_scale and, in split mode, a plane pitch of 0 or below rows * n return ADVH_EINVAL before any HIP call. */
+int advh_layer_inject(const float* src, int rows, int64_t n, float* resid, void* op, int split, int64_t op_lo, advh_stream_t stream);
+int advh_layer_tap(const float* g, const float* act, float inv_scale, int rows, int64_t n, float* out, float* row_sum,
+                   advh_stream_t stream);
+int advh_layer_conductance_accumulate(const float* grad, const float* act, int B, int64_t n, int steps, int ngrad, int first,
+                                      float* prev_grad, float* prev_act, float* total, advh_stream_t stream);
+
 /* Attribution metrics (csrc/attribution_metrics.hip): Captum's infidelity and sensitivity_max of the [B][n] inputs x, restated
  * (captum is absent).  S perturbed samples per clip, processed in chunks of p consecutive samples [s0, s0 + p); a chunk's rows
  * are clip-major, row b * p + s' (Captum's repeat_interleave), and the noise of a row comes from its global counter

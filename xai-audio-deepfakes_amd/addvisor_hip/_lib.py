@@ -72,6 +72,9 @@ SIGNATURES = {
     "advh_philox_normal": (_i, [C.c_uint64, _i64, _i, _i64, _i, _p, _p]),
     "advh_nt_fold": (_i, [_p, _i, _i, _i64, _p, _p, _p]),
     "advh_nt_finalize": (_i, [_p, _p, _i, _i64, _i, _i, _p, _p]),
+    "advh_layer_inject": (_i, [_p, _i, _i64, _p, _p, _i, _i64, _p]),
+    "advh_layer_tap": (_i, [_p, _p, _f, _i, _i64, _p, _p, _p]),
+    "advh_layer_conductance_accumulate": (_i, [_p, _p, _i, _i64, _i, _i, _i, _p, _p, _p, _p]),
     "advh_metric_rows": (_i, [_p, _i64, _i, _p, _p, _p]),
     "advh_metric_row_dot": (_i, [_p, _p, _i, _i, _i64, _p, _p]),
     "advh_infidelity_fold": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),

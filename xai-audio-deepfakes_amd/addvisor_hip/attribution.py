@@ -42,7 +42,7 @@ import torch
 
 from . import _lib
 from .embedder import HipEmbedder
-from .embedder_grad import EmbedderGrad
+from .embedder_grad import EmbedderGrad, check_layer  # noqa: F401  (check_layer(layer, nl): the Layer* methods' layer check)
 
 
 def _st():
@@ -356,6 +356,39 @@ def check_permutation_args(feature_mask, B: int, L: int) -> Tuple[torch.Tensor, 
         raise ValueError("FeaturePermutation takes one [1, L] feature_mask (the same features permuted in every clip), "
                          f"not {list(feature_mask.shape)}")
     return feature_indices(feature_mask, B, L)
+
+
+def check_steps(n_steps, method: str, least: int = 1) -> int:
+    """``n_steps`` and ``method`` of the path methods: an integer >= ``least`` and one of ``METHODS`` (ValueError)."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or n_steps < least:
+        raise ValueError(f"n_steps must be an integer >= {least}, not {n_steps!r}")
+    return int(n_steps)
+
+
+def check_layer_path_args(layer, nl: int, baselines, B: int, L: int, n_steps, method: str, internal_batch_size=None,
+                          extra_point: bool = False):
+    """The arguments of LayerIntegratedGradients / LayerConductance / InternalInfluence, before any GPU work (ValueError):
+    ``check_layer``; waveform-space ``baselines`` as ``check_ig_baselines``; ``n_steps`` and ``method`` as ``check_steps`` --
+    the rule is evaluated at ``n_steps`` points, ``n_steps + 1`` with ``extra_point`` (LayerConductance), and a Riemann rule
+    needs more than one; ``internal_batch_size`` None or an integer >= 1.  Returns ``(layer, baselines [1|B, L], alphas,
+    step_sizes)``."""
+    l = check_layer(layer, nl)
+    base = check_ig_baselines(baselines, B, L)
+    n = check_steps(n_steps, method) + int(extra_point)
+    alphas, steps = approximation(method, n)
+    if internal_batch_size is not None:
+        _positive_int(internal_batch_size, "internal_batch_size")
+    return l, base, alphas, steps
+
+
+def frame_index(L: int, T: int, hop: int = 320) -> np.ndarray:
+    """The encoder frame of each waveform sample: sample j belongs to frame ``min(j // hop, T - 1)`` (``hop``: the product of
+    the feature encoder's strides, 320 for wav2vec2; the samples behind the last whole hop go to the last frame).  int64 ``[L]``."""
+    if L < 1 or T < 1 or hop < 1:
+        raise ValueError("frame_index needs L, T and hop >= 1")
+    return np.minimum(np.arange(L, dtype=np.int64) // hop, T - 1)
 
 
 SIM_MODES = ("cosine", "euclidean")                                    # advh_row_similarity's mode = the index
@@ -1500,6 +1533,155 @@ class HipAttribution:
         afterwards and ``torch.manual_seed`` reproduces the call; Captum's RNG stream is not reproduced."""
         return sensitivity_max(explain, waves, self.emb.dev, perturb_func, perturb_radius, n_perturb_samples, norm_ord,
                                max_examples_per_batch, seed, **kwargs)
+
+    # ------------------------------------------------------------------ layer attributions (captum.attr.Layer*, InternalInfluence)
+    def _layer_chunks(self, B: int, n_points: int, internal_batch_size: Optional[int]) -> int:
+        return min(max(1, (internal_batch_size or 128) // B), n_points)           # whole steps per chunk, as integrated_gradients
+
+    def _expand_base(self, base, x):
+        return base.to(x.device, torch.float32).expand(x.shape[0], -1).contiguous()
+
+    def layer_activation(self, waves, layer: int):
+        """Captum's LayerActivation: ``hidden_states[layer](x)``, ``[B, T, H]`` fp32."""
+        l = check_layer(layer, self.eg.emb.nl)
+        x = self._prep(waves)
+        self.eg.forward(x)
+        return self._checked(self.eg.hidden(l), "layer activation", "the forward pass produced a non-finite activation")
+
+    def layer_gradient_x_activation(self, waves, layer: int, multiply_by_inputs: bool = True):
+        """Captum's LayerGradientXActivation: ``dF/dh_l`` times ``h_l = hidden_states[layer](x)`` (the gradient alone with
+        ``multiply_by_inputs=False``), ``[B, T, H]`` fp32: one forward, one backward stopped at the layer."""
+        l = check_layer(layer, self.eg.emb.nl)
+        x = self._prep(waves)
+        self.eg.forward(x)
+        g = self.eg.backward(self.loss_scale, to_layer=l)
+        if multiply_by_inputs:
+            g = self.eg.layer_tap(g, 1.0, self.eg.hidden(l))
+        return self._checked(g)
+
+    def layer_integrated_gradients(self, waves, layer: int, baselines=None, n_steps: int = 50, method: str = "gausslegendre",
+                                   internal_batch_size: Optional[int] = None, multiply_by_inputs: bool = True,
+                                   return_convergence_delta: bool = False):
+        """Captum's LayerIntegratedGradients: the path runs in the layer's activation space, from ``hb = h_l(b)`` to
+        ``hx = h_l(x)`` (one full forward each; ``b`` a waveform-space baseline as for ``integrated_gradients``), through
+        ``forward_from(l, .)`` and ``backward(to_layer=l)`` -- nothing below the layer runs per path point.
+        ``attr = (sum_k w_k g_k) * (hx - hb)`` ``[B, T, H]`` (the sum alone with ``multiply_by_inputs=False``);
+        ``delta[b] = sum attr[b] - (F(x_b) - F(b_b))`` with F from the two full forwards."""
+        B, L = _dims(waves)
+        l, base, alphas, steps = check_layer_path_args(layer, self.eg.emb.nl, baselines, B, L, n_steps, method, internal_batch_size)
+        if return_convergence_delta and not multiply_by_inputs:
+            raise NotImplementedError("the convergence delta needs multiply_by_inputs=True")
+        x = self._prep(waves)
+        eg = self.eg
+        fx = eg.forward(x)[0].view(-1)
+        hx = eg.hidden(l)
+        fb = eg.forward(self._expand_base(base, x))[0].view(-1)
+        hb = eg.hidden(l)
+        T, H = hx.shape[1:]
+        n = T * H
+        per = self._layer_chunks(B, n_steps, internal_batch_size)
+        npad = -(-n_steps // per) * per
+        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
+        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
+        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
+        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
+        d = _desc(hx.view(B, n), hb.view(B, n), None, npad, 0)
+        total = torch.zeros((B, n), dtype=torch.float32, device=x.device)
+        pts = torch.empty((per * B, T, H), dtype=torch.float32, device=x.device)
+        for s0 in range(0, npad, per):
+            _points(d, a_all, s0 * B, per * B, pts)
+            eg.forward_from(l, pts)
+            g = eg.backward(self.loss_scale, to_layer=l)                        # [per*B, T, H], step-major
+            _accumulate(d, g, w_all, ACC_IG, s0 * B, per * B, total)
+        if not multiply_by_inputs:
+            return self._checked(total.view(B, T, H))
+        out = torch.empty_like(total)
+        sums = torch.empty(B, dtype=torch.float32, device=x.device) if return_convergence_delta else None
+        _accumulate(d, total, None, FIN_IG, 0, B, out, sums)
+        out = self._checked(out.view(B, T, H))
+        if not return_convergence_delta:
+            return out
+        return out, (sums.double() - (fx.double() - fb.double())).float()
+
+    def _wave_path(self, waves, layer, baselines, n_steps, method, internal_batch_size, extra_point):
+        B, L = _dims(waves)
+        l, base, alphas, steps = check_layer_path_args(layer, self.eg.emb.nl, baselines, B, L, n_steps, method, internal_batch_size,
+                                                       extra_point)
+        x = self._prep(waves)
+        return x, base.to(x.device, torch.float32).contiguous(), l, alphas, steps
+
+    def layer_conductance(self, waves, layer: int, baselines=None, n_steps: int = 50, method: str = "gausslegendre",
+                          internal_batch_size: Optional[int] = None):
+        """Captum's LayerConductance: the ``n_steps + 1`` points ``b + alpha_k (x - b)`` of ``approximation(method, n_steps + 1)``
+        in waveform space, each through a full forward and a backward stopped at the layer;
+        ``attr = sum_{k < n_steps} g_k * (h_{k+1} - h_k)`` ``[B, T, H]`` (the last point needs no backward), summed in step order
+        by advh_layer_conductance_accumulate: the result does not depend on ``internal_batch_size``."""
+        x, base, l, alphas, _ = self._wave_path(waves, layer, baselines, n_steps, method, internal_batch_size, True)
+        B, L = x.shape
+        eg, lib = self.eg, _lib.lib()
+        npts = n_steps + 1
+        per = self._layer_chunks(B, npts, internal_batch_size)
+        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
+        d = _desc(x, base, None, npts, 0)
+        # one workspace shape: a short last chunk leaves the previous chunk's (finite) points in the rows it does not use
+        pts = torch.zeros((per * B, L), dtype=torch.float32, device=x.device)
+        total = prev_g = prev_a = None
+        for s0 in range(0, npts, per):
+            ns = min(per, npts - s0)
+            ngrad = min(ns, n_steps - s0)                                       # the path's last point needs no gradient
+            _points(d, a_all, s0 * B, ns * B, pts)
+            eg.forward(pts)
+            act = eg.hidden(l)                                                  # [per*B, T, H], step-major
+            g = eg.backward(self.loss_scale, to_layer=l) if ngrad > 0 else None
+            if total is None:
+                total, prev_g, prev_a = (torch.zeros_like(act[:B]) for _ in range(3))
+            _lib.check(lib.advh_layer_conductance_accumulate(None if g is None else g.data_ptr(), act.data_ptr(), B, act[0].numel(), ns,
+                                                             ngrad, int(s0 == 0), prev_g.data_ptr(), prev_a.data_ptr(), total.data_ptr(),
+                                                             _st()), "advh_layer_conductance_accumulate")
+        return self._checked(total)
+
+    def internal_influence(self, waves, layer: int, baselines=None, n_steps: int = 50, method: str = "gausslegendre",
+                           internal_batch_size: Optional[int] = None):
+        """Captum's InternalInfluence: ``attr = sum_k w_k g_k`` ``[B, T, H]``, ``g_k = dF/dh_l`` at the ``n_steps`` waveform-space
+        points ``b + alpha_k (x - b)`` (a full forward and a backward stopped at the layer each)."""
+        x, base, l, alphas, steps = self._wave_path(waves, layer, baselines, n_steps, method, internal_batch_size, False)
+        B, L = x.shape
+        eg = self.eg
+        per = self._layer_chunks(B, n_steps, internal_batch_size)
+        npad = -(-n_steps // per) * per
+        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
+        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
+        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
+        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
+        d = _desc(x, base, None, npad, 0)
+        pts = torch.empty((per * B, L), dtype=torch.float32, device=x.device)
+        total = dl = None
+        for s0 in range(0, npad, per):
+            _points(d, a_all, s0 * B, per * B, pts)
+            eg.forward(pts)
+            g = eg.backward(self.loss_scale, to_layer=l)                        # [per*B, T, H], step-major
+            if total is None:
+                total = torch.zeros_like(g[:B])
+                flat = total.view(B, -1)
+                dl = _desc(flat, flat, None, npad, 0)                           # ACC_IG reads neither x nor the baseline
+            _accumulate(dl, g, w_all, ACC_IG, s0 * B, per * B, total)
+        return self._checked(total)
+
+    def frames_to_wave(self, rel: torch.Tensor, L: int) -> torch.Tensor:
+        """Per-frame relevance ``[B, T]`` spread to the ``L`` samples of each clip (``frame_index``): ``[B, L]`` fp32."""
+        T = rel.shape[1]
+        hop = int(np.prod(self.emb.cfg.conv_stride))
+        idx = torch.from_numpy(frame_index(L, T, hop)).to(rel.device)
+        return rel.float().index_select(1, idx).contiguous()
+
+    def layer_relevance(self, attr: torch.Tensor, L: int) -> torch.Tensor:
+        """A layer attribution ``[B, T, H]`` as waveform relevance ``[B, L]``: summed over the channels of each frame
+        (advh_layer_tap's row sums), then ``frames_to_wave``."""
+        attr = attr.contiguous()
+        B, T, H = attr.shape
+        rel = torch.empty(B * T, dtype=torch.float32, device=attr.device)
+        self.eg.layer_tap(attr.view(B * T, H), 1.0, want_out=False, row_sum=rel)
+        return self.frames_to_wave(rel.view(B, T), L)
 
     def _ig_zero(self, waves, n_steps: int, internal_batch_size: Optional[int]):
         x = self._prep(waves)

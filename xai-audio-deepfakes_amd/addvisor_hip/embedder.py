@@ -237,6 +237,13 @@ class HipEmbedder:
         """Algorithmic FLOPs (2*MAC) of one forward for B clips of L samples."""
         return self._workspace(B, L)["flops"]
 
+    def flops_from(self, B: int, L: int, layer: int) -> float:
+        """``flops`` of the part of the forward a chain started at ``hidden_states[layer]`` runs: encoder layers
+        ``layer .. nl-1`` (the LayerNorms and the pooling are not counted, as in ``flops``)."""
+        ws = self._workspace(B, L)
+        T, H = ws["T"], self.cfg.hidden_size
+        return sum(sum(p.flops for p in lay.values()) + 4.0 * B * T * T * H for lay in ws["layers"][layer:])
+
     # ------------------------------------------------------------------ forward
     def forward(self, wave: torch.Tensor, length: Optional[int] = None, want_hidden: bool = True,
                 normalize: bool = True, slot: int = 0):

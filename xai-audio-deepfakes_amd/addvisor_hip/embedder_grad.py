@@ -53,6 +53,15 @@ def plan_conv1d_dgrad(B: int, P_out: int, weight: torch.Tensor, stride: int, dev
                       out=(P_out * s * Cin, 0, s * Cin, 0), device=device, cache=cache, split=split), nt
 
 
+def check_layer(layer, nl: int) -> int:
+    """A layer of the ``captum.attr.Layer*`` methods: an integer index into ``hidden_states``, ``0 <= layer <= nl``
+    (``nl = HipEmbedder.nl``; the layers above it do not reach the logit).  Raises ValueError."""
+    if isinstance(layer, bool) or not isinstance(layer, (int, np.integer)) or not 0 <= layer <= nl:
+        raise ValueError(f"layer must be an integer index into hidden_states, 0 <= layer <= {nl}; got {layer!r} "
+                         "(layers above layer_index do not reach the logit)")
+    return int(layer)
+
+
 class EmbedderGrad:
     def __init__(self, emb: HipEmbedder, precision: Optional[str] = None):
         """``precision``: None = the embedder's own ("f32": split-format chain; "f16": fp16 chain), or "f16" to run the fp16
@@ -218,7 +227,21 @@ class EmbedderGrad:
         else:
             f["pos"].run(f["xg"], out_f=w["h1"], resid=h, out_pre=w["pc"])
             emb.enc_ln(w["h1"], M, eps, out_f=w["x"][0], out_h=h16, split=sp)
-        for l in range(nl):
+        self._start = None
+        self._encoder_tail(w, 0, B)
+        self._last = (wave, B, n_in, L)
+        return f["logit"].clone().view(B, 1), f["prob"].clone().view(B, 1)
+
+    def _encoder_tail(self, w: dict, start: int, B: int) -> None:
+        """Layers ``start .. nl-1`` on the rows of ``w["x"][start]`` (post-LN: and their operand copy in ``h16``), the final
+        LayerNorm where the model has one, and the pooling + logreg, with the saves of the backward."""
+        emb, cfg, lib, sp = self.emb, self.cfg, _lib.lib(), self.split
+        f = w["f"]
+        st = torch.cuda.current_stream().cuda_stream
+        T, M, H = f["T"], f["M"], cfg.hidden_size
+        eps, nl = cfg.layer_norm_eps, emb.nl
+        h16 = f["h16"]
+        for l in range(start, nl):
             lay = f["layers"][l]
             if self.stable:
                 emb.ln1[l](w["x"][l], M, eps, out_h=h16, split=sp)
@@ -247,8 +270,69 @@ class EmbedderGrad:
             final = w["xf"]
         _lib.check(lib.advh_pool_logreg(final.data_ptr(), emb.coef.data_ptr(), emb.intercept, f["logit"].data_ptr(),
                                         f["prob"].data_ptr(), None, B, T, H, st), "advh_pool_logreg")
-        self._last = (wave, B, n_in, L)
-        return f["logit"].clone().view(B, 1), f["prob"].clone().view(B, 1)
+
+    # ------------------------------------------------------------------ the chain from / to a layer (captum.attr.Layer*)
+    def _hidden_buf(self, w: dict, l: int) -> torch.Tensor:
+        # hidden_states[nl] of a full-depth pre-LN model is the output of the final LayerNorm: it lives in w["xf"]
+        return w["xf"] if (l == self.emb.nl and self._final_ln) else w["x"][l]
+
+    def hidden(self, layer: int) -> torch.Tensor:
+        """``hidden_states[layer]`` of the last ``forward`` / ``forward_from`` as a fresh ``[B, T, H]`` fp32 tensor."""
+        l = check_layer(layer, self.emb.nl)
+        if getattr(self, "_last", None) is None:
+            raise RuntimeError("hidden() needs a forward pass first")
+        if self._start is not None and l < self._start:
+            raise ValueError(f"the last pass started at layer {self._start}: hidden_states[{l}] was not computed")
+        _, B, _, L = self._last
+        w = self._workspace(B, L)
+        return self._hidden_buf(w, l).view(B, w["f"]["T"], self.cfg.hidden_size).clone()
+
+    def forward_from(self, layer: int, hidden: torch.Tensor):
+        """The classifier from ``hidden_states[layer]`` on: ``hidden [R, T, H]`` fp32 rows take the place of the layer's input,
+        layers ``layer .. nl-1`` run with the saves of ``forward`` (so that ``backward(to_layer >= layer)`` works afterwards),
+        then the final LayerNorm of a full-depth pre-LN model -- it produces ``hidden_states[nl]``, so a chain started AT ``nl``
+        is the pooling + logreg alone -- and the pooling + logreg.  Nothing below the layer is launched.  ``T`` must be the
+        frame count of the last ``forward`` (its clip length picks the workspace).  Returns ``(logits [R,1], probs [R,1])``."""
+        l = check_layer(layer, self.emb.nl)
+        if getattr(self, "_last", None) is None:
+            raise RuntimeError("forward_from() needs one forward pass first (it fixes the clip length of the workspace)")
+        L = self._last[3]
+        H, nl = self.cfg.hidden_size, self.emb.nl
+        if not torch.is_tensor(hidden) or hidden.dim() != 3 or hidden.dtype != torch.float32 or not hidden.is_cuda:
+            raise ValueError("hidden must be a CUDA fp32 tensor [R, T, H]")
+        R = hidden.shape[0]
+        w = self._workspace(R, L)
+        f = w["f"]
+        T, M = f["T"], f["M"]
+        if tuple(hidden.shape[1:]) != (T, H):
+            raise ValueError(f"hidden must be [R, {T}, {H}] (the frames of the last forward), not {list(hidden.shape)}")
+        hidden = hidden.contiguous()
+        self._final_ln = self.stable and nl == self.cfg.num_hidden_layers
+        # post-LN: layer l reads its GEMM operand from h16, which the previous LayerNorm wrote -- written here from the same values
+        op = f["h16"] if (l < nl and not self.stable) else None
+        _lib.check(_lib.lib().advh_layer_inject(
+            hidden.data_ptr(), M, H, self._hidden_buf(w, l).data_ptr(), None if op is None else op.data_ptr(), int(self.split),
+            op.stride(0) if (op is not None and self.split) else 0, torch.cuda.current_stream().cuda_stream), "advh_layer_inject")
+        self._start = l
+        st = torch.cuda.current_stream().cuda_stream
+        if l == nl:
+            _lib.check(_lib.lib().advh_pool_logreg(self._hidden_buf(w, l).data_ptr(), self.emb.coef.data_ptr(), self.emb.intercept,
+                                                   f["logit"].data_ptr(), f["prob"].data_ptr(), None, R, T, H, st), "advh_pool_logreg")
+        else:
+            self._encoder_tail(w, l, R)
+        self._last = (None, R, None, L)
+        return f["logit"].clone().view(R, 1), f["prob"].clone().view(R, 1)
+
+    def layer_tap(self, g: torch.Tensor, inv_scale: float = 1.0, act: Optional[torch.Tensor] = None, want_out: bool = True,
+                  row_sum: Optional[torch.Tensor] = None):
+        """advh_layer_tap on contiguous fp32 rows ``g [rows, ...]``: ``g * inv_scale (* act)`` as a fresh tensor of g's shape
+        (None with ``want_out=False``), and the per-row sums into ``row_sum [rows]`` if given."""
+        rows = g.shape[0]
+        out = torch.empty_like(g) if want_out else None
+        _lib.check(_lib.lib().advh_layer_tap(g.data_ptr(), None if act is None else act.data_ptr(), inv_scale, rows, g.numel() // rows,
+                                             None if out is None else out.data_ptr(), None if row_sum is None else row_sum.data_ptr(),
+                                             torch.cuda.current_stream().cuda_stream), "advh_layer_tap")
+        return out
 
     # ------------------------------------------------------------------ backward
     def _ln_bwd(self, ln, x, dy, M, out_f=None, out_h=None, add=None, dact=None, remap=(0, 0), gelu=False, eps=None):
@@ -275,9 +359,20 @@ class EmbedderGrad:
             _lib.check(lib.advh_attention_bwd_f16(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), B, T, H, heads, st),
                        "advh_attention_bwd_f16")
 
-    def backward(self, loss_scale: float = 4096.0, seed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def backward(self, loss_scale: float = 4096.0, seed: Optional[torch.Tensor] = None, to_layer: Optional[int] = None) -> torch.Tensor:
         """d logit / d wave for the clips of the last ``forward`` call: ``[B, n_in]`` fp32.  With ``seed [B]``
-        (dL/d logit per clip) the result is dL/d wave instead (vector-Jacobian product: LMACLoss backward)."""
+        (dL/d logit per clip) the result is dL/d wave instead (vector-Jacobian product: LMACLoss backward).
+        ``to_layer=l``: the chain stops once ``d logit / d hidden_states[l]`` is in the residual-stream buffer and returns it,
+        ``[B, T, H]`` fp32 (divided by ``loss_scale``, advh_layer_tap); the layers below, the positional convolution, the feature
+        encoder and the waveform kernels are not launched.  It works after ``forward`` and after ``forward_from(l', .)`` with
+        ``l' <= l``; ``hidden_states[nl]`` of a full-depth pre-LN model is the final LayerNorm's output, so ``to_layer=nl`` is the
+        pooling's backward alone there."""
+        stop = 0 if to_layer is None else check_layer(to_layer, self.emb.nl)
+        if to_layer is None and self._start is not None:
+            raise RuntimeError(f"the last pass started at layer {self._start} (forward_from): only backward(to_layer >= "
+                               f"{self._start}) is defined")
+        if to_layer is not None and self._start is not None and stop < self._start:
+            raise ValueError(f"the last pass started at layer {self._start}: the gradient at layer {stop} needs a pass from there")
         emb, cfg, lib, sp = self.emb, self.cfg, _lib.lib(), self.split
         wave, B, n_in, L = self._last
         w = self._workspace(B, L)
@@ -297,10 +392,10 @@ class EmbedderGrad:
         else:
             _lib.check(lib.advh_pool_logreg_bwd(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(), B, T, H, st),
                        "advh_pool_logreg_bwd")
-        if self._final_ln:
+        if self._final_ln and stop < nl:
             self._ln_bwd(emb.enc_ln, w["x"][nl], da, M, out_f=db, out_h=d16)
             da, db = db, da
-        for l in range(nl - 1, -1, -1):
+        for l in range(nl - 1, stop - 1, -1):
             bl = w["layers"][l]
             if self.stable:                                # da = d x_{l+1} (fp32), d16 its fp16 copy
                 bl["ff2"].run(d16, out_h=w["dI"], dact_src=w["g1"][l])
@@ -318,6 +413,8 @@ class EmbedderGrad:
                 bl["out"].run(d16, out_h=w["dctx"])
                 self._att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
                 bl["qkv"].run(w["dqkv"], out_f=da, resid=db)                                  # da = d x_l
+        if to_layer is not None:                                                              # da = d hidden_states[stop]
+            return self.layer_tap(da.view(B, T, H), 1.0 / loss_scale)
         if not self.stable:
             self._ln_bwd(emb.enc_ln, w["h1"], da, M, out_f=db)                                # d h1
             da, db = db, da

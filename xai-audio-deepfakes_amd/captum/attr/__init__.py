@@ -2,7 +2,10 @@
 (Saliency, InputXGradient, IntegratedGradients, GradientShap) on the HIP backward path, the perturbation methods (Occlusion,
 FeatureAblation, FeaturePermutation), the Shapley methods (ShapleyValueSampling, ShapleyValues, KernelShap) and Lime on the HIP
 forward with the ablated, permuted or coalition batches built on the device; NoiseTunnel (SmoothGrad, SmoothGrad-squared,
-VarGrad) around any of those eleven, with the noisy rows and the moments on the device.
+VarGrad) around any of those eleven, with the noisy rows and the moments on the device; and the layer methods (LayerActivation,
+LayerGradientXActivation, LayerIntegratedGradients, LayerConductance, InternalInfluence) at ``hidden_states[layer]`` of the
+encoder, on the HIP chain started and stopped at that layer (csrc/attribution_layer.hip).  They return ``[B, T, H]`` maps;
+NoiseTunnel does not wrap them.
 
 ``Method(model).attribute(inputs, target=None, ...)`` expects ``model`` to be a
 ``captum_saliency.Wav2vec2LogReg`` (or anything exposing ``.hip_attribution()``): the waveform -> logit
@@ -227,6 +230,102 @@ class FeaturePermutation(_Method):
         B, L = inputs.shape
         _A.check_permutation_args(feature_mask, B, L)
         return _engine(self.model).feature_permutation(inputs, feature_mask=feature_mask, internal_batch_size=ibs)
+
+
+def _layer_checks(model, inputs, target, layer, attribute_to_layer_input):
+    """The checks every layer method shares, before the engine is touched: one output (``target`` None), a ``[B, L]`` input, the
+    layer's output only (``attribute_to_layer_input=True`` raises NotImplementedError) and ``check_layer`` against the model's
+    ``layer_index`` (ValueError)."""
+    _Method._check(inputs, target)
+    if attribute_to_layer_input:
+        raise NotImplementedError("the layer methods (HIP build) attribute to a layer's output, hidden_states[layer]; "
+                                  "attribute_to_layer_input=True is not supported")
+    if not hasattr(model, "hip_attribution"):
+        raise TypeError("captum.attr (HIP build) only attributes captum_saliency.Wav2vec2LogReg models")
+    nl = model.num_layers() if hasattr(model, "num_layers") else None
+    if nl is not None:
+        _A.check_layer(layer, nl)
+    elif isinstance(layer, bool) or not isinstance(layer, int) or layer < 0:
+        raise ValueError(f"layer must be an integer index into hidden_states, not {layer!r}")
+
+
+class _LayerMethod(_Method):
+    """``Method(forward_func, layer)``: ``layer`` is an integer index ``l`` into the encoder's ``hidden_states``,
+    ``0 <= l <= layer_index`` -- not an ``nn.Module`` (the frozen embedder has none to hook).  Attributions are ``[B, T, H]``."""
+
+    def __init__(self, forward_func, layer, device_ids=None):
+        super().__init__(forward_func)
+        self.layer = layer
+
+
+class LayerActivation(_LayerMethod):
+    """Captum's LayerActivation: ``hidden_states[layer](inputs)``."""
+
+    def attribute(self, inputs, additional_forward_args=None, attribute_to_layer_input=False):
+        _layer_checks(self.model, inputs, None, self.layer, attribute_to_layer_input)
+        return _engine(self.model).layer_activation(inputs, self.layer)
+
+
+class LayerGradientXActivation(_LayerMethod):
+    """Captum's LayerGradientXActivation: ``dF/dh_l * h_l`` (the gradient alone with ``multiply_by_inputs=False``)."""
+
+    def __init__(self, forward_func, layer, device_ids=None, multiply_by_inputs=True):
+        super().__init__(forward_func, layer)
+        self.multiply_by_inputs = multiply_by_inputs
+
+    def attribute(self, inputs, target=None, additional_forward_args=None, attribute_to_layer_input=False):
+        _layer_checks(self.model, inputs, target, self.layer, attribute_to_layer_input)
+        return _engine(self.model).layer_gradient_x_activation(inputs, self.layer, multiply_by_inputs=self.multiply_by_inputs)
+
+
+def _layer_path_checks(method_obj, inputs, target, attribute_to_layer_input, baselines, n_steps, method, internal_batch_size,
+                       extra_point=False):
+    _layer_checks(method_obj.model, inputs, target, method_obj.layer, attribute_to_layer_input)
+    B, L = inputs.shape
+    _A.check_ig_baselines(baselines, B, L)
+    _A.approximation(method, _A.check_steps(n_steps, method) + int(extra_point))
+    if internal_batch_size is not None:
+        _A._positive_int(internal_batch_size, "internal_batch_size")
+
+
+class LayerIntegratedGradients(_LayerMethod):
+    """Captum's LayerIntegratedGradients: integrated gradients along the straight path between the layer's activations of the
+    baseline and of the input (``baselines`` live in waveform space: None, a number, ``[1, L]`` or ``[B, L]``).
+    ``return_convergence_delta=True`` returns ``(attributions, delta [B])``."""
+
+    def __init__(self, forward_func, layer, device_ids=None, multiply_by_inputs=True):
+        super().__init__(forward_func, layer)
+        self.multiply_by_inputs = multiply_by_inputs
+
+    def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, n_steps=50, method="gausslegendre",
+                  internal_batch_size=None, return_convergence_delta=False, attribute_to_layer_input=False):
+        _layer_path_checks(self, inputs, target, attribute_to_layer_input, baselines, n_steps, method, internal_batch_size)
+        return _engine(self.model).layer_integrated_gradients(
+            inputs, self.layer, baselines=baselines, n_steps=n_steps, method=method, internal_batch_size=internal_batch_size,
+            multiply_by_inputs=self.multiply_by_inputs, return_convergence_delta=return_convergence_delta)
+
+
+class LayerConductance(_LayerMethod):
+    """Captum's LayerConductance: ``sum_k dF/dh_l(x_k) * (h_l(x_{k+1}) - h_l(x_k))`` over ``n_steps + 1`` points of the
+    waveform-space path from the baseline to the input.  The convergence delta is not computed."""
+
+    def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, n_steps=50, method="gausslegendre",
+                  internal_batch_size=None, return_convergence_delta=False, attribute_to_layer_input=False):
+        _layer_path_checks(self, inputs, target, attribute_to_layer_input, baselines, n_steps, method, internal_batch_size, True)
+        if return_convergence_delta:
+            raise NotImplementedError("LayerConductance (HIP build) does not compute the convergence delta")
+        return _engine(self.model).layer_conductance(inputs, self.layer, baselines=baselines, n_steps=n_steps, method=method,
+                                                     internal_batch_size=internal_batch_size)
+
+
+class InternalInfluence(_LayerMethod):
+    """Captum's InternalInfluence: the layer gradient integrated along the waveform-space path from the baseline to the input."""
+
+    def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, n_steps=50, method="gausslegendre",
+                  internal_batch_size=None, attribute_to_layer_input=False):
+        _layer_path_checks(self, inputs, target, attribute_to_layer_input, baselines, n_steps, method, internal_batch_size)
+        return _engine(self.model).internal_influence(inputs, self.layer, baselines=baselines, n_steps=n_steps, method=method,
+                                                      internal_batch_size=internal_batch_size)
 
 
 _WRAPPABLE = (Saliency, InputXGradient, IntegratedGradients, GradientShap, Occlusion, FeatureAblation, FeaturePermutation,

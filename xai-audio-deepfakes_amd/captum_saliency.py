@@ -12,6 +12,8 @@ from captum.attr import Saliency, InputXGradient, IntegratedGradients, GradientS
 from captum.attr import Occlusion, FeatureAblation  # noqa: F401
 from captum.attr import ShapleyValueSampling, ShapleyValues, KernelShap  # noqa: F401
 from captum.attr import Lime, FeaturePermutation  # noqa: F401
+from captum.attr import LayerActivation, LayerGradientXActivation, LayerIntegratedGradients, LayerConductance  # noqa: F401
+from captum.attr import InternalInfluence  # noqa: F401
 from captum.attr._core.lime import get_exp_kernel_similarity_function  # noqa: F401
 from captum._utils.models.linear_model import SkLearnLasso, SkLearnRidge, SkLearnLinearRegression  # noqa: F401
 from captum.metrics import infidelity, sensitivity_max, NoisyPerturbation  # noqa: F401
@@ -45,6 +47,12 @@ class Wav2vec2LogReg(nn.Module):
         logits, _ = self.ap.classify(waveform)
         return logits
 
+    def num_layers(self):
+        """``nl``: the last index into ``hidden_states`` that reaches the logit (``HipEmbedder.nl``), from the configuration
+        alone -- the layer methods check their ``layer`` against it before any GPU work."""
+        cfg, _ = _rt.embedder_config_and_weights()
+        return min(cfg.layer_index, cfg.num_hidden_layers)
+
     def hip_attribution(self):
         if self._att is None:
             from addvisor_hip.attribution import HipAttribution
@@ -73,9 +81,18 @@ def _check_batch(method, waves):
         raise ValueError("method='feature_permutation' takes each segment from another clip of the batch: pass two clips or more")
 
 
-def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5, stdevs=0.01):
+def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5, stdevs=0.01, layer=None):
     """The attribution of ``explain_waves``'s ``method`` (wrapped in NoiseTunnel when ``nt_type`` is set) as a callable
-    ``[R, L] -> [R, L]`` on the engine ``att``."""
+    ``[R, L] -> [R, L]`` on the engine ``att``.  The layer methods attribute ``hidden_states[layer]`` (default: the layer the
+    classifier reads); their ``[R, T, H]`` map is summed over the channels and each frame's relevance spread to its samples
+    (``HipAttribution.layer_relevance``)."""
+    if method in ("layer_integrated_gradients", "layer_gradient_x_activation"):
+        if nt_type is not None:
+            raise ValueError("NoiseTunnel does not wrap the layer methods")
+        l = att.eg.emb.nl if layer is None else layer
+        if method == "layer_integrated_gradients":
+            return lambda w: att.layer_relevance(att.layer_integrated_gradients(w, l, n_steps=n_steps), w.shape[-1])
+        return lambda w: att.layer_relevance(att.layer_gradient_x_activation(w, l), w.shape[-1])
     fn = {"saliency": att.saliency, "input_x_gradient": att.input_x_gradient,
           "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
           "occlusion": lambda w: att.occlusion(w, window, stride),
@@ -89,20 +106,22 @@ def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, n
 
 
 def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5,
-                  stdevs=0.01):
+                  stdevs=0.01, layer=None):
     """Loop body of compute_camptum_saliency_metrics (captum_saliency.py:125-192) for a batch ``[B, L]``:
     attribution -> |attr|/max time mask -> wave*mask, wave*(1-mask) -> three classifier passes.
     ``method="occlusion"`` occludes ``window``-sample windows every ``stride`` samples (default 100 ms / 50 ms at 16 kHz);
     ``method="shapley_value_sampling"`` / ``"kernel_shap"`` attribute ``window``-sample segments (default n_samples = 25), as do
     ``"lime"`` (n_samples = 50, the cosine kernel, a Lasso with alpha = 0.01) and ``"feature_permutation"`` (each segment taken
     from another clip of the batch: it needs two clips or more, ValueError before any GPU work otherwise).
+    ``method="layer_integrated_gradients"`` / ``"layer_gradient_x_activation"`` attribute ``hidden_states[layer]`` (``layer=None``:
+    the layer the classifier reads) and mask the waveform with each frame's relevance summed over the channels.
     ``nt_type`` ("smoothgrad", "smoothgrad_sq", "vargrad") wraps the method in NoiseTunnel over ``nt_samples`` noisy copies
     of each clip; ``stdevs`` is the noise's standard deviation in waveform units (Captum's default of 1.0 would drown a
     waveform in [-1, 1]).  Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
     _check_batch(method, waves)
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
-    attr = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs)(x)
+    attr = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs, layer)(x)
     _, w_rel, w_irr = att.time_mask(attr, x)
     emb = _rt.hip_embedder()
     B = x.shape[0]
@@ -111,7 +130,7 @@ def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=16
 
 
 def score_explanations(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5,
-                       stdevs=0.01, n_perturb_samples=10, perturb_radius=0.02, norm_ord="fro", multiply_by_inputs=False):
+                       stdevs=0.01, n_perturb_samples=10, perturb_radius=0.02, norm_ord="fro", multiply_by_inputs=False, layer=None):
     """Captum's two explanation metrics of ``explain_waves``'s attribution (``method``, optionally in NoiseTunnel) for a batch
     ``[B, L]``: ``{"infidelity": [B], "sensitivity_max": [B]}`` fp32.  Infidelity perturbs each clip ``n_perturb_samples``
     times with ``NoisyPerturbation(stdevs, multiply_by_inputs)`` (``x - stdevs * N(0, 1)``; ``stdevs`` in waveform units, as in
@@ -120,7 +139,7 @@ def score_explanations(model, waves, method="input_x_gradient", n_steps=50, wind
     _check_batch(method, waves)
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
-    explain = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs)
+    explain = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs, layer)
     attr = explain(x)
     return {"infidelity": infidelity(model, NoisyPerturbation(stdevs, multiply_by_inputs), x, attr,
                                      n_perturb_samples=n_perturb_samples),

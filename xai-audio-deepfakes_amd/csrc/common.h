@@ -9,6 +9,7 @@ int advh_init_attention();   // attention.hip
 // per-translation-unit setters of the split-format range flag pointer (csrc/device_math.h: ADVH_SPLIT_FLAG_SETTER)
 int advh_split_flag_attention(int* flag);
 int advh_split_flag_attention_bwd_f32(int* flag);
+int advh_split_flag_attribution_layer(int* flag);
 int advh_split_flag_attention_bwd_x3(int* flag);
 int advh_split_flag_backward(int* flag);
 int advh_split_flag_conv_taps(int* flag);
