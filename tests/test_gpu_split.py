@@ -15,6 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import embedder_ops_ref
 from addvisor_hip import _lib, gemm as G, ops, synthetic as syn
 from addvisor_hip.embedder import HipEmbedder
 from addvisor_hip.unet import HipUNet
@@ -204,7 +205,16 @@ def test_split_unet_5s_exact_indices(gpu_device, golden):
     assert hashlib.sha256(idx.tobytes()).digest() == g["idx_sha256"].tobytes()
 
 
-@pytest.mark.parametrize("T,heads,dm", [(199, 3, 64), (49, 2, 32), (17, 2, 16), (199, 2, 120), (249, 1, 128), (113, 2, 72), (40, 2, 120)])
+ATT_CASES = [(199, 3, 64), (49, 2, 32), (17, 2, 16), (199, 2, 120), (249, 1, 128), (113, 2, 72), (40, 2, 120),
+             (199, 2, 40), (100, 2, 48), (256, 1, 56), (30, 3, 56),              # attention_x3_kernel<*, 64>: head dims 40 / 48 / 56
+             (100, 2, 64), (256, 2, 64), (65, 1, 64), (64, 1, 64),               # the NT = 8 and 16 instances, the 64 / 65 boundary
+             (256, 2, 32), (100, 2, 16), (1, 2, 32), (16, 1, 64),                # one frame, one whole 16-row tile
+             (208, 1, 64), (209, 1, 64),                                         # NT = 13 / 16
+             (112, 1, 120), (113, 1, 120), (224, 1, 120), (225, 1, 120), (256, 1, 128),   # the streaming kernel's key blocks of 112
+             (199, 1, 72), (60, 2, 104)]
+
+
+@pytest.mark.parametrize("T,heads,dm", ATT_CASES)
 def test_split_attention_kernel(gpu_device, T, heads, dm):
     """advh_attention_split (softmax(Q K^T / sqrt(d)) V, modeling_wav2vec2.py:438-548) against fp64 on split-format q | k | v:
     whole-clip K / V^T in LDS for head dims <= 64, key blocks of 112 with an online softmax above (XLS-R's 120).
@@ -224,6 +234,29 @@ def test_split_attention_kernel(gpu_device, T, heads, dm):
     e = rel(G.join_planes(ctx), ref)
     print(f"split attention T={T} heads={heads} dm={dm}: rel {e:.2e}")
     assert e <= TOL_KERNEL
+
+
+@pytest.mark.parametrize("T,heads,dm", ATT_CASES + [(199, 12, 64)])
+def test_attention_f16_kernel(gpu_device, T, heads, dm):
+    """advh_attention_f16 (the f16 mode's forward attention) against fp64 on the fp16 q | k | v the kernel reads.  The kernel
+    rounds the probabilities to fp16 before P V and the result to fp16, so elementwise
+    |out - ref| <= 2^-11 (sum_j p_j |v_j| + |ref|) (1 + 2^-6) + 5e-6 max|v|, p from the fp64 reference."""
+    _lib.init()
+    B, H = 2, heads * dm
+    g = torch.Generator().manual_seed(T + dm)
+    qkv = (rnd(g, B * T, 3 * H) * 1.5).half()
+    ctx = torch.full((B * T, H), 7.0, dtype=torch.float16, device=gpu_device)
+    dq = qkv.to(gpu_device)
+    _lib.check(_lib.lib().advh_attention_f16(dq.data_ptr(), ctx.data_ptr(), B, T, H, heads, torch.cuda.current_stream().cuda_stream),
+               "advh_attention_f16")
+    x = qkv.double().view(B, T, 3, heads, dm)
+    q, k, v = (x[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+    ref, p = embedder_ops_ref.attention(q, k, v)
+    bound = 2.0 ** -11 * (p @ v.abs() + ref.abs()) * (1 + 2.0 ** -6) + TOL_KERNEL * v.abs().max()
+    out = ctx.cpu().double().view(B, T, heads, dm).permute(0, 2, 1, 3)
+    ratio = ((out - ref).abs() / bound).max().item()
+    print(f"f16 attention T={T} heads={heads} dm={dm}: worst |err| / bound {ratio:.3f}, rel {rel(out, ref):.2e}")
+    assert ratio <= 1.0
 
 
 def test_split_xlsr_shaped_embedder(gpu_device):

@@ -148,6 +148,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wave, long stride, int n_in, int L,
                                                     const float2* __restrict__ stats, const float* __restrict__ w0,
                                                     const float* __restrict__ bias, const float2* __restrict__ norm,
+                                                    const float* __restrict__ beta,
                                                     _Float16* __restrict__ out, long out_lo, int T0, int P0, int C0, int mode) {
     __shared__ float xs[TT * S0 + K0];
     const int b = blockIdx.y, t0 = blockIdx.x * TT, tid = threadIdx.x;
@@ -166,7 +167,12 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wa
 #pragma unroll
         for (int k = 0; k < K0; ++k) wr[j][k] = w0[(c + j) * K0 + k];
         sc[j] = 1.f; sh[j] = 0.f;
-        if (mode == 0) { float2 nn = norm[(long)b * C0 + c + j]; sc[j] = nn.x; sh[j] = nn.y; }
+        if (mode == 0) {
+            float2 nn = norm[(long)b * C0 + c + j]; sc[j] = nn.x; sh[j] = nn.y;
+            // One frame: its deviation from the mean over time is identically zero, so y = beta.  conv * scale + shift would
+            // instead show conv's fp32 rounding times rstd = 1 / sqrt(eps) = 316 (4e-4 of the output).
+            if (T0 == 1) { sc[j] = 0.f; sh[j] = beta[c + j]; }
+        }
         else if (bias) sh[j] = bias[c + j];
     }
     const int tend = min(TT, P0 - t0);
@@ -207,7 +213,7 @@ static int frontend_launch(const float* wave, int64_t wave_stride, int n_in, int
         hipLaunchKernelGGL(gn_stats_kernel, dim3(B), dim3(256), 0, s, wave, (long)wave_stride, n_in, L,
                            (const float2*)stats_ws, w0, gamma, beta, (float2*)norm_ws, (float2*)mr_ws, T0, C0);
     hipLaunchKernelGGL(conv0_kernel, dim3((P0 + TT - 1) / TT, B), dim3(256), 0, s, wave, (long)wave_stride, n_in, L,
-                       (const float2*)stats_ws, w0, bias0, (const float2*)norm_ws, (_Float16*)out, (long)out_lo, T0, P0, C0, mode);
+                       (const float2*)stats_ws, w0, bias0, (const float2*)norm_ws, beta, (_Float16*)out, (long)out_lo, T0, P0, C0, mode);
     return ADVH_LAUNCH_CHECK();
 }
 

@@ -19,7 +19,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 
 // LayerNorm over the last dim C (C % 4 == 0, C <= 64*4*MAXV): torch.nn.functional.layer_norm semantics
-// (biased variance, eps inside the sqrt); two-pass in registers for accuracy.
+// (biased variance, eps inside the sqrt); two-pass in registers, with the mean's own rounding taken out, for accuracy.
 // in: fp32 or fp16 rows, optionally + an fp16 addend row (residual + branch); out_f (fp32) and/or out_h (fp16);
 // optional GELU after the affine.
 template <bool IN_F32, int MAXV>
@@ -54,24 +54,28 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
             v[i][0] = v[i][1] = v[i][2] = v[i][3] = 0.f;
         }
     }
+    // The fp32 mean carries the rounding of its sum (and of its own storage): up to ~2^-24 |mean|, which a row with
+    // |mean| >> std would see as an offset of 2^-24 |mean| / std in every output.  The residuals d = v - mean are exact there,
+    // so their own mean `dm` is that rounding: it is taken out of d and of the variance (sum (d - dm)^2 = sum d^2 - C dm^2).
     const float mean = wave_sum(s) / C;
-    float q = 0.f;
+    float q = 0.f, sd = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         int c = (i * 64 + lane) * 4;
         if (c < C) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { float d = v[i][r] - mean; q += d * d; }
+            for (int r = 0; r < 4; ++r) { float d = v[i][r] - mean; v[i][r] = d; sd += d; q += d * d; }
         }
     }
-    const float rstd = rsqrtf(wave_sum(q) / C + eps);
+    const float dm = wave_sum(sd) / C;
+    const float rstd = rsqrtf(fmaxf(wave_sum(q) / C - dm * dm, 0.f) + eps);
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         int c = (i * 64 + lane) * 4;
         if (c < C) {
             float4 g = *(const float4*)(gamma + c), b = *(const float4*)(beta + c);
-            float o[4] = {(v[i][0] - mean) * rstd * g.x + b.x, (v[i][1] - mean) * rstd * g.y + b.y,
-                          (v[i][2] - mean) * rstd * g.z + b.z, (v[i][3] - mean) * rstd * g.w + b.w};
+            float o[4] = {(v[i][0] - dm) * rstd * g.x + b.x, (v[i][1] - dm) * rstd * g.y + b.y,
+                          (v[i][2] - dm) * rstd * g.z + b.z, (v[i][3] - dm) * rstd * g.w + b.w};
             if (gelu) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[r] = gelu_fast(o[r]);
