@@ -722,9 +722,11 @@ typedef struct advh_taps_desc {
 } advh_taps_desc;
 /* The same layer in the fp32-class mode, C = 64: X, W, resid, out_h, out_h2 are split-format plane pairs (lo plane x_lo / w_lo / r_lo /
  * o_lo elements behind the hi plane; out_h and out_h2 share o_lo), three MFMAs per fragment pair (the arithmetic of the x3 GEMM).  The weights
- * stream tap by tap through a two-slot LDS ring (two planes of an 11-tap tensor do not fit), the line buffer is double-buffered;
- * advh_conv_taps_split_tile(C, ntap, span) = positions per tile, 0 if the layer does not fit.  pre_act is not supported (ADVH_EUNSUPPORTED).
- * Replaces the x3 implicit GEMM for the k = 7 / 11 ResBlock convolutions of HiFi-GAN's 64-channel stage (hifigan.py:106-110, 180).  */
+ * stream tap by tap through a four-slot LDS ring, tap n + 3 requested when tap n starts (two planes of an 11-tap tensor do not fit); there is
+ * ONE line buffer, the next tile's lines are requested after the last tap and land under the epilogue.
+ * advh_conv_taps_split_tile(C, ntap, span) = positions per tile (256), 0 if the layer does not fit.  pre_act is not supported (ADVH_EUNSUPPORTED).
+ * Replaces the x3 implicit GEMM for ResBlock convolutions of HiFi-GAN's 64-channel stage (hifigan.py:106-110, 180): the first of a step from
+ * k = 3, the second from k = 7 (gemm.select_conv1d).  */
 int advh_conv_taps_split_tile(int C, int ntap, int span);
 int advh_conv_taps_split(const advh_taps_desc* d, int C, int64_t x_lo, int64_t w_lo, int64_t r_lo, int64_t o_lo, advh_stream_t stream);
 /* 2-D variant: 3x3 stride-1 "same" Conv2d, C_in = C_out = C in {32, 64}, on zero-haloed NHWC fp16 maps of ONE geometry
@@ -810,7 +812,7 @@ int advh_conv53s21_tile_lds_bytes(void);
 int advh_conv53s21_tile_split_lds_bytes(void);
 int advh_conv53s21_tile_split(const advh_convs21_desc* d, int Ci, int N, int64_t x_lo, int64_t w_lo, int64_t o_lo, advh_stream_t stream);
 int advh_conv_taps_tile(int C, int ntap, int span);       /* positions per workgroup tile (128/192/256); 0 = does not fit */
-int advh_conv_taps_lds_bytes(int C, int ntap, int span);  /* weights + two line buffers; -1 = does not fit           */
+int advh_conv_taps_lds_bytes(int C, int ntap, int span);  /* advh_conv_taps_f16: weights + two line buffers; -1 = does not fit */
 int advh_conv_taps_f16(const advh_taps_desc* d, int C, advh_stream_t stream);
 
 /* ---- training step of the U-Net mask decoder (addvisor.py:12-84 under train_addvisor.py:364-378)

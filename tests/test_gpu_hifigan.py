@@ -157,3 +157,39 @@ def test_split_line_tile_matches_implicit_gemm(gpu_device, k, dil, B, T):
         print(f"split line tile vs implicit GEMM, k={k} d={dil} {name}: {err:.2e}")
         assert err <= 1e-6, name
         assert float(ja[:, :halo].abs().max()) == 0.0 and float(ja[:, halo + T:].abs().max()) == 0.0      # the halo stays zero
+
+
+_NETWORK_CASE = {}
+
+
+def _network_case(padding_mode):
+    """Tiny generator, B = 2, T = 9 (the 32-channel stage: both clips inside one 256-position tile plus a ragged tile; the 64-channel
+    stage inside one tile): input and oracle waveform, computed once per padding mode."""
+    if padding_mode not in _NETWORK_CASE:
+        cfg = syn.hifigan_tiny_config()
+        sd = syn.hifigan_weights(cfg)
+        r = np.random.Generator(np.random.PCG64(9))
+        mel = torch.from_numpy(r.normal(-4.0, 2.0, size=(2, cfg.in_channels, 9)).astype(np.float32))
+        _NETWORK_CASE[padding_mode] = (cfg, sd, mel, hifigan_ref.generator(mel, sd, cfg, padding_mode=padding_mode))
+    return _NETWORK_CASE[padding_mode]
+
+
+@pytest.mark.parametrize("precision,line_tile,fuse,padding_mode,nsteps", [
+    ("f16", True, True, "reflect", 154),        # implicit GEMM + halo fills, whatever the flags say
+    ("f16", False, True, "zeros", 81),          # fp16 implicit GEMM only
+    ("f16", True, False, "zeros", 81),          # fp16 line tile, no fused steps
+    ("f16", True, True, "zeros", 66),           # fp16 fused steps (the default f16 network)
+    ("f32", True, False, "zeros", 81),          # x3 implicit GEMM only
+    ("f32", True, True, "zeros", 72),           # fused 32-channel steps + 64-channel split line tile (the default network)
+])
+def test_every_network_against_oracle(gpu_device, precision, line_tile, fuse, padding_mode, nsteps):
+    """The six distinct networks of tests/test_hifigan_plan_select_cpu.py's table, each decoded and compared with the oracle at the
+    stated tolerance of its precision: the GEMM-only and taps-only forms are no default of any other test."""
+    cfg, sd, mel, ref = _network_case(padding_mode)
+    net = HipHifigan(cfg, sd, gpu_device, line_tile=line_tile, fuse=fuse, padding_mode=padding_mode, precision=precision)
+    assert len(net._workspace(2, 9)["steps"]) == nsteps
+    wav = net.decode_batch(mel.to(gpu_device))
+    assert wav.shape == ref.shape == (2, 1, 9 * cfg.hop)
+    err = (wav.cpu() - ref).abs()
+    print(f"hifigan [{precision}] line_tile={line_tile} fuse={fuse} {padding_mode}: max err {err.max():.3e} mean {err.mean():.3e}")
+    assert err.max().item() <= TOL[precision][0] and err.mean().item() <= TOL[precision][1]

@@ -31,7 +31,9 @@ for plan, srcs, dst in ws["steps"]:
     e1.record(); e1.synchronize()
     ms = e0.elapsed_time(e1) / 5
     tot += ms
-    kind = getattr(plan, "kind", None) or G.TILE_NAMES[plan.tile] + ("*" if isinstance(plan, G.PlanGroup) else "")
+    kind = getattr(plan, "kind", "gemm")
+    if kind == "gemm":
+        kind = G.TILE_NAMES[plan.tile] + ("*" if isinstance(plan, G.PlanGroup) else "")
     kind += "+head" if getattr(plan, "head", None) else ""
     print(f"{'+'.join(srcs):8s} -> {dst:4s} {kind:14s} {ms*1e3:8.1f} us  {plan.flops/ms/1e9:7.1f} TFLOP/s  ({plan.flops/1e9:6.1f} GF)")
 print(f"total GEMM-shaped layers {tot:.3f} ms")

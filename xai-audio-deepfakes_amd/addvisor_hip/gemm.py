@@ -201,6 +201,7 @@ class Source:
 
 class GemmPlan:
     """One launch of the implicit GEMM.  ``ktab_host``/``desc`` stay inspectable for the CPU tests."""
+    kind = "gemm"
 
     def __init__(self, *, M: int, N: int, w2: torch.Tensor, ktab: np.ndarray, sources: Sequence[Source],
                  Hg: int, Wg: int, window: Tuple[int, int, int, int], halo_zero: bool,
@@ -903,7 +904,6 @@ def plan_conv1d_same(src: Map1D, dst: Map1D, weight: torch.Tensor, bias: Optiona
                     bias=bias, act=act, slope=slope, slope2=slope2, device=device, split=dst.split)
 
 
-
 # ------------------------------------------------------------------------------------ LDS line-tile conv (narrow C)
 class TapsDesc(C.Structure):
     """Mirror of ``advh_taps_desc`` (include/addvisor_hip.h)."""
@@ -944,17 +944,14 @@ class TapsPlan:
         ntap = len(toff)
         assert w_taps.shape == (ntap, Cn, Cn) and Cn in (32, 64) and 0 < ntap <= 16
         span = max(max(toff), 0) - min(min(toff), 0)
-        self.split = split
+        self.split, self.kind = split, "taps_x3" if split else "taps"
         if split:
             assert pre_slope is None and taps_split_tile(Cn, ntap, span) > 0
         else:
             assert taps_tile(Cn, ntap, span) > 0
         self.Cn, self.device = Cn, device
-        self.w = split_planes(w_taps.double()).contiguous() if split else w_taps.to(torch.float16).contiguous()     # [2, ntap, C, C] | [ntap, C, C]
-        self.bias = None if bias is None else bias.to(torch.float32).contiguous()
-        if device is not None:
-            self.w = self.w.to(device)
-            self.bias = None if self.bias is None else self.bias.to(device)
+        self.w = _to(device, split_planes(w_taps.double()).contiguous() if split else w_taps.to(torch.float16).contiguous())     # [2, ntap, C, C] | [ntap, C, C]
+        self.bias = _to(device, None if bias is None else bias.to(torch.float32).contiguous())
         d = TapsDesc()
         d.M, d.Hg, d.Wg = M, Hg, Wg
         d.h0, d.h1, d.w0, d.w1 = window
@@ -1118,11 +1115,42 @@ def select_upconv2d(coarse: FMap, skip: FMap, dst: FMap, wt: torch.Tensor, bt: t
                          slope=slope, device=device)
 
 
+# ------------------------------------------------------------------------------------ which kernel a vocoder layer gets
+def select_conv1d(src: Map1D, dst: Map1D, weight: torch.Tensor, bias: Optional[torch.Tensor], *, role: str, line_tile: bool,
+                  split_tile: bool, dilation: int = 1, pre_slope: Optional[float] = None, **kw):
+    """The plan of one HiFi-GAN ResBlock convolution (the maps need no storage; ``kw``: ``plan_conv1d_same``'s ``act``, ``slope``, ``slope2``,
+    ``device``).  ``role``: "conv1" (bias + LeakyReLU) or "conv2" (bias + residual, raw and pre-activated outputs) of its step.  fp16 maps
+    with ``line_tile``: the weights-in-LDS tile where ``taps_supported``.  Split maps with ``split_tile``: the streamed-weight tile of a
+    64-channel layer, from k = 3 for a conv1 and k = 7 for a conv2 (``taps_split_supported`` states the measurements), never with ``pre_slope``.
+    Every other layer runs the implicit GEMM, which cannot activate its input: a ``pre_slope`` layer that ends up there is an error."""
+    assert role in ("conv1", "conv2")
+    kw["dilation"] = dilation
+    if line_tile and not src.split and taps_supported(src, dst, weight, dilation):
+        return plan_conv1d_taps(src, dst, weight, bias, pre_slope=pre_slope, **kw)
+    if split_tile and pre_slope is None and taps_split_supported(src, dst, weight, dilation, min_k=3 if role == "conv1" else 7):
+        return plan_conv1d_taps(src, dst, weight, bias, **kw)
+    if pre_slope is not None:
+        raise RuntimeError("a layer of a line-buffer-activated stage does not fit the line-tile kernel")
+    return plan_conv1d_same(src, dst, weight, bias, **kw)
+
+
+def select_resblock_step(src: Map1D, dst: Map1D, w1, b1, w2, b2, *, dilation: int, slope: float, fused: bool, device=None):
+    """The fused plan of one HiFi-GAN ResBlock step in the maps' format (fp16: 32 or 64 channels while both weight tensors fit in LDS;
+    split: 32 channels), or None -- not ``fused``, or not the kernel's geometry -- when it must run as two convolutions."""
+    pair = ResblockPairX3Plan if dst.split else ResblockPairPlan
+    return pair(src, dst, w1, b1, w2, b2, dilation=dilation, slope=slope, device=device) if fused and pair.supported(src, dst, w1, w2, dilation) else None
+
+
 class ResblockDesc(C.Structure):
     """Mirror of ``advh_resblock_desc`` (include/addvisor_hip.h)."""
     _fields_ = [("X", C.c_void_p), ("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
                 ("out_h", C.c_void_p), ("M", C.c_int), ("Wg", C.c_int), ("w0", C.c_int), ("w1", C.c_int), ("k", C.c_int),
                 ("dil", C.c_int), ("slope", C.c_float)]
+
+
+class ResblockX3Desc(C.Structure):
+    """Mirror of ``advh_resblock_x3_desc``: ``advh_resblock_desc`` + the distances hi -> lo plane of the maps and the weights (elements)."""
+    _fields_ = ResblockDesc._fields_ + [("x_lo", C.c_int64), ("o_lo", C.c_int64), ("w_lo", C.c_int64)]
 
 
 def resblock_pair_lds_bytes(Cn: int, k: int, dil: int) -> int:
@@ -1132,49 +1160,6 @@ def resblock_pair_lds_bytes(Cn: int, k: int, dil: int) -> int:
     buf = ((rows * (Cn // 8) + 63) // 64 * 64) * 16
     one = 2 * k * Cn * Cn * 2 + buf
     return one if (one <= 80 * 1024 or one + buf > TAPS_MAX_LDS) else one + buf
-
-
-def resblock_pair_supported(src: Map1D, dst: Map1D, w1: torch.Tensor, w2: torch.Tensor, dilation: int) -> bool:
-    Cn, k = w1.shape[0], w1.shape[2]
-    return (Cn in (32, 64) and tuple(w1.shape) == (Cn, Cn, k) and tuple(w2.shape) == (Cn, Cn, k) and k % 2 == 1 and src.C == Cn
-            and dst.C == Cn and (src.B, src.T, src.halo) == (dst.B, dst.T, dst.halo) and src.halo >= (k - 1) * dilation // 2
-            and resblock_pair_lds_bytes(Cn, k, dilation) <= TAPS_MAX_LDS)
-
-
-class ResblockPairPlan:
-    """One launch of ``advh_resblock_pair_f16``: ``dst = src + conv2(lrelu(conv1(lrelu(src))))`` (HiFi-GAN ResBlock1 step)."""
-
-    def __init__(self, src: Map1D, dst: Map1D, w1, b1, w2, b2, *, dilation: int, slope: float, device=None):
-        assert resblock_pair_supported(src, dst, w1, w2, dilation)
-        Cn, k = w1.shape[0], w1.shape[2]
-        self.Cn = Cn
-        pack = lambda w: w.permute(2, 0, 1).to(torch.float16).contiguous()
-        self.w1, self.w2 = pack(w1), pack(w2)
-        self.b1, self.b2 = b1.to(torch.float32).contiguous(), b2.to(torch.float32).contiguous()
-        if device is not None:
-            self.w1, self.w2, self.b1, self.b2 = (t.to(device) for t in (self.w1, self.w2, self.b1, self.b2))
-        d = ResblockDesc()
-        d.M, d.Wg, d.w0, d.w1, d.k, d.dil, d.slope = dst.B * dst.P, dst.P, dst.halo, dst.halo + dst.T, k, dilation, slope
-        self.desc = d
-        self.flops = 2 * 2.0 * dst.B * dst.T * Cn * Cn * k
-
-    def run(self, A0: torch.Tensor, A1=None, *, out_h: torch.Tensor, stream: Optional[int] = None, **_):
-        d = self.desc
-        for t in (A0, out_h):
-            assert t.dtype == torch.float16 and t.is_cuda and t.is_contiguous() and t.numel() == d.M * self.Cn
-        assert A0.data_ptr() != out_h.data_ptr()
-        d.X, d.out_h = A0.data_ptr(), out_h.data_ptr()
-        d.W1, d.W2, d.b1, d.b2 = self.w1.data_ptr(), self.w2.data_ptr(), self.b1.data_ptr(), self.b2.data_ptr()
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().advh_resblock_pair_f16(C.byref(d), self.Cn, stream), "advh_resblock_pair_f16")
-
-
-class ResblockX3Desc(C.Structure):
-    """Mirror of ``advh_resblock_x3_desc`` (include/addvisor_hip.h)."""
-    _fields_ = [("X", C.c_void_p), ("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
-                ("out_h", C.c_void_p), ("M", C.c_int), ("Wg", C.c_int), ("w0", C.c_int), ("w1", C.c_int), ("k", C.c_int),
-                ("dil", C.c_int), ("slope", C.c_float), ("x_lo", C.c_int64), ("o_lo", C.c_int64), ("w_lo", C.c_int64)]
 
 
 def resblock_pair_x3_lds_bytes(Cn: int, k: int, dil: int) -> int:
@@ -1188,42 +1173,67 @@ def resblock_pair_x3_lds_bytes(Cn: int, k: int, dil: int) -> int:
     return lds if lds <= TAPS_MAX_LDS else -1
 
 
-def resblock_pair_x3_supported(src: Map1D, dst: Map1D, w1: torch.Tensor, w2: torch.Tensor, dilation: int) -> bool:
+def _resblock_pair_fits(src: Map1D, dst: Map1D, w1: torch.Tensor, w2: torch.Tensor, dilation: int, lds_bytes) -> bool:
+    """Both fused ResBlock kernels: two square odd-k weights of one shape, maps of one geometry, halo >= padding, and the kernel's
+    ``lds_bytes(Cn, k, dilation)`` (<= 0: not its geometry) within the LDS."""
     Cn, k = w1.shape[0], w1.shape[2]
-    return (src.split and dst.split and Cn == 32 and tuple(w1.shape) == (Cn, Cn, k) and tuple(w2.shape) == (Cn, Cn, k) and k % 2 == 1
-            and src.C == Cn and dst.C == Cn and (src.B, src.T, src.halo) == (dst.B, dst.T, dst.halo)
-            and src.halo >= (k - 1) * dilation // 2 and resblock_pair_x3_lds_bytes(Cn, k, dilation) > 0)
+    return (tuple(w1.shape) == (Cn, Cn, k) and tuple(w2.shape) == (Cn, Cn, k) and k % 2 == 1 and src.C == Cn and dst.C == Cn
+            and (src.B, src.T, src.halo) == (dst.B, dst.T, dst.halo) and src.halo >= (k - 1) * dilation // 2
+            and 0 < lds_bytes(Cn, k, dilation) <= TAPS_MAX_LDS)
 
 
-class ResblockPairX3Plan:
-    """One launch of ``advh_resblock_pair_x3``: ``dst = src + conv2(lrelu(conv1(lrelu(src))))`` on split-format maps (the fp32-class
-    form of ``ResblockPairPlan``; HiFi-GAN ResBlock1 step of the 32-channel stage)."""
+def resblock_pair_supported(src: Map1D, dst: Map1D, w1: torch.Tensor, w2: torch.Tensor, dilation: int) -> bool:
+    return w1.shape[0] in (32, 64) and _resblock_pair_fits(src, dst, w1, w2, dilation, resblock_pair_lds_bytes)
+
+
+def resblock_pair_x3_supported(src: Map1D, dst: Map1D, w1: torch.Tensor, w2: torch.Tensor, dilation: int) -> bool:
+    return src.split and dst.split and _resblock_pair_fits(src, dst, w1, w2, dilation, resblock_pair_x3_lds_bytes)      # 32 channels
+
+
+class _ResblockPair:
+    """One fused HiFi-GAN ResBlock1 step, ``dst = src + conv2(lrelu(conv1(lrelu(src))))``, the intermediate map in LDS; ``run`` takes
+    ``GemmPlan.run``'s call shape.  A variant states ``kind``, ``planes`` (tensors are ``planes`` x the map), ``supported``, ``Desc``,
+    ``pack`` (a weight ``[k][C_out][C_in]`` to its fp16 operand) and ``launch``."""
 
     def __init__(self, src: Map1D, dst: Map1D, w1, b1, w2, b2, *, dilation: int, slope: float, device=None):
-        assert resblock_pair_x3_supported(src, dst, w1, w2, dilation)
+        assert self.supported(src, dst, w1, w2, dilation)
         Cn, k = w1.shape[0], w1.shape[2]
-        self.Cn = Cn
-        pack = lambda w: split_planes(w.permute(2, 0, 1)).contiguous()          # [2][k][C_out][C_in]
-        self.w1, self.w2 = pack(w1), pack(w2)
-        self.b1, self.b2 = b1.to(torch.float32).contiguous(), b2.to(torch.float32).contiguous()
-        if device is not None:
-            self.w1, self.w2, self.b1, self.b2 = (t.to(device) for t in (self.w1, self.w2, self.b1, self.b2))
-        d = ResblockX3Desc()
+        self.w1, self.w2 = (_to(device, self.pack(w.permute(2, 0, 1)).contiguous()) for w in (w1, w2))
+        self.b1, self.b2 = (_to(device, b.to(torch.float32).contiguous()) for b in (b1, b2))
+        self.Cn, d = Cn, self.Desc()
         d.M, d.Wg, d.w0, d.w1, d.k, d.dil, d.slope = dst.B * dst.P, dst.P, dst.halo, dst.halo + dst.T, k, dilation, slope
-        d.w_lo = k * Cn * Cn
-        self.desc = d
-        self.flops = 2 * 2.0 * dst.B * dst.T * Cn * Cn * k
-        self.tile = None
+        if self.planes == 2:                                   # pitch of the weight planes; a map's is taken per launch
+            d.w_lo = self.w1.stride(0)
+        self.desc, self.flops = d, 2 * 2.0 * dst.B * dst.T * Cn * Cn * k
 
     def run(self, A0: torch.Tensor, A1=None, *, out_h: torch.Tensor, stream: Optional[int] = None, **_):
         d = self.desc
         for t in (A0, out_h):
-            assert t.dtype == torch.float16 and t.is_cuda and t.shape[0] == 2 and t[0].is_contiguous() and t[0].numel() == d.M * self.Cn
+            plane = t if self.planes == 1 else t[0]                # a plane pair may have any plane pitch
+            assert t.dtype == torch.float16 and t.is_cuda and (self.planes == 1 or t.shape[0] == 2) and plane.is_contiguous() and plane.numel() == d.M * self.Cn
         assert A0.data_ptr() != out_h.data_ptr()
-        d.X, d.out_h, d.x_lo, d.o_lo = A0.data_ptr(), out_h.data_ptr(), A0.stride(0), out_h.stride(0)
-        d.W1, d.W2, d.b1, d.b2 = self.w1.data_ptr(), self.w2.data_ptr(), self.b1.data_ptr(), self.b2.data_ptr()
+        d.X, d.out_h, d.W1, d.W2, d.b1, d.b2 = (t.data_ptr() for t in (A0, out_h, self.w1, self.w2, self.b1, self.b2))
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
+        self.launch(d, A0, out_h, stream)
+
+
+class ResblockPairPlan(_ResblockPair):
+    """``advh_resblock_pair_f16`` (csrc/resblock_pair.hip): fp16 maps and weights, 32 or 64 channels."""
+    kind, planes, supported, Desc = "resblock_pair", 1, staticmethod(resblock_pair_supported), ResblockDesc
+    pack = staticmethod(lambda w: w.to(torch.float16))
+
+    def launch(self, d, A0, out_h, stream):
+        _lib.check(_lib.lib().advh_resblock_pair_f16(C.byref(d), self.Cn, stream), "advh_resblock_pair_f16")
+
+
+class ResblockPairX3Plan(_ResblockPair):
+    """``advh_resblock_pair_x3`` (csrc/resblock_pair_x3.hip): the fp32-class form, split-format maps and weights, 32 channels."""
+    kind, planes, supported, Desc = "resblock_pair_x3", 2, staticmethod(resblock_pair_x3_supported), ResblockX3Desc
+    pack = staticmethod(split_planes)
+
+    def launch(self, d, A0, out_h, stream):
+        d.x_lo, d.o_lo = A0.stride(0), out_h.stride(0)
         _lib.check(_lib.lib().advh_resblock_pair_x3(C.byref(d), self.Cn, stream), "advh_resblock_pair_x3")
 
 

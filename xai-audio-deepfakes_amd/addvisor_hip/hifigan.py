@@ -16,6 +16,7 @@ fused line-tile kernels keep their intermediate in LDS with zero padding, so tha
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -27,34 +28,50 @@ from .synthetic import HifiganConfig
 HALO = 32          # >= the largest "same" padding: (11 - 1) * 5 / 2 = 25
 
 
+# One entry of the decode loop.  ``plan`` / ``src`` by ``kind``: "gemm" the plan and its input map, "halo" the fill mode (1 = the mirrored
+# interior, 0 = zeros) and the map, "mix" the LeakyReLU slope and the maps averaged into ``dst``.
+Step = namedtuple("Step", "kind plan src resid dst dst2", defaults=(None, None, None))
+
+
+def _launch(plan, src, dst, resid=None, dst2=None):
+    return Step("gemm", plan, src, resid, dst, dst2)
+
+
+def _halo(m, mode=1):
+    return Step("halo", mode, m)
+
+
+def _mix(slope, outs, dst):
+    return Step("mix", slope, outs, dst=dst)
+
+
 class HipHifigan:
     def __init__(self, cfg: HifiganConfig, sd: Dict[str, torch.Tensor], device, line_tile: bool = True, fuse: bool = True,
                  padding_mode: str = "zeros", inference_padding: int = 0, precision: Optional[str] = None):
-        """``line_tile``: run the 32- / 64-channel ResBlock convolutions on the weights-in-LDS kernel
-        (``advh_conv_taps_f16``) instead of the implicit GEMM; ``fuse``: whole ResBlock steps in one kernel where both
-        weight tensors fit in LDS (``advh_resblock_pair_f16``).  ``padding_mode`` / ``inference_padding``: see the module
-        docstring.  ``precision``: None = ``ADDVISOR_PRECISION`` (default "f32": the fp32-class mode of the explanation path
-        -- split-format maps, three MFMAs per product; the reference runs the vocoder in fp32, hifigan.py:180) or "f16"
-        (fp16 operands, LDS line-tile kernels; stated tolerance 2e-2 on waveforms)."""
+        """``precision``: None = ``ADDVISOR_PRECISION`` (default "f32": the fp32-class mode of the explanation path -- split-format
+        maps, three MFMAs per product; the reference runs the vocoder in fp32, hifigan.py:180) or "f16" (fp16 operands; stated
+        tolerance 2e-2 on waveforms).  ``padding_mode`` / ``inference_padding``: see the module docstring.
+        "f16": ``line_tile`` runs the 32- / 64-channel ResBlock convolutions on the weights-in-LDS kernel (``advh_conv_taps_f16``) instead
+        of the implicit GEMM; ``fuse`` (needs ``line_tile``) whole ResBlock steps where both weights fit in LDS (``advh_resblock_pair_f16``).
+        "f32": ``line_tile`` is ignored; ``fuse`` gates both the fused step of the 32-channel stage (``advh_resblock_pair_x3``) and the
+        64-channel line tile with streamed weights (``advh_conv_taps_split``); the other layers run the x3 implicit GEMM.
+        "reflect" forces the implicit GEMM everywhere: the tile kernels zero-pad their LDS intermediate."""
         _lib.init()
         precision = precision or default_precision()
         self._ctor = dict(line_tile=line_tile, fuse=fuse, padding_mode=padding_mode, inference_padding=inference_padding)
         if precision not in ("f16", "f32"):
             raise ValueError("precision must be 'f16' or 'f32'")
         self.precision, self.split = precision, precision == "f32"
-        # fp32-class mode: the 32-channel ResBlock steps have a fused split-format kernel (csrc/resblock_pair_x3.hip), the k >= 7 convolutions
-        # of the 64-channel stage a split-format line tile with streamed weights (csrc/conv_taps.hip); the other layers run the x3 implicit GEMM
-        self.fuse_x3 = self.split and fuse and padding_mode == "zeros"
-        if self.split:
-            line_tile = fuse = False
         if padding_mode not in ("zeros", "reflect"):
             raise ValueError("padding_mode must be 'zeros' or 'reflect'")
         if inference_padding < 0:
             raise ValueError("inference_padding must be >= 0")
         self.padding_mode, self.inference_padding = padding_mode, int(inference_padding)
-        if padding_mode == "reflect":
-            line_tile = fuse = False                       # the fused kernels zero-pad their LDS intermediate
-        self.cfg, self.dev, self.line_tile, self.fuse = cfg, device, line_tile, fuse
+        tiles = padding_mode == "zeros"
+        self.lds_tile = tiles and not self.split and line_tile          # fp16 weights-in-LDS convolutions
+        self.lds_fuse = self.lds_tile and fuse                           # fp16 fused ResBlock steps
+        self.split_tile = tiles and self.split and fuse                  # split fused 32-channel steps + 64-channel line tile
+        self.cfg, self.dev = cfg, device
         self.sd = {k: v.detach().float() for k, v in sd.items()}
         ch = cfg.upsample_initial_channel
         for _ in cfg.upsample_rates:
@@ -74,100 +91,77 @@ class HipHifigan:
             return self
         return type(self)(self.cfg, self.sd, self.dev, precision=precision, **self._ctor)
 
+    def _stage_policy(self, co: int) -> Tuple[bool, bool]:
+        """``(in_lds, fused)`` of the stage with ``co`` channels.  ``in_lds``: its ResBlock kernels apply LeakyReLU to the raw map inside
+        their line buffer, so the stage keeps no pre-activated copies (no ``lx`` / ``la`` / ``lb`` maps): an fp16 stage whose every kernel
+        size fits the line tile, a split stage whose EVERY step has the fused kernel.  ``fused``: it uses ``select_resblock_step``."""
+        ks, ds = self.cfg.resblock_kernel_sizes, self.cfg.resblock_dilations
+        if self.split:
+            fused = (self.split_tile and all(G.resblock_pair_x3_lds_bytes(co, k, d) > 0 for k in ks for d in ds)
+                     and HALO >= (max(ks) - 1) * max(ds) // 2)
+            return fused, fused
+        in_lds = self.lds_tile and co in (32, 64) and all(G.taps_tile(co, k, (k - 1) * max(ds)) > 0 for k in ks)
+        return in_lds, in_lds and self.lds_fuse
+
+    def _resblock_step(self, steps, p: str, d: int, policy, cx, clx, tmp, ox, ol):
+        """Append step ``d`` of ResBlock ``p``, ``ox = cx + conv2(lrelu(conv1(lrelu(cx))))``: one fused launch where the stage fuses and the kernel
+        takes the step, else conv1 (``clx`` = lrelu(cx), or ``cx`` if ``in_lds``) -> ``tmp`` and conv2 -> ``ox`` (+ lrelu(ox) -> ``ol``) with their halo fills."""
+        (in_lds, fused), sd = policy, self.sd
+        dil, slope = self.cfg.resblock_dilations[d], self.cfg.leaky_slope
+        w1, b1, w2, b2 = (sd[f"{p}convs{c}.{d}.{n}"] for c in (1, 2) for n in ("weight", "bias"))
+        plan = G.select_resblock_step(cx, ox, w1, b1, w2, b2, dilation=dil, slope=slope, fused=fused, device=self.dev)
+        if plan is not None:
+            steps.append(_launch(plan, cx, ox))
+            return
+        pick = dict(line_tile=self.lds_tile, split_tile=self.split_tile, device=self.dev)
+        reflect, c1_src = self.padding_mode == "reflect", cx if in_lds else clx
+        steps.append(_launch(G.select_conv1d(c1_src, tmp, w1, b1, role="conv1", dilation=dil, act="leaky", slope=slope,
+                                             pre_slope=slope if in_lds else None, **pick), c1_src, tmp))
+        if reflect:
+            steps.append(_halo(tmp))
+        steps.append(_launch(G.select_conv1d(tmp, ox, w2, b2, role="conv2", slope2=slope, **pick), tmp, ox, resid=cx, dst2=ol))
+        if reflect and ol is not None:             # the next conv1 reads lrelu(x) reflect-padded (the raw ox only feeds residuals)
+            steps.append(_halo(ol))
+
     def _workspace(self, B: int, T: int) -> dict:
-        key = (B, T)
-        if key in self._ws:
-            return self._ws[key]
+        if (B, T) in self._ws:
+            return self._ws[B, T]
         cfg, sd, dev = self.cfg, self.sd, self.dev
         M = lambda t, c: G.Map1D(B, t, c, HALO, split=self.split).alloc(dev)
-
-        def conv(src, dst, w, b, **kw):
-            if self.line_tile and G.taps_supported(src, dst, w, kw.get("dilation", 1)):
-                return G.plan_conv1d_taps(src, dst, w, b, device=dev, **kw)
-            if (self.fuse_x3 and kw.get("pre_slope") is None
-                    and G.taps_split_supported(src, dst, w, kw.get("dilation", 1), min_k=3 if kw.get("act") == "leaky" else 7)):
-                return G.plan_conv1d_taps(src, dst, w, b, device=dev, **kw)       # fp32-class line tile with streamed weights (64 channels; first convolutions k >= 3, second ones k >= 7)
-            if kw.pop("pre_slope", None) is not None:
-                raise RuntimeError("a layer of a line-buffer-activated stage does not fit the line-tile kernel")
-            return G.plan_conv1d_same(src, dst, w, b, device=dev, **kw)
-
-        ch = cfg.upsample_initial_channel
-        reflect = self.padding_mode == "reflect"
-        mel = M(T, cfg.in_channels)
-        cur = M(T, ch)                       # lrelu(conv_pre(mel))
-        steps = []
-        if reflect:
-            steps.append(("halo", 1, mel, None, None, None))
-        steps.append(("gemm", G.plan_conv1d_same(mel, cur, sd["conv_pre.weight"], sd["conv_pre.bias"], act="leaky",
-                                                 slope=cfg.leaky_slope, device=dev), mel, None, cur, None))
-        t = T
-        nk, nd = len(cfg.resblock_kernel_sizes), len(cfg.resblock_dilations)
-        nstage = len(cfg.upsample_rates)
+        ch, reflect = cfg.upsample_initial_channel, self.padding_mode == "reflect"
+        mel, cur = M(T, cfg.in_channels), M(T, ch)           # cur: lrelu(conv_pre(mel))
+        steps = [_halo(mel)] if reflect else []
+        steps.append(_launch(G.plan_conv1d_same(mel, cur, sd["conv_pre.weight"], sd["conv_pre.bias"], act="leaky",
+                                                slope=cfg.leaky_slope, device=dev), mel, cur))
+        t, nk, nd, nstage = T, len(cfg.resblock_kernel_sizes), len(cfg.resblock_dilations), len(cfg.upsample_rates)
         for i, r in enumerate(cfg.upsample_rates):
             co, t2 = ch // 2, t * r
-            # stages whose ResBlock convolutions run on the line-tile kernel apply LeakyReLU to the raw map inside the
-            # line buffer: no pre-activated copies are stored or read there
-            in_lds = self.line_tile and co in (32, 64) and all(
-                G.taps_tile(co, k, (k - 1) * max(cfg.resblock_dilations)) > 0 for k in cfg.resblock_kernel_sizes)
-            # fp32-class mode: a stage whose EVERY ResBlock step has the fused split-format kernel needs no pre-activated copies either
-            x3_stage = self.fuse_x3 and all(G.resblock_pair_x3_lds_bytes(co, k, dd) > 0 for k in cfg.resblock_kernel_sizes
-                                            for dd in cfg.resblock_dilations) and HALO >= (max(cfg.resblock_kernel_sizes) - 1) * max(cfg.resblock_dilations) // 2
-            in_lds = in_lds or x3_stage
-            x = M(t2, co)
-            lx = None if in_lds else M(t2, co)
-            steps.append(("gemm", G.plan_convT1d(cur, x, sd[f"ups.{i}.weight"], sd[f"ups.{i}.bias"], stride=r,
-                                                 slope2=cfg.leaky_slope, device=dev), cur, None, x, lx))
+            policy = in_lds, _ = self._stage_policy(co)
+            x, lx = M(t2, co), None if in_lds else M(t2, co)
+            steps.append(_launch(G.plan_convT1d(cur, x, sd[f"ups.{i}.weight"], sd[f"ups.{i}.bias"], stride=r,
+                                                slope2=cfg.leaky_slope, device=dev), cur, x, dst2=lx))
             if reflect:                                    # the ResBlock convolutions read x / lrelu(x) reflect-padded
-                steps.append(("halo", 1, x, None, None, None))
-                steps.append(("halo", 1, lx, None, None, None))
+                steps += [_halo(x), _halo(lx)]
             tmp, pa, pb = M(t2, co), M(t2, co), M(t2, co)
             la, lb = (None, None) if in_lds else (M(t2, co), M(t2, co))
             outs = [M(t2, co) for _ in range(nk)]
             for j in range(nk):
-                p = f"resblocks.{i * nk + j}."
                 cx, clx = x, lx
                 for d in range(nd):
                     last = d == nd - 1
                     ox = outs[j] if last else (pa if d % 2 == 0 else pb)
-                    w1, w2 = sd[p + f"convs1.{d}.weight"], sd[p + f"convs2.{d}.weight"]
-                    if x3_stage:
-                        assert G.resblock_pair_x3_supported(cx, ox, w1, w2, cfg.resblock_dilations[d])
-                        steps.append(("gemm", G.ResblockPairX3Plan(cx, ox, w1, sd[p + f"convs1.{d}.bias"], w2, sd[p + f"convs2.{d}.bias"],
-                                                                  dilation=cfg.resblock_dilations[d], slope=cfg.leaky_slope, device=dev),
-                                      cx, None, ox, None))
-                        cx, clx = ox, None
-                        continue
-                    if in_lds and self.fuse and G.resblock_pair_supported(cx, ox, w1, w2, cfg.resblock_dilations[d]):
-                        # both convolutions of the step in one kernel, the intermediate map stays in LDS
-                        steps.append(("gemm", G.ResblockPairPlan(cx, ox, w1, sd[p + f"convs1.{d}.bias"], w2, sd[p + f"convs2.{d}.bias"],
-                                                                dilation=cfg.resblock_dilations[d], slope=cfg.leaky_slope, device=dev),
-                                      cx, None, ox, None))
-                        cx, clx = ox, None
-                        continue
-                    c1_src = cx if in_lds else clx
-                    steps.append(("gemm", conv(c1_src, tmp, sd[p + f"convs1.{d}.weight"], sd[p + f"convs1.{d}.bias"],
-                                               dilation=cfg.resblock_dilations[d], act="leaky", slope=cfg.leaky_slope,
-                                               **(dict(pre_slope=cfg.leaky_slope) if in_lds else {})),
-                                  c1_src, None, tmp, None))
                     ol = None if (last or in_lds) else (la if d % 2 == 0 else lb)
-                    if reflect:
-                        steps.append(("halo", 1, tmp, None, None, None))
-                    steps.append(("gemm", conv(tmp, ox, sd[p + f"convs2.{d}.weight"], sd[p + f"convs2.{d}.bias"],
-                                               slope2=cfg.leaky_slope), tmp, cx, ox, ol))
-                    if reflect and ol is not None:         # the next conv1 reads lrelu(x) reflect-padded (the raw ox only feeds residuals)
-                        steps.append(("halo", 1, ol, None, None, None))
+                    self._resblock_step(steps, f"resblocks.{i * nk + j}.", d, policy, cx, clx, tmp, ox, ol)
                     cx, clx = ox, ol
             nxt = M(t2, co)
-            slope = cfg.leaky_slope if i < nstage - 1 else 0.01            # F.leaky_relu default before conv_post
-            steps.append(("mix", slope, outs, None, nxt, None))
+            steps.append(_mix(cfg.leaky_slope if i < nstage - 1 else 0.01, outs, nxt))       # F.leaky_relu's default before conv_post
             if reflect:
                 # the mix runs over whole padded maps; the transposed convolution that follows needs a ZERO halo (it is not a
                 # "same" conv), conv_post a reflected one
-                steps.append(("halo", 1 if i == nstage - 1 else 0, nxt, None, None, None))
+                steps.append(_halo(nxt, 1 if i == nstage - 1 else 0))
             cur, ch, t = nxt, co, t2
-        ws = dict(mel=mel, steps=steps, last=cur, T_out=t, wav=torch.empty(B, 1, t, dtype=torch.float32, device=dev))
-        ws["flops"] = sum(s[1].flops for s in steps if s[0] == "gemm") + 2.0 * B * t * ch * cfg.post_kernel
-        self._ws[key] = ws
+        self._ws[B, T] = ws = dict(mel=mel, steps=steps, last=cur, T_out=t, wav=torch.empty(B, 1, t, dtype=torch.float32, device=dev))
+        ws["flops"] = sum(s.plan.flops for s in steps if s.kind == "gemm") + 2.0 * B * t * ch * cfg.post_kernel
         return ws
 
     def flops(self, B: int, T: int) -> float:
@@ -199,13 +193,10 @@ class HipHifigan:
             elif kind == "halo":                       # split maps: both planes are [B][P][C] images of the same geometry
                 _lib.check(lib.advh_halo_fill_f16(src.t.data_ptr(), src.B * (2 if sp else 1), src.T, src.C, src.halo, plan, st), "advh_halo_fill_f16")
             elif sp:
-                a, b, c = src
-                _lib.check(lib.advh_hifigan_mrf_mix_split(a.t.data_ptr(), b.t.data_ptr(), c.t.data_ptr(), dst.t.data_ptr(), plan,
-                                                          dst.t.stride(0), dst.t.stride(0), st), "advh_hifigan_mrf_mix_split")
+                _lib.check(lib.advh_hifigan_mrf_mix_split(*(m.t.data_ptr() for m in src), dst.t.data_ptr(), plan, dst.t.stride(0), dst.t.stride(0), st),
+                           "advh_hifigan_mrf_mix_split")
             else:
-                a, b, c = src
-                _lib.check(lib.advh_hifigan_mrf_mix(a.t.data_ptr(), b.t.data_ptr(), c.t.data_ptr(), dst.t.data_ptr(), plan,
-                                                    dst.t.numel(), st), "advh_hifigan_mrf_mix")
+                _lib.check(lib.advh_hifigan_mrf_mix(*(m.t.data_ptr() for m in src), dst.t.data_ptr(), plan, dst.t.numel(), st), "advh_hifigan_mrf_mix")
         last = ws["last"]
         if sp:
             _lib.check(lib.advh_hifigan_conv_post_split(last.t.data_ptr(), last.t.stride(0), self.post_w.data_ptr(), self.post_b,

@@ -337,7 +337,7 @@ __global__ __launch_bounds__(64 * NW) void conv_taps2d_kernel(const advh_taps2d_
 // 64 x 64 (one per SIMD, nothing to cover LDS time and the per-tap barrier with) it ran level with the GEMM: profiles/r03_conv_taps_x3_experiment.txt.
 template <int NJ, int NW>
 __global__ __launch_bounds__(64 * NW) void conv_taps_x3_kernel(const advh_taps_desc p, long x_lo, long w_lo, long r_lo, long o_lo) {
-    constexpr int C = 64, CH = 8, CT = 4, KS = 2, TT = 16 * NJ * NW, NTH = 64 * NW, WTAP = C * C * 2, WPT = 2 * (C * CH / NTH);   // WPT: DMA instructions per thread and tap     // WTAP: bytes of one plane of one tap
+    constexpr int C = 64, CH = 8, CT = 4, KS = 2, TT = 16 * NJ * NW, NTH = 64 * NW, WTAP = C * C * 2, WPT = 2 * (C * CH / NTH);   // WPT: DMA instructions per thread and tap (2 with eight wavefronts)     // WTAP: bytes of one plane of one tap
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int fr = lane & 15, g = lane >> 4;
@@ -429,8 +429,9 @@ __global__ __launch_bounds__(64 * NW) void conv_taps_x3_kernel(const advh_taps_d
             }
         };
         for (int t = 0; t < p.ntap; ++t, ++n) {
-            // t = 0: the tile's lines, the previous epilogue's stores and taps n, n + 1 must have landed (everything); later: all but the 4 DMA
-            // instructions per thread of the youngest requested tap (n + 2)
+            // t = 0: the tile's lines, the previous epilogue's stores and taps n, n + 1 must have landed (everything); later: all but the WPT DMA
+            // instructions per thread of the youngest requested tap (n + 2) -- a count that holds only if every thread issues the same number
+            static_assert((C * CH) % NTH == 0, "vmcnt(WPT) counts per thread: the chunks of a tap must divide evenly among the threads");
             if (t == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPT) : "memory");
             __syncthreads();                                       // ... everyone's pieces; every wavefront is done with tap n - 1 (its slot is free).
@@ -564,7 +565,7 @@ extern "C" int advh_conv_taps2d_f16(const advh_taps2d_desc* d, int C, advh_strea
     return ADVH_LAUNCH_CHECK();
 }
 
-// column tiles of the split-arithmetic 64-channel kernel: 4 (256 positions per tile) where weights ring + two line buffers fit, else 3
+// positions per tile of the split-arithmetic 64-channel kernel: 256 where the four-slot weight ring + ONE line buffer (two planes each) fit, else 0
 extern "C" int advh_conv_taps_split_tile(int C, int ntap, int span) {
     if (C != 64 || ntap <= 0 || ntap > 16 || span < 0) return 0;
     return taps_x3_lds(span, 4) <= 160 * 1024 ? 256 : 0;
