@@ -441,6 +441,35 @@ int advh_layer_tap(const float* g, const float* act, float inv_scale, int rows, 
 int advh_layer_conductance_accumulate(const float* grad, const float* act, int B, int64_t n, int steps, int ngrad, int first,
                                       float* prev_grad, float* prev_act, float* total, advh_stream_t stream);
 
+/* Neuron attributions (csrc/attribution_neuron.hip): Captum's NeuronGradient, NeuronIntegratedGradients, NeuronGradientShap,
+ * NeuronConductance and NeuronFeatureAblation of one unit, or one band of units, of hidden_states[l], restated (captum is
+ * absent).  The forward stops at the layer (EmbedderGrad.forward(to_layer=l)) and the backward starts there from a seed gradient
+ * (EmbedderGrad.backward(from_layer=l, ...)) and runs the lower chain down to the waveform; these kernels are the two ends.
+ * A selection box is six ints (t0, t1, tstep, h0, h1, hstep) over the [T][H] frame of a clip: the normalised form of Captum's
+ * neuron_selector, a pair of ints or slices -- half-open, steps > 0, an int i is (i, i + 1, 1); the neuron's value is the sum
+ * over the box (Captum aggregates slices by sum).  All rows fp32, contiguous, [R][T][H] with R clip rows.  One thread per
+ * element, every product rounded on its own, the box sum a fixed-shape tree in one workgroup per clip row, no atomics: equal
+ * inputs give equal bits.
+ *
+ * advh_layer_seed : the gradient at hidden_states[l] the lower chain starts from, in place of the autograd seed of
+ *     captum.attr.NeuronGradient (torch.autograd.grad of the selected neuron): resid [R * T][H] fp32, the residual-stream
+ *     gradient, and, if op != NULL, its GEMM-operand copy -- one fp16 plane (split = 0) or the split format's hi plane at op and
+ *     lo plane op_lo elements behind (split = 1; op_lo >= R * T * H), converted as by advh_layer_inject: |x| > 65504 saturates
+ *     and raises the sticky range flag (advh_split_overflow), NaN stays NaN planes and leaves it clear.  Every element of both
+ *     outputs is written, so neither needs clearing first.  Box mode (src == NULL): scale * (row_scale ? row_scale[r] : 1) inside
+ *     the box of clip row r, 0 elsewhere (row_scale [R]: captum.attr.NeuronConductance's layer-gradient entry per path point).
+ *     Dense mode (src [R][T][H] != NULL; box is not read, row_scale must be NULL): scale * src, any vector-Jacobian seed.
+ * advh_neuron_values : out[r] = sum over the box of v[r][t][h], v [R][T][H]: the neuron's activation (the forward_func output
+ *     captum.attr.NeuronFeatureAblation differences, and the s_n of the completeness checks) when v is hidden_states[l], the
+ *     neuron's entry of a layer gradient (captum.attr.NeuronConductance) when v is dF/dh_l.
+ * NaN / inf in the inputs propagate into the results (the caller's finiteness check reports them).  Null pointers (op, row_scale
+ * and src excepted, and box in dense mode), R, T or H <= 0, an empty or out-of-range box or a step <= 0, row_scale given in dense
+ * mode, a non-finite scale, a split flag outside {0, 1} and, in split mode, a plane pitch of 0 or below R * T * H return
+ * ADVH_EINVAL before any HIP call. */
+int advh_layer_seed(const float* src, const float* row_scale, float scale, int R, int T, int H, const int* box, float* resid, void* op,
+                    int split, int64_t op_lo, advh_stream_t stream);
+int advh_neuron_values(const float* v, int R, int T, int H, const int* box, float* out, advh_stream_t stream);
+
 /* Attribution metrics (csrc/attribution_metrics.hip): Captum's infidelity and sensitivity_max of the [B][n] inputs x, restated
  * (captum is absent).  S perturbed samples per clip, processed in chunks of p consecutive samples [s0, s0 + p); a chunk's rows
  * are clip-major, row b * p + s' (Captum's repeat_interleave), and the noise of a row comes from its global counter

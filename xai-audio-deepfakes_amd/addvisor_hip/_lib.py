@@ -75,6 +75,8 @@ SIGNATURES = {
     "advh_layer_inject": (_i, [_p, _i, _i64, _p, _p, _i, _i64, _p]),
     "advh_layer_tap": (_i, [_p, _p, _f, _i, _i64, _p, _p, _p]),
     "advh_layer_conductance_accumulate": (_i, [_p, _p, _i, _i64, _i, _i, _i, _p, _p, _p, _p]),
+    "advh_layer_seed": (_i, [_p, _p, _f, _i, _i, _i, _p, _p, _p, _i, _i64, _p]),
+    "advh_neuron_values": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "advh_metric_rows": (_i, [_p, _i64, _i, _p, _p, _p]),
     "advh_metric_row_dot": (_i, [_p, _p, _i, _i, _i64, _p, _p]),
     "advh_infidelity_fold": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),

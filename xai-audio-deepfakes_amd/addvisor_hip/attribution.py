@@ -24,6 +24,11 @@ builds FeatureAblation's rows with each feature taken from another clip of the b
 counter-based generator through the path-point kernel, the wrapped method attributes them, and the first and second moments are
 folded in fp64 on the device (csrc/attribution_paths.hip).
 
+The layer methods (``captum.attr.Layer*``, ``InternalInfluence``) attribute to ``hidden_states[l]`` on the chain started and
+stopped at a layer (csrc/attribution_layer.hip); the neuron methods (``captum.attr.Neuron*``) attribute one unit, or one band of
+units, of ``hidden_states[l]`` to the waveform on the forward stopped at the layer and the backward started there from a seed
+(csrc/attribution_neuron.hip), reusing the path, draw and ablation helpers above.
+
 ``captum.metrics.infidelity`` / ``sensitivity_max`` score any of them (``infidelity``, ``sensitivity_max``): the perturbed rows
 of each chunk of samples come from the same counter-based generator (or a Python perturb_func), and the per-row dot products,
 norms and per-clip folds run on csrc/attribution_metrics.hip.
@@ -381,6 +386,40 @@ def check_layer_path_args(layer, nl: int, baselines, B: int, L: int, n_steps, me
     if internal_batch_size is not None:
         _positive_int(internal_batch_size, "internal_batch_size")
     return l, base, alphas, steps
+
+
+def _selector_axis(sel, dim: int, what: str) -> Tuple[int, int, int]:
+    if isinstance(sel, slice):
+        for v in (sel.start, sel.stop, sel.step):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError(f"neuron_selector: the {what} slice must have integer bounds and step, not {sel!r}")
+        step = 1 if sel.step is None else int(sel.step)
+        if step <= 0:
+            raise ValueError(f"neuron_selector: the {what} slice needs a step >= 1, not {sel!r}")
+        lo, hi, _ = slice(sel.start, sel.stop, step).indices(dim)          # negative and open bounds as in Python
+        if lo >= hi:
+            raise ValueError(f"neuron_selector: the {what} slice {sel!r} selects nothing of {dim}")
+        return lo, hi, step
+    if isinstance(sel, bool) or not isinstance(sel, (int, np.integer)):
+        raise ValueError(f"neuron_selector: the {what} entry must be an int or a slice, not {sel!r}")
+    i = int(sel) + (dim if sel < 0 else 0)
+    if not 0 <= i < dim:
+        raise ValueError(f"neuron_selector: {what} index {int(sel)} is out of range for {dim}")
+    return i, i + 1, 1
+
+
+def check_neuron_selector(selector, T: int, H: int) -> Tuple[int, int, int, int, int, int]:
+    """``neuron_selector`` of the ``captum.attr.Neuron*`` methods over the ``[T, H]`` frame of ``hidden_states[l]``: a ``(t, h)``
+    tuple of ints or slices.  Negative indices and open or negative slice bounds behave as in Python; a slice is half-open with
+    a step >= 1, and several selected units are aggregated by sum, as Captum does.  Returns the selection box
+    ``(t0, t1, tstep, h0, h1, hstep)`` of advh_layer_seed / advh_neuron_values (an int ``i`` is ``(i, i + 1, 1)``).  A bare int, a
+    wrong arity, a step <= 0, an empty slice and an index out of range raise ValueError; a callable selector raises
+    NotImplementedError."""
+    if callable(selector):
+        raise NotImplementedError("a callable neuron_selector is not supported (HIP build): pass a (t, h) tuple of ints or slices")
+    if not isinstance(selector, (tuple, list)) or len(selector) != 2:
+        raise ValueError(f"neuron_selector must be a (t, h) tuple of ints or slices into the [{T}, {H}] frame, not {selector!r}")
+    return _selector_axis(selector[0], T, "frame") + _selector_axis(selector[1], H, "channel")
 
 
 def frame_index(L: int, T: int, hop: int = 320) -> np.ndarray:
@@ -920,11 +959,22 @@ def philox_normal(seed: int, row0: int, rows: int, n: int, device, raw: bool = F
     return out.view(torch.int32) if raw else out
 
 
+# The seed of the neuron methods at hidden_states[l]: the largest power of two for which the largest gradient-plane magnitude
+# measured over the cases of tests/test_gpu_neuron_attr.py stays at or under 65 504 / 16 (DESIGN, "Neuron attributions").
+NEURON_LOSS_SCALE = 128.0
+
+
 class HipAttribution:
-    def __init__(self, emb: HipEmbedder, loss_scale: float = 4096.0, precision: Optional[str] = None):
+    def __init__(self, emb: HipEmbedder, loss_scale: float = 4096.0, precision: Optional[str] = None,
+                 neuron_loss_scale: float = NEURON_LOSS_SCALE):
         """``precision``: None = the embedder's (an fp32-class embedder gives the fp32-class gradient chain, the reference's
-        fp32 autograd class); "f16" = the fp16-operand chain."""
+        fp32 autograd class); "f16" = the fp16-operand chain.  ``neuron_loss_scale``: the power of two the neuron methods seed
+        ``hidden_states[l]`` with (a unit seed there is far larger than the logit's ``coef / T``; DESIGN)."""
+        v = neuron_loss_scale
+        if not (isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0 and math.isfinite(v) and math.frexp(v)[0] == 0.5):
+            raise ValueError(f"neuron_loss_scale must be a positive power of two, not {v!r}")
         self.emb, self.eg, self.loss_scale = emb, EmbedderGrad(emb, precision), loss_scale
+        self.neuron_loss_scale = float(neuron_loss_scale)
         self.precision = self.eg.precision
 
     def _prep(self, waves: torch.Tensor) -> torch.Tensor:
@@ -1682,6 +1732,158 @@ class HipAttribution:
         rel = torch.empty(B * T, dtype=torch.float32, device=attr.device)
         self.eg.layer_tap(attr.view(B * T, H), 1.0, want_out=False, row_sum=rel)
         return self.frames_to_wave(rel.view(B, T), L)
+
+    # ------------------------------------------------------------------ neuron attributions (captum.attr.Neuron*)
+    def _neuron_args(self, waves, layer, neuron):
+        """``(B, L, layer, box)`` before any GPU work: ``check_layer`` and ``check_neuron_selector`` against the frame count of
+        an ``L``-sample clip."""
+        B, L = _dims(waves)
+        emb = self.eg.emb
+        l = check_layer(layer, emb.nl)
+        return B, L, l, check_neuron_selector(neuron, emb._lengths(L)[-1], emb.cfg.hidden_size)
+
+    def _checked_neuron(self, out, what: str = "neuron attribution"):
+        return self._checked(out, what, f"the gradient chain overflowed at neuron_loss_scale={self.neuron_loss_scale:g} (lower "
+                             "HipAttribution.neuron_loss_scale by a power of two), or a path point has no scale (a constant clip)")
+
+    def neuron_gradient(self, waves, layer: int, neuron):
+        """Captum's NeuronGradient: ``d s_n / d x`` ``[B, L]`` fp32, ``s_n(x)`` the sum over the selection ``neuron`` (a
+        ``(t, h)`` tuple of ints or slices, ``check_neuron_selector``) of ``hidden_states[layer](x)``: one forward stopped at
+        the layer, one backward started there from the selection's indicator."""
+        _, _, l, box = self._neuron_args(waves, layer, neuron)
+        x = self._prep(waves)
+        self.eg.forward(x, to_layer=l)
+        return self._checked_neuron(self.eg.backward(self.neuron_loss_scale, from_layer=l, neuron=box))
+
+    def _neuron_path(self, x, base, alphas, steps, n_steps, internal_batch_size, multiply_by_inputs, point_gradient):
+        """The path loop of ``integrated_gradients`` with ``point_gradient(pts) -> [rows, L]`` in the place of the logit's
+        gradient: whole steps per chunk, step-major rows, zero-weight padding steps."""
+        B, L = x.shape
+        per = self._layer_chunks(B, n_steps, internal_batch_size)
+        npad = -(-n_steps // per) * per
+        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
+        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
+        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
+        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
+        d = _desc(x, base, None, npad, 0)
+        total = torch.zeros_like(x)
+        pts = torch.empty((per * B, L), dtype=torch.float32, device=x.device)
+        for s0 in range(0, npad, per):
+            _points(d, a_all, s0 * B, per * B, pts)
+            _accumulate(d, point_gradient(pts), w_all, ACC_IG, s0 * B, per * B, total)
+        out = torch.empty_like(x)
+        if multiply_by_inputs:
+            _accumulate(d, total, None, FIN_IG, 0, B, out)
+        else:
+            d.S = 1                                                             # FIN_MEAN with S = 1: the sum itself
+            _accumulate(d, total, None, FIN_MEAN, 0, B, out)
+        return self._checked_neuron(out)
+
+    def _neuron_path_args(self, waves, layer, neuron, baselines, n_steps, method, internal_batch_size):
+        B, L, l, box = self._neuron_args(waves, layer, neuron)
+        base = check_ig_baselines(baselines, B, L)
+        alphas, steps = approximation(method, check_steps(n_steps, method))
+        if internal_batch_size is not None:
+            _positive_int(internal_batch_size, "internal_batch_size")
+        return l, box, base, alphas, steps
+
+    def neuron_integrated_gradients(self, waves, layer: int, neuron, baselines=None, n_steps: int = 50, method: str = "gausslegendre",
+                                    internal_batch_size: Optional[int] = None, multiply_by_inputs: bool = True):
+        """Captum's NeuronIntegratedGradients: ``integrated_gradients`` with ``s_n`` (``neuron_gradient``) in the place of the
+        logit -- every path point runs the chain below the layer only, forward and backward.  ``[B, L]``; no convergence delta
+        (Captum's class has none)."""
+        l, box, base, alphas, steps = self._neuron_path_args(waves, layer, neuron, baselines, n_steps, method, internal_batch_size)
+        x = self._prep(waves)
+        eg, scale = self.eg, self.neuron_loss_scale
+
+        def point_gradient(pts):
+            eg.forward(pts, to_layer=l)
+            return eg.backward(scale, from_layer=l, neuron=box)
+        return self._neuron_path(x, base.to(x.device, torch.float32).contiguous(), alphas, steps, n_steps, internal_batch_size,
+                                 multiply_by_inputs, point_gradient)
+
+    def neuron_conductance(self, waves, layer: int, neuron, baselines=None, n_steps: int = 50, method: str = "gausslegendre",
+                           internal_batch_size: Optional[int] = None, multiply_by_inputs: bool = True):
+        """Captum's NeuronConductance of a single neuron ``h_n`` (``neuron``: two ints; a slice raises ValueError -- Captum's
+        aggregate multiplies a summed layer gradient into a summed neuron gradient, which is not restated): over the ``n_steps``
+        waveform-space points ``x_k`` of the rule, ``attr = (x - b) * sum_k w_k m_k (d h_n / d x)(x_k)`` with
+        ``m_k = dF/dh_n(x_k)`` (the sum alone with ``multiply_by_inputs=False``).  Per chunk: a full forward, the backward
+        stopped at the layer, advh_neuron_values on that gradient, then the backward from the layer seeded with ``m``."""
+        l, box, base, alphas, steps = self._neuron_path_args(waves, layer, neuron, baselines, n_steps, method, internal_batch_size)
+        if any(isinstance(s, slice) for s in neuron):
+            raise ValueError("neuron_conductance takes a single neuron (two ints): Captum's aggregate over a slice is ambiguous")
+        x = self._prep(waves)
+        eg = self.eg
+
+        def point_gradient(pts):
+            eg.forward(pts)
+            m = eg.neuron_values(eg.backward(self.loss_scale, to_layer=l), box)        # dF/dh_n of every row
+            return eg.backward(self.neuron_loss_scale, from_layer=l, neuron=box, row_scale=m)
+        return self._neuron_path(x, base.to(x.device, torch.float32).contiguous(), alphas, steps, n_steps, internal_batch_size,
+                                 multiply_by_inputs, point_gradient)
+
+    def neuron_gradient_shap(self, waves, layer: int, neuron, baselines, n_samples: int = 5, stdevs: float = 0.0,
+                             multiply_by_inputs: bool = True, seed: Optional[int] = None, internal_batch_size: Optional[int] = None):
+        """Captum's NeuronGradientShap: ``gradient_shap`` with ``s_n`` in the place of the logit, on the same draws
+        (``shap_draws(seed, ...)``, ``philox_normal(seed, ...)``).  ``[B, L]``."""
+        B, L, l, box = self._neuron_args(waves, layer, neuron)
+        if callable(baselines) and not torch.is_tensor(baselines):
+            baselines = baselines(waves) if inspect.signature(baselines).parameters else baselines()
+        base = check_shap_args(baselines, B, L, n_samples, stdevs)
+        if internal_batch_size is not None:
+            _positive_int(internal_batch_size, "internal_batch_size")
+        seed = draw_seed() if seed is None else int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2**64)")
+        S = int(n_samples)
+        idx, alpha = shap_draws(seed, B, S, base.shape[0])
+        x = self._prep(waves)
+        dev = x.device
+        base = base.to(dev, torch.float32).contiguous()
+        bidx = torch.from_numpy(idx).to(dev)
+        a_all = torch.from_numpy(alpha).to(dev)
+        R = B * S
+        chunk = min(internal_batch_size or 128, R)
+        d = _desc(x, base, bidx, S, 1, float(stdevs), seed)
+        total = torch.zeros_like(x)
+        # one workspace shape: a short last chunk leaves the previous chunk's (finite) points in the rows it does not use
+        pts = torch.zeros((chunk, L), dtype=torch.float32, device=dev)
+        mode = ACC_SHAP if multiply_by_inputs else ACC_SHAP_GRAD
+        for row0 in range(0, R, chunk):
+            rows = min(chunk, R - row0)
+            _points(d, a_all, row0, rows, pts)
+            self.eg.forward(pts, to_layer=l)
+            g = self.eg.backward(self.neuron_loss_scale, from_layer=l, neuron=box)      # [chunk, L], clip-major
+            _accumulate(d, g, None, mode, row0, rows, total)
+        out = torch.empty_like(x)
+        _accumulate(d, total, None, FIN_MEAN, 0, B, out)
+        return self._checked_neuron(out)
+
+    def neuron_feature_ablation(self, waves, layer: int, neuron, baselines=None, feature_mask=None,
+                                internal_batch_size: Optional[int] = None):
+        """Captum's NeuronFeatureAblation: ``feature_ablation`` with ``s_n`` in the place of the logit --
+        ``attr[b, t] = s_n(x)[b] - s_n(ablated)[k(b, t), b]``; the ablated rows run through the forward stopped at the layer and
+        advh_neuron_values."""
+        B, L, l, box = self._neuron_args(waves, layer, neuron)
+        base = check_ig_baselines(baselines, B, L)
+        index, K = feature_indices(feature_mask, B, L)
+        chunk = min(check_internal_batch(internal_batch_size), K * B)
+        x = self._prep(waves)
+        eg = self.eg
+        base = base.to(x.device, torch.float32).contiguous()
+        index = index.to(x.device).contiguous()
+        d = ablation_desc(x, base, ABL_FEATURE, K, mask=index)
+        value = lambda rows: eg.neuron_values(eg.forward(rows, to_layer=l), box)
+        pts = torch.empty((chunk, L), dtype=torch.float32, device=x.device)
+        nchunk = -(-K * B // chunk)
+        fk = torch.empty(nchunk * chunk, dtype=torch.float32, device=x.device)     # whole chunks: the last one padded with copies of x
+        for c in range(nchunk):
+            ablation_points(d, c * chunk, chunk, pts)
+            fk[c * chunk:(c + 1) * chunk] = value(pts)
+        attr = torch.empty_like(x)
+        ablation_accumulate(d, value(x), fk, attr)
+        return self._checked(attr, "neuron feature ablation",
+                             "the neuron's activation of the clips or of their ablations is not finite (check the inputs and baselines)")
 
     def _ig_zero(self, waves, n_steps: int, internal_batch_size: Optional[int]):
         x = self._prep(waves)

@@ -20,6 +20,7 @@ the residual-stream gradient is fp32.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -62,6 +63,19 @@ def check_layer(layer, nl: int) -> int:
     return int(layer)
 
 
+def check_box(box, T: int, H: int) -> Tuple[int, int, int, int, int, int]:
+    """A selection box ``(t0, t1, tstep, h0, h1, hstep)`` over the ``[T, H]`` frame of a layer (the normalised neuron selector
+    of the ``captum.attr.Neuron*`` methods, ``attribution.check_neuron_selector``): six ints, half-open ranges inside the frame,
+    non-empty, steps > 0.  Raises ValueError."""
+    ok = isinstance(box, (tuple, list)) and len(box) == 6 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in box)
+    if ok:
+        t0, t1, ts, h0, h1, hs = (int(v) for v in box)
+        ok = 0 <= t0 < t1 <= T and ts > 0 and 0 <= h0 < h1 <= H and hs > 0
+    if not ok:
+        raise ValueError(f"a selection box is (t0, t1, tstep, h0, h1, hstep) inside [0, {T}) x [0, {H}), non-empty, steps > 0; got {box!r}")
+    return t0, t1, ts, h0, h1, hs
+
+
 class EmbedderGrad:
     def __init__(self, emb: HipEmbedder, precision: Optional[str] = None):
         """``precision``: None = the embedder's own ("f32": split-format chain; "f16": fp16 chain), or "f16" to run the fp16
@@ -80,6 +94,7 @@ class EmbedderGrad:
         self.stable = self.cfg.do_stable_layer_norm            # pre-LN encoder
         self._ws: Dict[Tuple[int, int], dict] = {}
         self._wcache: dict = {}
+        self._stop: Optional[int] = None                       # forward(to_layer=l): the layer the last pass stopped at
 
     # ------------------------------------------------------------------ buffers and plans
     def _workspace(self, B: int, L: int) -> dict:
@@ -176,7 +191,13 @@ class EmbedderGrad:
         return w
 
     # ------------------------------------------------------------------ forward with saves
-    def forward(self, wave: torch.Tensor, length: Optional[int] = None):
+    def forward(self, wave: torch.Tensor, length: Optional[int] = None, to_layer: Optional[int] = None):
+        """The classifier with the backward's saves: ``(logits [B,1], probs [B,1])``.  ``to_layer=l`` (the neuron methods,
+        ``captum.attr.Neuron*``): the pass stops at ``hidden_states[l]`` -- the front end and layers ``0 .. l-1`` run with their
+        saves, and for ``l == nl`` of a full-depth pre-LN model the final LayerNorm, whose output ``hidden_states[nl]`` is; no
+        layer ``>= l``, no pooling and no logreg is launched -- and returns it, ``[B, T, H]`` fp32.  After such a pass only
+        ``hidden(l' <= l)`` and ``backward(from_layer <= l, ...)`` are defined."""
+        stop = None if to_layer is None else check_layer(to_layer, self.emb.nl)
         emb, cfg, lib, sp = self.emb, self.cfg, _lib.lib(), self.split
         wave = wave.contiguous()
         B, n_in = wave.shape
@@ -228,20 +249,24 @@ class EmbedderGrad:
             f["pos"].run(f["xg"], out_f=w["h1"], resid=h, out_pre=w["pc"])
             emb.enc_ln(w["h1"], M, eps, out_f=w["x"][0], out_h=h16, split=sp)
         self._start = None
-        self._encoder_tail(w, 0, B)
+        self._stop = stop
+        self._encoder_tail(w, 0, B, stop)
         self._last = (wave, B, n_in, L)
+        if stop is not None:
+            return self._hidden_buf(w, stop).view(B, T, H).clone()
         return f["logit"].clone().view(B, 1), f["prob"].clone().view(B, 1)
 
-    def _encoder_tail(self, w: dict, start: int, B: int) -> None:
+    def _encoder_tail(self, w: dict, start: int, B: int, stop: Optional[int] = None) -> None:
         """Layers ``start .. nl-1`` on the rows of ``w["x"][start]`` (post-LN: and their operand copy in ``h16``), the final
-        LayerNorm where the model has one, and the pooling + logreg, with the saves of the backward."""
+        LayerNorm where the model has one, and the pooling + logreg, with the saves of the backward.  ``stop=l``: layers
+        ``start .. l-1`` alone, and the final LayerNorm only when ``l == nl`` (it produces ``hidden_states[nl]``); no pooling."""
         emb, cfg, lib, sp = self.emb, self.cfg, _lib.lib(), self.split
         f = w["f"]
         st = torch.cuda.current_stream().cuda_stream
         T, M, H = f["T"], f["M"], cfg.hidden_size
         eps, nl = cfg.layer_norm_eps, emb.nl
         h16 = f["h16"]
-        for l in range(start, nl):
+        for l in range(start, nl if stop is None else stop):
             lay = f["layers"][l]
             if self.stable:
                 emb.ln1[l](w["x"][l], M, eps, out_h=h16, split=sp)
@@ -265,9 +290,13 @@ class EmbedderGrad:
                 emb.ln2[l](w["s2"][l], M, eps, out_f=w["x"][l + 1], out_h=h16, split=sp)
         final = w["x"][nl]
         self._final_ln = self.stable and nl == cfg.num_hidden_layers
+        if stop is not None and stop < nl:
+            return
         if self._final_ln:
             emb.enc_ln(w["x"][nl], M, eps, out_f=w["xf"], split=sp)
             final = w["xf"]
+        if stop is not None:
+            return
         _lib.check(lib.advh_pool_logreg(final.data_ptr(), emb.coef.data_ptr(), emb.intercept, f["logit"].data_ptr(),
                                         f["prob"].data_ptr(), None, B, T, H, st), "advh_pool_logreg")
 
@@ -283,6 +312,8 @@ class EmbedderGrad:
             raise RuntimeError("hidden() needs a forward pass first")
         if self._start is not None and l < self._start:
             raise ValueError(f"the last pass started at layer {self._start}: hidden_states[{l}] was not computed")
+        if self._stop is not None and l > self._stop:
+            raise ValueError(f"the last pass stopped at layer {self._stop}: hidden_states[{l}] was not computed")
         _, B, _, L = self._last
         w = self._workspace(B, L)
         return self._hidden_buf(w, l).view(B, w["f"]["T"], self.cfg.hidden_size).clone()
@@ -314,6 +345,7 @@ class EmbedderGrad:
             hidden.data_ptr(), M, H, self._hidden_buf(w, l).data_ptr(), None if op is None else op.data_ptr(), int(self.split),
             op.stride(0) if (op is not None and self.split) else 0, torch.cuda.current_stream().cuda_stream), "advh_layer_inject")
         self._start = l
+        self._stop = None
         st = torch.cuda.current_stream().cuda_stream
         if l == nl:
             _lib.check(_lib.lib().advh_pool_logreg(self._hidden_buf(w, l).data_ptr(), self.emb.coef.data_ptr(), self.emb.intercept,
@@ -359,14 +391,65 @@ class EmbedderGrad:
             _lib.check(lib.advh_attention_bwd_f16(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), B, T, H, heads, st),
                        "advh_attention_bwd_f16")
 
-    def backward(self, loss_scale: float = 4096.0, seed: Optional[torch.Tensor] = None, to_layer: Optional[int] = None) -> torch.Tensor:
+    def neuron_values(self, v: torch.Tensor, box) -> torch.Tensor:
+        """advh_neuron_values: ``out[r]`` = the sum over the selection box of the contiguous fp32 rows ``v [R, T, H]``."""
+        R, T, H = v.shape
+        b = (ctypes.c_int * 6)(*check_box(box, T, H))
+        out = torch.empty(R, dtype=torch.float32, device=v.device)
+        _lib.check(_lib.lib().advh_neuron_values(v.data_ptr(), R, T, H, b, out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                   "advh_neuron_values")
+        return out
+
+    def _seed_args(self, B, T, H, seed, to_layer, from_layer, neuron, layer_seed, row_scale):
+        """The arguments of ``backward(from_layer=l, ...)``, before any launch: ``(l, box | None)``."""
+        if from_layer is None:
+            if neuron is not None or layer_seed is not None or row_scale is not None:
+                raise ValueError("neuron, layer_seed and row_scale belong to backward(from_layer=l, ...)")
+            return None, None
+        l = check_layer(from_layer, self.emb.nl)
+        if seed is not None or to_layer is not None:
+            raise ValueError("backward(from_layer=l, ...) runs the chain below the layer: it takes neither seed nor to_layer")
+        if (neuron is None) == (layer_seed is None):
+            raise ValueError("backward(from_layer=l, ...) needs exactly one of neuron (a selection box) and layer_seed ([R, T, H])")
+        if self._start is not None:
+            raise RuntimeError(f"the last pass started at layer {self._start} (forward_from): the lower chain has no saves of it")
+        if self._stop is not None and l > self._stop:
+            raise ValueError(f"the last pass stopped at layer {self._stop}: a backward from layer {l} needs a pass up to there")
+        dev_f32 = lambda t: torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
+        if neuron is None:
+            if row_scale is not None:
+                raise ValueError("row_scale scales a neuron's seed; fold it into layer_seed")
+            if not dev_f32(layer_seed) or tuple(layer_seed.shape) != (B, T, H):
+                raise ValueError(f"layer_seed must be a CUDA fp32 tensor [{B}, {T}, {H}] (the rows of the last forward)")
+            return l, None
+        if row_scale is not None and (not dev_f32(row_scale) or tuple(row_scale.shape) != (B,)):
+            raise ValueError(f"row_scale must be a CUDA fp32 tensor [{B}]")
+        return l, check_box(neuron, T, H)
+
+    def backward(self, loss_scale: float = 4096.0, seed: Optional[torch.Tensor] = None, to_layer: Optional[int] = None,
+                 from_layer: Optional[int] = None, neuron=None, layer_seed: Optional[torch.Tensor] = None,
+                 row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
         """d logit / d wave for the clips of the last ``forward`` call: ``[B, n_in]`` fp32.  With ``seed [B]``
         (dL/d logit per clip) the result is dL/d wave instead (vector-Jacobian product: LMACLoss backward).
         ``to_layer=l``: the chain stops once ``d logit / d hidden_states[l]`` is in the residual-stream buffer and returns it,
         ``[B, T, H]`` fp32 (divided by ``loss_scale``, advh_layer_tap); the layers below, the positional convolution, the feature
         encoder and the waveform kernels are not launched.  It works after ``forward`` and after ``forward_from(l', .)`` with
         ``l' <= l``; ``hidden_states[nl]`` of a full-depth pre-LN model is the final LayerNorm's output, so ``to_layer=nl`` is the
-        pooling's backward alone there."""
+        pooling's backward alone there.
+        ``from_layer=l`` (the neuron methods, ``captum.attr.Neuron*``): the chain starts at ``hidden_states[l]`` from a seed
+        gradient instead of the logit -- ``neuron=box``: ``loss_scale (* row_scale[r])`` inside the selection box
+        (``check_box``) of every clip row and 0 elsewhere; ``layer_seed [B, T, H]``: ``loss_scale * layer_seed``
+        (advh_layer_seed) -- and runs layers ``l-1 .. 0`` and the lower chain: ``[B, n_in]`` fp32, the vector-Jacobian product
+        ``seed . d hidden_states[l] / d wave`` (divided by ``loss_scale``).  Nothing above the layer is launched.  It works after
+        ``forward(...)`` with ``to_layer`` None or ``>= l``, also after a ``backward(to_layer=...)`` of the same pass (the saves
+        are read-only); at ``l == nl`` of a full-depth pre-LN model the seed passes through the final LayerNorm's backward."""
+        if getattr(self, "_last", None) is None:
+            raise RuntimeError("backward() needs a forward pass first")
+        _w = self._workspace(self._last[1], self._last[3])["f"]
+        top, box = self._seed_args(self._last[1], _w["T"], self.cfg.hidden_size, seed, to_layer, from_layer, neuron, layer_seed, row_scale)
+        if from_layer is None and self._stop is not None:
+            raise RuntimeError(f"the last pass stopped at layer {self._stop} (forward(to_layer=...)): only backward(from_layer <= "
+                               f"{self._stop}, ...) is defined")
         stop = 0 if to_layer is None else check_layer(to_layer, self.emb.nl)
         if to_layer is None and self._start is not None:
             raise RuntimeError(f"the last pass started at layer {self._start} (forward_from): only backward(to_layer >= "
@@ -382,20 +465,30 @@ class EmbedderGrad:
         C, nfe, nl = cfg.conv_dim, len(f["Ls"]), emb.nl
         da, db, d16, t16 = w["da"], w["db"], w["d16"], w["t16"]
         heads = cfg.num_attention_heads
-        if seed is None:
-            w["dlogit"].fill_(loss_scale)
+        if top is not None:                                # da / d16 = the seed at hidden_states[top]: every element written
+            p = lambda t: None if t is None else t.data_ptr()
+            src = None if layer_seed is None else layer_seed.contiguous()
+            rs = None if row_scale is None else row_scale.contiguous()
+            _lib.check(lib.advh_layer_seed(
+                p(src), p(rs), loss_scale, B, T, H,
+                None if box is None else (ctypes.c_int * 6)(*box), da.data_ptr(), d16.data_ptr(), int(sp), d16.stride(0) if sp else 0, st),
+                "advh_layer_seed")
         else:
-            w["dlogit"].copy_(seed.reshape(-1).to(w["dlogit"].dtype) * loss_scale)
-        if sp:
-            _lib.check(lib.advh_pool_logreg_bwd_split(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(),
-                                                      d16.stride(0), B, T, H, st), "advh_pool_logreg_bwd_split")
-        else:
-            _lib.check(lib.advh_pool_logreg_bwd(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(), B, T, H, st),
-                       "advh_pool_logreg_bwd")
-        if self._final_ln and stop < nl:
+            top = nl
+            if seed is None:
+                w["dlogit"].fill_(loss_scale)
+            else:
+                w["dlogit"].copy_(seed.reshape(-1).to(w["dlogit"].dtype) * loss_scale)
+            if sp:
+                _lib.check(lib.advh_pool_logreg_bwd_split(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(),
+                                                          d16.stride(0), B, T, H, st), "advh_pool_logreg_bwd_split")
+            else:
+                _lib.check(lib.advh_pool_logreg_bwd(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(), B, T, H, st),
+                           "advh_pool_logreg_bwd")
+        if self._final_ln and stop < nl and top == nl:
             self._ln_bwd(emb.enc_ln, w["x"][nl], da, M, out_f=db, out_h=d16)
             da, db = db, da
-        for l in range(nl - 1, stop - 1, -1):
+        for l in range(top - 1, stop - 1, -1):
             bl = w["layers"][l]
             if self.stable:                                # da = d x_{l+1} (fp32), d16 its fp16 copy
                 bl["ff2"].run(d16, out_h=w["dI"], dact_src=w["g1"][l])

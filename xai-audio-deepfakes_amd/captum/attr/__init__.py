@@ -5,7 +5,10 @@ forward with the ablated, permuted or coalition batches built on the device; Noi
 VarGrad) around any of those eleven, with the noisy rows and the moments on the device; and the layer methods (LayerActivation,
 LayerGradientXActivation, LayerIntegratedGradients, LayerConductance, InternalInfluence) at ``hidden_states[layer]`` of the
 encoder, on the HIP chain started and stopped at that layer (csrc/attribution_layer.hip).  They return ``[B, T, H]`` maps;
-NoiseTunnel does not wrap them.
+NoiseTunnel does not wrap them.  The neuron methods (NeuronGradient, NeuronIntegratedGradients, NeuronGradientShap,
+NeuronConductance, NeuronFeatureAblation) attribute one unit, or one band of units, of ``hidden_states[layer]`` to the waveform
+(``[B, L]``), on the forward stopped at the layer and the backward started there (csrc/attribution_neuron.hip); NoiseTunnel
+does not wrap them either.
 
 ``Method(model).attribute(inputs, target=None, ...)`` expects ``model`` to be a
 ``captum_saliency.Wav2vec2LogReg`` (or anything exposing ``.hip_attribution()``): the waveform -> logit
@@ -326,6 +329,107 @@ class InternalInfluence(_LayerMethod):
         _layer_path_checks(self, inputs, target, attribute_to_layer_input, baselines, n_steps, method, internal_batch_size)
         return _engine(self.model).internal_influence(inputs, self.layer, baselines=baselines, n_steps=n_steps, method=method,
                                                       internal_batch_size=internal_batch_size)
+
+
+def _neuron_checks(method_obj, inputs, target, neuron_selector, attribute_to_neuron_input):
+    """The checks every neuron method shares, before the engine is touched: those of ``_layer_checks``; the neuron's output only
+    (``attribute_to_neuron_input=True`` raises NotImplementedError); ``check_neuron_selector`` against the model's frame shape
+    (ValueError; NotImplementedError for a callable)."""
+    model = method_obj.model
+    _layer_checks(model, inputs, target, method_obj.layer, False)
+    if attribute_to_neuron_input:
+        raise NotImplementedError("the neuron methods (HIP build) attribute a neuron's output, an entry of hidden_states[layer]; "
+                                  "attribute_to_neuron_input=True is not supported")
+    if hasattr(model, "frame_shape"):
+        _A.check_neuron_selector(neuron_selector, *model.frame_shape(inputs.shape[1]))
+    elif callable(neuron_selector):
+        raise NotImplementedError("a callable neuron_selector is not supported (HIP build)")
+    elif not isinstance(neuron_selector, (tuple, list)) or len(neuron_selector) != 2:
+        raise ValueError(f"neuron_selector must be a (t, h) tuple of ints or slices, not {neuron_selector!r}")
+
+
+class _NeuronMethod(_LayerMethod):
+    """``Method(forward_func, layer)`` with ``attribute(inputs, neuron_selector, ...)``: ``layer`` as for the layer methods,
+    ``neuron_selector`` a ``(t, h)`` tuple of ints or slices into the ``[T, H]`` frame of ``hidden_states[layer]`` (several
+    units are summed, as Captum does; a callable raises NotImplementedError).  Attributions are ``[B, L]``."""
+
+    def __init__(self, forward_func, layer, device_ids=None, multiply_by_inputs=True):
+        super().__init__(forward_func, layer)
+        self.multiply_by_inputs = multiply_by_inputs
+
+    def _path_checks(self, inputs, target, neuron_selector, attribute_to_neuron_input, baselines, n_steps, method, internal_batch_size):
+        _neuron_checks(self, inputs, target, neuron_selector, attribute_to_neuron_input)
+        B, L = inputs.shape
+        _A.check_ig_baselines(baselines, B, L)
+        _A.approximation(method, _A.check_steps(n_steps, method))
+        if internal_batch_size is not None:
+            _A._positive_int(internal_batch_size, "internal_batch_size")
+
+
+class NeuronGradient(_NeuronMethod):
+    """Captum's NeuronGradient: the gradient of the selected neuron with respect to the waveform."""
+
+    def __init__(self, forward_func, layer, device_ids=None):
+        super().__init__(forward_func, layer)
+
+    def attribute(self, inputs, neuron_selector, additional_forward_args=None, attribute_to_neuron_input=False):
+        _neuron_checks(self, inputs, None, neuron_selector, attribute_to_neuron_input)
+        return _engine(self.model).neuron_gradient(inputs, self.layer, neuron_selector)
+
+
+class NeuronIntegratedGradients(_NeuronMethod):
+    """Captum's NeuronIntegratedGradients: integrated gradients of the selected neuron along the waveform-space path from
+    ``baselines`` (None, a number, ``[1, L]`` or ``[B, L]``) to the input.  It has no convergence delta."""
+
+    def attribute(self, inputs, neuron_selector, baselines=None, target=None, additional_forward_args=None, n_steps=50,
+                  method="gausslegendre", internal_batch_size=None, attribute_to_neuron_input=False):
+        self._path_checks(inputs, target, neuron_selector, attribute_to_neuron_input, baselines, n_steps, method, internal_batch_size)
+        return _engine(self.model).neuron_integrated_gradients(
+            inputs, self.layer, neuron_selector, baselines=baselines, n_steps=n_steps, method=method,
+            internal_batch_size=internal_batch_size, multiply_by_inputs=self.multiply_by_inputs)
+
+
+class NeuronGradientShap(_NeuronMethod):
+    """Captum's NeuronGradientShap: GradientShap of the selected neuron (``baselines [N_b, L]`` or a callable returning it;
+    draws as GradientShap)."""
+
+    def attribute(self, inputs, neuron_selector, baselines, n_samples=5, stdevs=0.0, additional_forward_args=None,
+                  attribute_to_neuron_input=False):
+        _neuron_checks(self, inputs, None, neuron_selector, attribute_to_neuron_input)
+        return _engine(self.model).neuron_gradient_shap(inputs, self.layer, neuron_selector, baselines, n_samples=n_samples,
+                                                        stdevs=stdevs, multiply_by_inputs=self.multiply_by_inputs)
+
+
+class NeuronConductance(_NeuronMethod):
+    """Captum's NeuronConductance: the conductance of a single neuron (``neuron_selector``: two ints; a slice raises ValueError)
+    along the waveform-space path, ``(x - b) * sum_k w_k dF/dh_n(x_k) dh_n/dx(x_k)``.  ``method`` defaults to Captum's
+    ``riemann_trapezoid`` here."""
+
+    def attribute(self, inputs, neuron_selector, baselines=None, target=None, additional_forward_args=None, n_steps=50,
+                  method="riemann_trapezoid", internal_batch_size=None, attribute_to_neuron_input=False):
+        self._path_checks(inputs, target, neuron_selector, attribute_to_neuron_input, baselines, n_steps, method, internal_batch_size)
+        if any(isinstance(s, slice) for s in neuron_selector):
+            raise ValueError("NeuronConductance (HIP build) takes a single neuron: two ints, not slices")
+        return _engine(self.model).neuron_conductance(
+            inputs, self.layer, neuron_selector, baselines=baselines, n_steps=n_steps, method=method,
+            internal_batch_size=internal_batch_size, multiply_by_inputs=self.multiply_by_inputs)
+
+
+class NeuronFeatureAblation(_NeuronMethod):
+    """Captum's NeuronFeatureAblation: FeatureAblation with the selected neuron's activation in the place of the logit."""
+
+    def __init__(self, forward_func, layer, device_ids=None):
+        super().__init__(forward_func, layer)
+
+    def attribute(self, inputs, neuron_selector, baselines=None, additional_forward_args=None, feature_mask=None,
+                  attribute_to_neuron_input=False, perturbations_per_eval=1):
+        ibs = _perturbation_batch(inputs, None, perturbations_per_eval)
+        _neuron_checks(self, inputs, None, neuron_selector, attribute_to_neuron_input)
+        B, L = inputs.shape
+        _A.check_ig_baselines(baselines, B, L)
+        _A.feature_indices(feature_mask, B, L)
+        return _engine(self.model).neuron_feature_ablation(inputs, self.layer, neuron_selector, baselines=baselines,
+                                                           feature_mask=feature_mask, internal_batch_size=ibs)
 
 
 _WRAPPABLE = (Saliency, InputXGradient, IntegratedGradients, GradientShap, Occlusion, FeatureAblation, FeaturePermutation,

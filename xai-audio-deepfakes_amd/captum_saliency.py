@@ -14,6 +14,8 @@ from captum.attr import ShapleyValueSampling, ShapleyValues, KernelShap  # noqa:
 from captum.attr import Lime, FeaturePermutation  # noqa: F401
 from captum.attr import LayerActivation, LayerGradientXActivation, LayerIntegratedGradients, LayerConductance  # noqa: F401
 from captum.attr import InternalInfluence  # noqa: F401
+from captum.attr import NeuronGradient, NeuronIntegratedGradients, NeuronGradientShap, NeuronConductance  # noqa: F401
+from captum.attr import NeuronFeatureAblation  # noqa: F401
 from captum.attr._core.lime import get_exp_kernel_similarity_function  # noqa: F401
 from captum._utils.models.linear_model import SkLearnLasso, SkLearnRidge, SkLearnLinearRegression  # noqa: F401
 from captum.metrics import infidelity, sensitivity_max, NoisyPerturbation  # noqa: F401
@@ -53,6 +55,15 @@ class Wav2vec2LogReg(nn.Module):
         cfg, _ = _rt.embedder_config_and_weights()
         return min(cfg.layer_index, cfg.num_hidden_layers)
 
+    def frame_shape(self, n_samples):
+        """``(T, H)`` of ``hidden_states[l]`` for clips of ``n_samples`` samples, from the configuration alone -- the neuron
+        methods check their ``neuron_selector`` against it before any GPU work."""
+        cfg, _ = _rt.embedder_config_and_weights()
+        n = int(n_samples)
+        for k, s in zip(cfg.conv_kernel, cfg.conv_stride):
+            n = (n - k) // s + 1
+        return n, cfg.hidden_size
+
     def hip_attribution(self):
         if self._att is None:
             from addvisor_hip.attribution import HipAttribution
@@ -81,11 +92,21 @@ def _check_batch(method, waves):
         raise ValueError("method='feature_permutation' takes each segment from another clip of the batch: pass two clips or more")
 
 
-def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5, stdevs=0.01, layer=None):
+def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5, stdevs=0.01, layer=None, neuron=None):
     """The attribution of ``explain_waves``'s ``method`` (wrapped in NoiseTunnel when ``nt_type`` is set) as a callable
     ``[R, L] -> [R, L]`` on the engine ``att``.  The layer methods attribute ``hidden_states[layer]`` (default: the layer the
     classifier reads); their ``[R, T, H]`` map is summed over the channels and each frame's relevance spread to its samples
-    (``HipAttribution.layer_relevance``)."""
+    (``HipAttribution.layer_relevance``).  The neuron methods attribute the unit(s) ``neuron`` (a ``(t, h)`` tuple of ints or
+    slices) of that layer to the waveform directly."""
+    if method in ("neuron_gradient", "neuron_integrated_gradients"):
+        if nt_type is not None:
+            raise ValueError("NoiseTunnel does not wrap the neuron methods")
+        if neuron is None:
+            raise ValueError(f"method={method!r} needs neuron=(t, h)")
+        l = att.eg.emb.nl if layer is None else layer
+        if method == "neuron_integrated_gradients":
+            return lambda w: att.neuron_integrated_gradients(w, l, neuron, n_steps=n_steps)
+        return lambda w: att.neuron_gradient(w, l, neuron)
     if method in ("layer_integrated_gradients", "layer_gradient_x_activation"):
         if nt_type is not None:
             raise ValueError("NoiseTunnel does not wrap the layer methods")
@@ -106,7 +127,7 @@ def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, n
 
 
 def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5,
-                  stdevs=0.01, layer=None):
+                  stdevs=0.01, layer=None, neuron=None):
     """Loop body of compute_camptum_saliency_metrics (captum_saliency.py:125-192) for a batch ``[B, L]``:
     attribution -> |attr|/max time mask -> wave*mask, wave*(1-mask) -> three classifier passes.
     ``method="occlusion"`` occludes ``window``-sample windows every ``stride`` samples (default 100 ms / 50 ms at 16 kHz);
@@ -114,14 +135,16 @@ def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=16
     ``"lime"`` (n_samples = 50, the cosine kernel, a Lasso with alpha = 0.01) and ``"feature_permutation"`` (each segment taken
     from another clip of the batch: it needs two clips or more, ValueError before any GPU work otherwise).
     ``method="layer_integrated_gradients"`` / ``"layer_gradient_x_activation"`` attribute ``hidden_states[layer]`` (``layer=None``:
-    the layer the classifier reads) and mask the waveform with each frame's relevance summed over the channels.
+    the layer the classifier reads) and mask the waveform with each frame's relevance summed over the channels;
+    ``method="neuron_gradient"`` / ``"neuron_integrated_gradients"`` attribute the unit(s) ``neuron`` (a ``(t, h)`` tuple of ints
+    or slices) of ``hidden_states[layer]`` to the waveform.
     ``nt_type`` ("smoothgrad", "smoothgrad_sq", "vargrad") wraps the method in NoiseTunnel over ``nt_samples`` noisy copies
     of each clip; ``stdevs`` is the noise's standard deviation in waveform units (Captum's default of 1.0 would drown a
     waveform in [-1, 1]).  Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
     _check_batch(method, waves)
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
-    attr = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs, layer)(x)
+    attr = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs, layer, neuron)(x)
     _, w_rel, w_irr = att.time_mask(attr, x)
     emb = _rt.hip_embedder()
     B = x.shape[0]
@@ -130,7 +153,7 @@ def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=16
 
 
 def score_explanations(model, waves, method="input_x_gradient", n_steps=50, window=1600, stride=800, nt_type=None, nt_samples=5,
-                       stdevs=0.01, n_perturb_samples=10, perturb_radius=0.02, norm_ord="fro", multiply_by_inputs=False, layer=None):
+                       stdevs=0.01, n_perturb_samples=10, perturb_radius=0.02, norm_ord="fro", multiply_by_inputs=False, layer=None, neuron=None):
     """Captum's two explanation metrics of ``explain_waves``'s attribution (``method``, optionally in NoiseTunnel) for a batch
     ``[B, L]``: ``{"infidelity": [B], "sensitivity_max": [B]}`` fp32.  Infidelity perturbs each clip ``n_perturb_samples``
     times with ``NoisyPerturbation(stdevs, multiply_by_inputs)`` (``x - stdevs * N(0, 1)``; ``stdevs`` in waveform units, as in
@@ -139,7 +162,7 @@ def score_explanations(model, waves, method="input_x_gradient", n_steps=50, wind
     _check_batch(method, waves)
     att = model.hip_attribution()
     x = waves.to(device, torch.float32)
-    explain = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs, layer)
+    explain = _explainer(att, method, n_steps, window, stride, nt_type, nt_samples, stdevs, layer, neuron)
     attr = explain(x)
     return {"infidelity": infidelity(model, NoisyPerturbation(stdevs, multiply_by_inputs), x, attr,
                                      n_perturb_samples=n_perturb_samples),

@@ -10,6 +10,7 @@ int advh_init_attention();   // attention.hip
 int advh_split_flag_attention(int* flag);
 int advh_split_flag_attention_bwd_f32(int* flag);
 int advh_split_flag_attribution_layer(int* flag);
+int advh_split_flag_attribution_neuron(int* flag);
 int advh_split_flag_attention_bwd_x3(int* flag);
 int advh_split_flag_backward(int* flag);
 int advh_split_flag_conv_taps(int* flag);
