@@ -516,6 +516,66 @@ int advh_row_norm(const float* v, int rows, int64_t n, int ord, float* out, advh
 int advh_sensitivity_fold(const float* e, const float* et, const float* enorm, int B, int p, int64_t n, int ord, float* ratio,
                           float* smax, advh_stream_t stream);
 
+/* Adversarial attacks (csrc/attribution_robust.hip): Captum's FGSM and PGD (captum.robust) on the [B][n] clips, restated from
+ * Captum 0.7's robust/_core/fgsm.py and pgd.py (captum is absent).  These kernels are the iterate update between two
+ * forward + backward pairs of the gradient chain; all rows fp32, contiguous.  Every product, sum and difference is rounded on
+ * its own (no FMA contraction), as the unfused torch expressions round them.
+ *
+ * advh_robust_step : launch rows [row0, row0 + rows) of the B * p rows into out [rows][n]; row r is clip b = r / p and ladder
+ *     index k = r % p (p = 1 for FGSM and PGD proper; p = K builds an epsilon ladder).  x and grad have B rows (indexed by b) or
+ *     B * p rows (indexed by r).  Per element j:
+ *       gl = seed[b] * grad[.][j]                       seed = dL/d logit per clip, NULL = 1: the chain runs with the unit seed
+ *                                                       and the per-clip factor is applied here (the loss gradient, by linearity)
+ *       e  = (float)(multiplier * eps[k])               multiplier = -1 if targeted else +1, the product in double (a Python float)
+ *       v  = |gl| > 1e-6f ? x + (e * sign(gl)) * mask : x
+ *            -- FGSM._perturb: torch.where(torch.abs(grad) > self.zero_thresh, inp + multiplier * epsilon * torch.sign(grad) * mask,
+ *            inp); zero_thresh = 10 ** -6 is a constant here; mask NULL gives x + e * sign(gl); mask is [1][n] or [B][n]
+ *       norm 0 : no projection (FGSM)
+ *       norm 1 : v = x0 + clamp(v - x0, -radius, radius)          -- PGD._clip, "Linf": inputs + torch.clamp(diff, -radius, radius)
+ *       norm 2 : d = v - x0, s = sqrt(sum_j d^2), v = x0 + d * (s > radius ? radius / (s + 1e-7f) : 1)
+ *            -- PGD._clip, "L2": inputs + torch.renorm(diff, 2, 0, radius); the row sum is a fixed-shape tree in one workgroup
+ *            (thread t adds quads t, t + 256, ... in order, then a wave64 xor tree and (w0 + w1) + (w2 + w3)); the second pass
+ *            recomputes d, so the row is never staged
+ *       out = clamp(v, lo, hi)                          -- self.bound: torch.clamp(x, min=lower_bound, max=upper_bound); -+inf allowed
+ *     out may alias the launch rows of x.  eps is a HOST array of p doubles (p <= ADVH_ROBUST_MAX_P): the p step sizes travel as
+ *     kernel arguments.
+ * advh_robust_random_start : PGD._random_point, bounded; clip b draws from Philox row b of seed (the words of advh_philox_normal):
+ *       norm 1 : out = clamp(x0 + radius * (2u - 1), lo, hi), u the uniforms of advh_metric_rows' mode 0 (the row of S = 1, p = 1)
+ *            -- torch.rand_like(center) * radius * 2 - radius
+ *       norm 2 : out = clamp(x0 + (r_b / ||z||) * z, lo, hi), z = N(seed, b, :), ||z|| over the same tree, r_b = radius * u_b^(1/n),
+ *            u_b the first uniform of Philox row B + b  -- F.normalize(torch.randn_like(center)) * torch.rand(B) ** (1 / d) * radius
+ * advh_robust_first_flip : the fold of an epsilon ladder, one thread per clip, k in increasing order: out[b] = eps[k] (a device
+ *     array of K floats) and first[b] = k of the first k with (logit[b * K + k] > 0) != (clean_logit[b] > 0); +inf and K when no
+ *     k flips the decision.
+ * No atomics: equal inputs give equal bits, for every split of the rows over launches.  NaN / inf propagate into the results
+ * (the caller's finiteness check reports them).  Null pointers (seed and mask excepted, and x0 when norm == 0), non-positive
+ * sizes, p above ADVH_ROBUST_MAX_P, an unknown norm, a targeted flag outside {0, 1}, a radius or eps that is negative or not
+ * finite, lo > hi or a NaN bound, x_rows / grad_rows that are neither B nor B * p, mask_rows neither 1 nor B, a row window outside
+ * B * p and B * p (B * K) above int range return ADVH_EINVAL before any HIP call.
+ * Replaces captum.robust.FGSM(...).perturb(...) and captum.robust.PGD(...).perturb(...). */
+#define ADVH_ROBUST_MAX_P 64
+typedef struct advh_robust_desc {
+    const float* x0;       /* [B][n] clean clips: the projection's centre (norm 1, 2)            */
+    const float* x;        /* [x_rows][n] current iterate                                       */
+    const float* grad;     /* [grad_rows][n] d logit / d x of the unit seed                     */
+    const float* seed;     /* [B] dL/d logit per clip, or NULL (1)                              */
+    const float* mask;     /* [mask_rows][n], or NULL                                           */
+    const double* eps;     /* HOST [p] step sizes, each finite and >= 0                         */
+    int64_t n;
+    int B, p;
+    int x_rows, grad_rows; /* B or B * p                                                        */
+    int mask_rows;         /* 1 or B                                                            */
+    int targeted;          /* 0: multiplier +1, 1: multiplier -1                                */
+    int norm;              /* 0: none (FGSM), 1: Linf, 2: L2                                    */
+    float radius;          /* norm 1, 2: finite, >= 0                                           */
+    float lo, hi;          /* the bounds, lo <= hi, -+inf allowed                               */
+} advh_robust_desc;
+int advh_robust_step(const advh_robust_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream);
+int advh_robust_random_start(const float* x0, int B, int64_t n, uint64_t seed, int norm, float radius, float lo, float hi, float* out,
+                             advh_stream_t stream);
+int advh_robust_first_flip(const float* logit, const float* clean_logit, const float* eps, int B, int K, float* out, int* first,
+                           advh_stream_t stream);
+
 /* Perturbation attributions (csrc/attribution_ablation.hip): Captum's Occlusion and FeatureAblation of the [B][n] inputs x,
  * restated (captum is absent).  K perturbations; the ablated rows are perturbation-major, row g = k * B + b (Captum's
  * input.repeat), and F is the classifier logit.

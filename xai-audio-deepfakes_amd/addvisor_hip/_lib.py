@@ -83,6 +83,9 @@ SIGNATURES = {
     "advh_infidelity_finalize": (_i, [_p, _i, _i, _i, _p, _p]),
     "advh_row_norm": (_i, [_p, _i, _i64, _i, _p, _p]),
     "advh_sensitivity_fold": (_i, [_p, _p, _p, _i, _i, _i64, _i, _p, _p, _p]),
+    "advh_robust_step": (_i, [_p, _i64, _i, _p, _p]),
+    "advh_robust_random_start": (_i, [_p, _i, _i64, C.c_uint64, _i, _f, _f, _f, _p, _p]),
+    "advh_robust_first_flip": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
     "advh_ablation_points": (_i, [_p, _i64, _i, _p, _p]),
     "advh_ablation_accumulate": (_i, [_p, _p, _p, _p, _p]),
     "advh_coalition_points": (_i, [_p, _i64, _i, _p, _p]),

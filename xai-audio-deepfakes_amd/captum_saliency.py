@@ -19,6 +19,7 @@ from captum.attr import NeuronFeatureAblation  # noqa: F401
 from captum.attr._core.lime import get_exp_kernel_similarity_function  # noqa: F401
 from captum._utils.models.linear_model import SkLearnLasso, SkLearnRidge, SkLearnLinearRegression  # noqa: F401
 from captum.metrics import infidelity, sensitivity_max, NoisyPerturbation  # noqa: F401
+from captum.robust import FGSM, PGD  # noqa: F401
 from classifier_embedder import TorchLogReg  # noqa: F401  (name kept for callers of the reference module)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -44,6 +45,7 @@ class Wav2vec2LogReg(nn.Module):
         self.ap = audioprocessor
         self.logReg = logReg
         self._att = None
+        self._rob = None
 
     def forward(self, waveform):
         logits, _ = self.ap.classify(waveform)
@@ -69,6 +71,12 @@ class Wav2vec2LogReg(nn.Module):
             from addvisor_hip.attribution import HipAttribution
             self._att = HipAttribution(_rt.hip_embedder())
         return self._att
+
+    def hip_robust(self):
+        if self._rob is None:
+            from addvisor_hip.robust import HipRobust
+            self._rob = HipRobust(self.hip_attribution())
+        return self._rob
 
 
 def extract_wavs(metadata):
@@ -168,6 +176,43 @@ def score_explanations(model, waves, method="input_x_gradient", n_steps=50, wind
                                      n_perturb_samples=n_perturb_samples),
             "sensitivity_max": sensitivity_max(explain, x, perturb_radius=perturb_radius, n_perturb_samples=n_perturb_samples,
                                                norm_ord=norm_ord)}
+
+
+ATTACKS = ("fgsm", "pgd")
+PGD_DEFAULTS = dict(radius=2e-3, step_size=5e-4, step_num=5)            # waveform units: a clip lives in [-1, 1]
+
+
+def attack_waves(model, waves, labels, attack="pgd", explain=None, **attack_kwargs):
+    """Attack a batch ``[B, L]`` against its ``labels`` (0 / 1, an int or ``[B]``: the default loss's target) with
+    ``captum.robust.FGSM`` (``attack="fgsm"``; ``epsilon``, default 1e-3) or ``PGD`` (``"pgd"``; ``radius``, ``step_size``,
+    ``step_num``, default 2e-3 / 5e-4 / 5), passing ``attack_kwargs`` (``loss_func``, ``lower_bound``, ``upper_bound`` go to the
+    constructor, the rest to ``perturb``).  Returns ``{"adversarial": [B, L], "predictions": [B, 1], "adversarial_predictions":
+    [B, 1]}`` (both from one forward over ``cat([x, x_adv])``) and, when ``explain`` names an ``explain_waves`` method (its
+    defaults), ``"explanation_shift" [B]``: ``||a(x_adv) - a(x)||_2 / ||a(x)||_2`` (a zero norm counts as 1), reduced on the
+    device by sensitivity_max's row-norm kernels."""
+    if attack not in ATTACKS:
+        raise ValueError(f"attack must be one of {ATTACKS}, not {attack!r}")
+    if explain is not None:
+        _check_batch(explain, waves)
+    kw = dict(attack_kwargs)
+    ctor = {k: kw.pop(k) for k in ("loss_func", "lower_bound", "upper_bound") if k in kw}
+    x = waves.to(device, torch.float32) if torch.is_tensor(waves) else waves
+    if attack == "fgsm":
+        x_adv = FGSM(model, **ctor).perturb(x, kw.pop("epsilon", 1e-3), labels, **kw)
+    else:
+        args = [kw.pop(k, v) for k, v in PGD_DEFAULTS.items()]
+        x_adv = PGD(model, **ctor).perturb(x, *args, labels, **kw)
+    B = x.shape[0]
+    _, _, p = _rt.hip_embedder().forward(torch.cat([x, x_adv], 0), want_hidden=False)
+    out = {"predictions": p[:B], "adversarial_predictions": p[B:], "adversarial": x_adv}
+    if explain is not None:
+        from addvisor_hip import attribution as _A
+        fn = _explainer(model.hip_attribution(), explain)
+        e, et = fn(x).contiguous(), fn(x_adv).contiguous()
+        shift = torch.zeros(B, dtype=torch.float32, device=e.device)
+        _A.sensitivity_fold(e, et, _A.row_norm(e, 0), 1, 0, shift)          # max(0, ratio) = ratio
+        out["explanation_shift"] = shift
+    return out
 
 
 def compute_camptum_saliency_metrics(model, metadata_path, target_class=None, root="LJSpeech_vocoded",
