@@ -101,6 +101,25 @@ int advh_istft_masked_bwd(const float* g_wave, int64_t g_stride, const float* ma
                           int Fm, int Tm, int mode, int which, float* dmask, int B, int T, int L, int hop, int win,
                           const float* window, advh_stream_t stream);
 
+/* The row-mapped pair of the mask-domain attributions (addvisor_hip/spectral_attribution.py): `rows` masks [rows][Fm][Tm] over
+ * the spectrograms spec [B][513][T][2] of B clips, mask-in branch only.  Launch row r reads the spectrogram of clip
+ *   c = (row0 + r) % B  (clip_major = 0: rows s * B + b, k * B + b, (p * K + j) * B + b)  or
+ *   c = (row0 + r) / S  (clip_major = 1: rows b * S + s),
+ * clamped to [0, B): the clip comes from the rule, no index array goes to the device.  S >= 1 in both rules.
+ * advh_istft_masked_rows     : wave [rows][wave_stride] <- istft(X_c * g(mask_r, |X_c|) / |X_c|), the arithmetic of
+ *                              advh_istft_masked_c64's mask-in signal.
+ * advh_istft_masked_rows_bwd : dmask [rows][Fm][Tm] (overwritten) from g_wave [rows][g_stride], the adjoint of the above down to
+ *                              the mask, read from the complex X (no sincos):  linear dm = sc (Re G Re X + Im G Im X), the imaginary
+ *                              term dropped on bins 0 and 512;  log1p dm = log1p(M) exp(m log1p(M)) da with cos, sin = X / M, and
+ *                              0 where M < 1e-12.  `mask` is read in ADVH_MASK_LOG1P mode only (NULL allowed otherwise).
+ * Argument errors return a negative code before any HIP call.                                                        */
+int advh_istft_masked_rows(const float* spec, const float* mask, int Fm, int Tm, int mode, float* wave, int64_t wave_stride,
+                           int rows, int64_t row0, int clip_major, int S, int B, int T, int L, int hop, int win,
+                           const float* window, advh_stream_t stream);
+int advh_istft_masked_rows_bwd(const float* g_wave, int64_t g_stride, const float* spec, const float* mask, int Fm, int Tm,
+                               int mode, float* dmask, int rows, int64_t row0, int clip_major, int S, int B, int T, int L,
+                               int hop, int win, const float* window, advh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Implicit GEMM on the matrix cores (fp16 operands, fp32 accumulate):
  *
@@ -608,6 +627,27 @@ typedef struct advh_ablation_desc {
 } advh_ablation_desc;
 int advh_ablation_points(const advh_ablation_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream);
 int advh_ablation_accumulate(const advh_ablation_desc* d, const float* f0, const float* fk, float* attr, advh_stream_t stream);
+
+/* Captum's Occlusion for a 2-D input (csrc/attribution_spectral.hip): x [B][Fm][Tm] (the STFT mask), windows (wf, wt) every
+ * (sf, st), cropped at the edges.  Per axis K = ceil((n - w) / s) + 1 (w <= n, and s <= w unless w == n); window
+ * k = kf * Kt + kt, first dimension slowest, as Captum's _occlusion_mask enumerates; occluded rows are k * B + b.
+ *   advh_occlusion2d_points     : out[r] = occluded row g = row0 + r ([rows][Fm * Tm]); rows g >= Kf * Kt * B copy x[g % B].
+ *   advh_occlusion2d_accumulate : attr[b][f][t] = (sum of f0[b] - fk[k * B + b] over the windows k covering (f, t), in
+ *                                 increasing k) / their count; one thread per bin, no atomics.                        */
+typedef struct advh_occlusion2d_desc {
+    const float* x;        /* [B][Fm * Tm] inputs                                               */
+    const float* base;     /* [base_rows][Fm * Tm] baselines, base_rows = 1 or B                 */
+    int B, base_rows;
+    int Fm, Tm;
+    int wf, wt, sf, st;    /* window and stride per axis                                        */
+    int Kf, Kt;            /* windows per axis (must equal the formula above)                    */
+} advh_occlusion2d_desc;
+int advh_occlusion2d_points(const advh_occlusion2d_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream);
+int advh_occlusion2d_accumulate(const advh_occlusion2d_desc* d, const float* f0, const float* fk, float* attr, advh_stream_t stream);
+
+/* Band x segment relevance: out [B][nb][ns] = sums of attr [B][Fm][Tm] over boxes of bw bins x sw frames, nb = ceil(Fm / bw),
+ * ns = ceil(Tm / sw), the last box of an axis cropped.  One workgroup and one fixed-shape tree per box, no atomics. */
+int advh_tf_pool(const float* attr, int B, int Fm, int Tm, int bw, int sw, float* out, advh_stream_t stream);
 
 /* Shapley attributions over feature groups (csrc/attribution_shapley.hip): Captum's ShapleyValueSampling, ShapleyValues and
  * KernelShap of the [B][n] inputs x, restated (captum is absent).  index[.][t] in [0, K) is the feature of sample t (the rank of

@@ -95,6 +95,11 @@ SIGNATURES = {
     "advh_row_similarity": (_i, [_p, _p, _i64, _i, _i, _i64, _i, _f, _p, _p]),
     "advh_lasso_cd": (_i, [_p, _p, _i, _i, C.c_double, C.c_double, _i, _p, _p, _p]),
     "advh_istft_masked_bwd": (_i, [_p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "advh_istft_masked_rows": (_i, [_p, _p, _i, _i, _i, _p, _i64, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "advh_istft_masked_rows_bwd": (_i, [_p, _i64, _p, _p, _i, _i, _i, _p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "advh_occlusion2d_points": (_i, [_p, _i64, _i, _p, _p]),
+    "advh_occlusion2d_accumulate": (_i, [_p, _p, _p, _p, _p]),
+    "advh_tf_pool": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "advh_istft_bandswap": (_i, [_p, _p, _i, _i, _i, _p, _i64, _i64, _i, _i, _i, _i, _i, _p, _p]),
     "advh_bn_partial_count": (_i, []),
     "advh_bn_stats": (_i, [_p, _p, _p, _p, _p]),

@@ -982,11 +982,23 @@ class HipAttribution:
             waves = waves[None]
         return waves.to(self.emb.dev, torch.float32).contiguous()
 
+    # The seam of the chunk loops below: every batch of rows they build goes through this forward / gradient pair, which is told
+    # the rows' layout -- row r of ``pts`` is global row ``row0 + r``, of clip ``(row0 + r) % B`` (``clip_major=0``: rows
+    # ``s * B + b``, ``k * B + b``, ``(p * K + j) * B + b``) or ``(row0 + r) // S`` (``clip_major=1``: rows ``b * S + s``).  A
+    # waveform row is the classifier's input itself, so the layout is not used here; the mask-domain engine
+    # (spectral_attribution.py) overrides the pair and resynthesises each row from its clip's spectrogram first.
+    def _row_gradient(self, pts: torch.Tensor, row0: int = 0, clip_major: int = 0, S: int = 1) -> torch.Tensor:
+        """d logit / d row over ``pts [R, n]``, ``[R, n]`` fp32."""
+        self.eg.forward(pts)
+        return self.eg.backward(self.loss_scale)
+
+    def _row_logit(self, pts: torch.Tensor, row0: int = 0, clip_major: int = 0, S: int = 1) -> torch.Tensor:
+        """``[R]`` fp32 logits of the rows ``pts [R, n]``."""
+        return self.eg.emb.forward(pts, want_hidden=False)[1].view(-1)
+
     def input_gradient(self, waves: torch.Tensor) -> torch.Tensor:
         """d logit / d wave, ``[B, L]`` fp32."""
-        x = self._prep(waves)
-        self.eg.forward(x)
-        return self.eg.backward(self.loss_scale)
+        return self._row_gradient(self._prep(waves))
 
     def _finalize(self, g, x, mode):
         out = torch.empty_like(g)
@@ -1014,7 +1026,7 @@ class HipAttribution:
 
     def logits(self, waves) -> torch.Tensor:
         """``[B]`` fp32 logits of the gradient chain's own forward (the F of the convergence deltas)."""
-        return self.eg.emb.forward(self._prep(waves), want_hidden=False)[1].view(-1)
+        return self._row_logit(self._prep(waves))
 
     def integrated_gradients(self, waves, n_steps: int = 50, internal_batch_size: Optional[int] = None, baselines=None,
                              method: str = "gausslegendre", multiply_by_inputs: bool = True, return_convergence_delta: bool = False):
@@ -1044,8 +1056,7 @@ class HipAttribution:
         pts = torch.empty((per * B, L), dtype=torch.float32, device=x.device)
         for s0 in range(0, npad, per):
             _points(d, a_all, s0 * B, per * B, pts)
-            self.eg.forward(pts)
-            g = self.eg.backward(self.loss_scale)                               # [per*B, L], step-major
+            g = self._row_gradient(pts, s0 * B)                                 # [per*B, L], step-major
             _accumulate(d, g, w_all, ACC_IG, s0 * B, per * B, total)
         out = torch.empty_like(x)
         sums = torch.empty(B, dtype=torch.float32, device=x.device) if return_convergence_delta else None
@@ -1100,8 +1111,7 @@ class HipAttribution:
         for row0 in range(0, R, chunk):
             rows = min(chunk, R - row0)
             _points(d, a_all, row0, rows, pts)
-            self.eg.forward(pts)
-            g = self.eg.backward(self.loss_scale)                               # [chunk, L], clip-major
+            g = self._row_gradient(pts, row0, 1, S)                             # [chunk, L], clip-major
             _accumulate(d, g, None, mode, row0, rows, total, row_sum)
         out = torch.empty_like(x)
         _accumulate(d, total, None, FIN_MEAN, 0, B, out)
@@ -1160,7 +1170,7 @@ class HipAttribution:
         chunk = min(chunk, R)
         pts = torch.empty((chunk, L), dtype=torch.float32, device=x.device)
         fk = self._row_logits(points or (lambda row0, out: ablation_points(d, row0, chunk, out)), 0, R, pts)
-        f0 = self.eg.emb.forward(x, want_hidden=False)[1].view(-1)
+        f0 = self._row_logit(x)
         attr = torch.empty_like(x)
         ablation_accumulate(d, f0, fk, attr)
         return self._checked(attr, what, "a logit of the clips or of their ablations is not finite (check the inputs and baselines)")
@@ -1174,7 +1184,7 @@ class HipAttribution:
         fk = torch.empty(nchunk * chunk, dtype=torch.float32, device=pts.device)
         for c in range(nchunk):
             points(row0 + c * chunk, pts)
-            fk[c * chunk:(c + 1) * chunk] = self.eg.emb.forward(pts, want_hidden=False)[1].view(-1)
+            fk[c * chunk:(c + 1) * chunk] = self._row_logit(pts, row0 + c * chunk)
         return fk
 
     def _shapley_args(self, waves, baselines, feature_mask, internal_batch_size):
@@ -1220,7 +1230,7 @@ class HipAttribution:
         kb = K * B
         G = max(1, min(P, max(GROUP_ROWS, chunk) // kb))
         pts = torch.empty((min(chunk, G * kb), L), dtype=torch.float32, device=dev)
-        fbase = self.eg.emb.forward(base.expand(B, L).contiguous(), want_hidden=False)[1].view(-1)
+        fbase = self._row_logit(base.expand(B, L).contiguous())
         total = torch.zeros_like(x)
         for p0 in range(0, P, G):
             g = min(G, P - p0)

@@ -147,6 +147,64 @@ def istft_masked_bwd(g_wave: torch.Tensor, mag: torch.Tensor, phase: torch.Tenso
     return dmask
 
 
+def _rows_args(spec, mask, clip_major, S, row0, length, hop, *others):
+    if not torch.is_complex(spec) or spec.dtype != torch.complex64 or spec.dim() != 3 or spec.shape[1] != NBIN:
+        raise ValueError("spec must be complex64 [B, 513, T]")
+    if not spec.is_cuda:
+        raise ValueError("spec must be a CUDA (HIP) tensor")
+    B, _, T = spec.shape
+    for t in (mask,) + others:
+        if t is not None and t.device != spec.device:
+            raise ValueError(f"every tensor must be on spec's device {spec.device}, got one on {t.device}")
+    if mask is not None:
+        if mask.dim() != 3 or mask.shape[0] < 1 or mask.shape[1] > NBIN or mask.shape[2] > T:
+            raise ValueError("mask must be [rows >= 1, Fm<=513, Tm<=T]")
+    if T != 1 + length // hop:
+        raise ValueError("T does not match length // hop + 1")
+    if clip_major not in (0, 1) or int(S) < 1 or int(row0) < 0:
+        raise ValueError("the row rule needs clip_major 0 or 1, S >= 1 and row0 >= 0")
+    return torch.view_as_real(spec.contiguous()), B, T
+
+
+def istft_masked_rows(spec: torch.Tensor, mask: torch.Tensor, length: int, domain: str = "linear", row0: int = 0,
+                      clip_major: int = 0, S: int = 1, hop: int = 322, win: int = 644,
+                      window: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mask-in resynthesis of :func:`istft_masked_c64` over ROWS: ``mask [rows, Fm, Tm]`` -> ``wave [rows, length]``, row r
+    applied to the spectrogram of clip ``(row0 + r) % B`` (``clip_major=0``) or ``(row0 + r) // S`` (``clip_major=1``) of
+    ``spec [B, 513, T]``, clamped to ``[0, B)``: the spectrograms are never copied per row."""
+    _lib.init()
+    mask = _req(mask, torch.float32, "mask")
+    sr, B, T = _rows_args(spec, mask, clip_major, S, row0, length, hop)
+    mode = {"linear": 1, "log1p": 2}[domain]
+    rows = mask.shape[0]
+    wave = torch.empty((rows, length), dtype=torch.float32, device=spec.device)
+    rc = _lib.lib().advh_istft_masked_rows(sr.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[2], mode, wave.data_ptr(), length,
+                                           rows, int(row0), int(clip_major), int(S), B, T, length, hop, win, _ptr(window), _stream())
+    _lib.check(rc, "advh_istft_masked_rows")
+    return wave
+
+
+def istft_masked_rows_bwd(g_wave: torch.Tensor, spec: torch.Tensor, mask: torch.Tensor, domain: str = "linear", row0: int = 0,
+                          clip_major: int = 0, S: int = 1, hop: int = 322, win: int = 644,
+                          window: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The adjoint of :func:`istft_masked_rows` down to the mask: ``g_wave [rows, length]`` -> ``dmask [rows, Fm, Tm]`` (the
+    shape of ``mask``, whose values are read in the ``log1p`` domain only), same row rule."""
+    _lib.init()
+    mask = _req(mask, torch.float32, "mask")
+    g_wave = _req(g_wave, torch.float32, "g_wave")
+    if g_wave.dim() != 2 or g_wave.shape[0] != mask.shape[0]:
+        raise ValueError("g_wave must be [rows, length], one row per mask row")
+    length = g_wave.shape[1]
+    sr, B, T = _rows_args(spec, mask, clip_major, S, row0, length, hop, g_wave)
+    mode = {"linear": 1, "log1p": 2}[domain]
+    dmask = torch.empty_like(mask)
+    rc = _lib.lib().advh_istft_masked_rows_bwd(g_wave.data_ptr(), length, sr.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[2],
+                                               mode, dmask.data_ptr(), mask.shape[0], int(row0), int(clip_major), int(S), B, T, length,
+                                               hop, win, _ptr(window), _stream())
+    _lib.check(rc, "advh_istft_masked_rows_bwd")
+    return dmask
+
+
 def istft_bandswap(spec_a: torch.Tensor, spec_b: torch.Tensor, length: int, k0: int = 0, kw: int = 64, nbands: int = 8,
                    hop: int = 322, win: int = 644, window: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Band-swap resynthesis (hifigan.py:196-228, train_logReg_swapping.py:64-92): for each band ``z`` the bins

@@ -13,16 +13,49 @@ does not wrap them either.
 ``Method(model).attribute(inputs, target=None, ...)`` expects ``model`` to be a
 ``captum_saliency.Wav2vec2LogReg`` (or anything exposing ``.hip_attribution()``): the waveform -> logit
 classifier whose frozen embedder runs on the GPU kernels.  Arbitrary ``nn.Module``s are not supported --
-there is no autograd fallback."""
+there is no autograd fallback.
+
+A model exposing ``.hip_mask_attribution()`` (``captum_saliency.MaskedSpectrogramLogReg``) is attributed over the STFT mask
+instead: Saliency, InputXGradient, IntegratedGradients, GradientShap, Occlusion, FeatureAblation and ShapleyValueSampling then
+take ``[B, Fm, Tm]`` inputs, baselines and feature masks (Occlusion: 2-tuples) and run on
+``addvisor_hip.spectral_attribution.HipSpectralAttribution``; every other method raises NotImplementedError for such a model."""
 import torch
 
 from addvisor_hip import attribution as _A
+from addvisor_hip import spectral_attribution as _S
 from addvisor_hip.linear_model import SkLearnLasso
 from ._core.feature_permutation import _permute_feature
 from ._core.lime import default_perturb_func, get_exp_kernel_similarity_function
 
 
+def _masked(model) -> bool:
+    """The model is attributed over the STFT mask (``[B, Fm, Tm]`` inputs) on ``HipSpectralAttribution``."""
+    return hasattr(model, "hip_mask_attribution")
+
+
+def _mask_checks(model, inputs, target):
+    """``[B, Fm, Tm]`` mask inputs of a mask-domain model, before its engine exists (ValueError) -> ``(B, Fm, Tm)``."""
+    B, Fm, Tm = _S.check_mask_inputs(inputs, target, model.mask_frames() if hasattr(model, "mask_frames") else None)
+    if hasattr(model, "num_clips") and B != model.num_clips():
+        raise ValueError(f"the model holds {model.num_clips()} clips; inputs has {B} masks")
+    return B, Fm, Tm
+
+
+def _mask_batch(model, inputs, target, perturbations_per_eval):
+    B, Fm, Tm = _mask_checks(model, inputs, target)
+    ppe = _A._positive_int(perturbations_per_eval, "perturbations_per_eval")
+    return B, Fm, Tm, (None if ppe == 1 else ppe * B)
+
+
+def _no_masks(model, what):
+    if _masked(model):
+        raise NotImplementedError(f"{what} over STFT masks is not implemented: HipSpectralAttribution offers Saliency, "
+                                  "InputXGradient, IntegratedGradients, GradientShap, Occlusion, FeatureAblation and "
+                                  "ShapleyValueSampling")
+
+
 def _engine(model):
+    _no_masks(model, "this method")
     if not hasattr(model, "hip_attribution"):
         raise TypeError("captum.attr (HIP build) only attributes captum_saliency.Wav2vec2LogReg models")
     return model.hip_attribution()
@@ -42,6 +75,10 @@ class _Method:
 
 class Saliency(_Method):
     def attribute(self, inputs, target=None, abs=True, additional_forward_args=None):
+        if _masked(self.model):
+            _mask_checks(self.model, inputs, target)
+            eng = self.model.hip_mask_attribution()
+            return eng.saliency(inputs) if abs else eng.input_gradient(inputs)
         self._check(inputs, target)
         eng = _engine(self.model)
         return eng.saliency(inputs) if abs else eng.input_gradient(inputs)
@@ -49,6 +86,9 @@ class Saliency(_Method):
 
 class InputXGradient(_Method):
     def attribute(self, inputs, target=None, additional_forward_args=None):
+        if _masked(self.model):
+            _mask_checks(self.model, inputs, target)
+            return self.model.hip_mask_attribution().input_x_gradient(inputs)
         self._check(inputs, target)
         return _engine(self.model).input_x_gradient(inputs)
 
@@ -62,6 +102,15 @@ class IntegratedGradients(_Method):
                   method="gausslegendre", internal_batch_size=None, return_convergence_delta=False):
         """Baselines: None (zero), a number, ``[1, L]`` or ``[B, L]``; methods: ``gausslegendre`` and the four Riemann
         rules.  ``return_convergence_delta=True`` returns ``(attributions, delta [B])``."""
+        if _masked(self.model):
+            B, Fm, Tm = _mask_checks(self.model, inputs, target)
+            _S.check_mask_baselines(baselines, B, Fm, Tm)
+            _A.approximation(method, _A.check_steps(n_steps, method))
+            if internal_batch_size is not None:
+                _A._positive_int(internal_batch_size, "internal_batch_size")
+            return self.model.hip_mask_attribution().integrated_gradients(
+                inputs, n_steps=n_steps, internal_batch_size=internal_batch_size, baselines=baselines, method=method,
+                multiply_by_inputs=self.multiply_by_inputs, return_convergence_delta=return_convergence_delta)
         self._check(inputs, target)
         return _engine(self.model).integrated_gradients(inputs, n_steps=n_steps, internal_batch_size=internal_batch_size,
                                                         baselines=baselines, method=method,
@@ -81,6 +130,15 @@ class GradientShap(_Method):
 
     def attribute(self, inputs, baselines, n_samples=5, stdevs=0.0, target=None, additional_forward_args=None,
                   return_convergence_delta=False):
+        if _masked(self.model):
+            B, Fm, Tm = _mask_checks(self.model, inputs, target)
+            if callable(baselines) and not torch.is_tensor(baselines):
+                raise NotImplementedError("GradientShap over STFT masks takes a [N_b, Fm, Tm] tensor of baseline masks, not a callable")
+            _S.check_mask_distribution(baselines, B, Fm, Tm, n_samples, stdevs)
+            if return_convergence_delta:
+                raise NotImplementedError("GradientShap over STFT masks (HipSpectralAttribution) does not compute the convergence delta")
+            return self.model.hip_mask_attribution().gradient_shap(inputs, baselines, n_samples=n_samples, stdevs=stdevs,
+                                                                   multiply_by_inputs=self.multiply_by_inputs)
         self._check(inputs, target)
         return _engine(self.model).gradient_shap(inputs, baselines, n_samples=n_samples, stdevs=stdevs,
                                                  multiply_by_inputs=self.multiply_by_inputs,
@@ -108,6 +166,11 @@ class Occlusion(_Method):
 
     def attribute(self, inputs, sliding_window_shapes, strides=None, baselines=None, target=None, additional_forward_args=None,
                   perturbations_per_eval=1, show_progress=False):
+        if _masked(self.model):                               # a (Fm, Tm) input: 2-tuples, windows cropped at the edges
+            B, Fm, Tm, ibs = _mask_batch(self.model, inputs, target, perturbations_per_eval)
+            w, s, _ = _S.check_occlusion2d_args(Fm, Tm, sliding_window_shapes, strides)
+            _S.check_mask_baselines(baselines, B, Fm, Tm)
+            return self.model.hip_mask_attribution().occlusion(inputs, w, s, baselines=baselines, internal_batch_size=ibs)
         ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
         B, L = inputs.shape
         win, stride, _ = _A.check_occlusion_args(L, sliding_window_shapes, strides)
@@ -122,6 +185,12 @@ class FeatureAblation(_Method):
 
     def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None,
                   perturbations_per_eval=1, show_progress=False):
+        if _masked(self.model):
+            B, Fm, Tm, ibs = _mask_batch(self.model, inputs, target, perturbations_per_eval)
+            _S.check_mask_baselines(baselines, B, Fm, Tm)
+            _A.feature_indices(_S.flat_feature_mask(feature_mask, B, Fm, Tm), B, Fm * Tm)
+            return self.model.hip_mask_attribution().feature_ablation(inputs, baselines=baselines, feature_mask=feature_mask,
+                                                                      internal_batch_size=ibs)
         ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
         B, L = inputs.shape
         _A.check_ig_baselines(baselines, B, L)
@@ -147,6 +216,13 @@ class ShapleyValueSampling(_Method):
 
     def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None, n_samples=25,
                   perturbations_per_eval=1, show_progress=False):
+        if _masked(self.model):
+            B, Fm, Tm, ibs = _mask_batch(self.model, inputs, target, perturbations_per_eval)
+            _S.check_mask_baselines(baselines, B, Fm, Tm)
+            _A.shapley_feature_indices(_S.flat_feature_mask(feature_mask, B, Fm, Tm), B, Fm * Tm)
+            _A.check_n_samples(n_samples)
+            return self.model.hip_mask_attribution().shapley_value_sampling(inputs, baselines=baselines, feature_mask=feature_mask,
+                                                                            n_samples=n_samples, internal_batch_size=ibs)
         ibs = _shapley_checks(inputs, target, perturbations_per_eval, baselines, feature_mask)
         _A.check_n_samples(n_samples)
         return _engine(self.model).shapley_value_sampling(inputs, baselines=baselines, feature_mask=feature_mask,
@@ -158,6 +234,7 @@ class ShapleyValues(_Method):
 
     def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None,
                   perturbations_per_eval=1, show_progress=False):
+        _no_masks(self.model, "ShapleyValues")
         ibs = _shapley_checks(inputs, target, perturbations_per_eval, baselines, feature_mask)
         return _engine(self.model).shapley_values(inputs, baselines=baselines, feature_mask=feature_mask, internal_batch_size=ibs)
 
@@ -170,6 +247,7 @@ class KernelShap(_Method):
 
     def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None, n_samples=25,
                   perturbations_per_eval=1, return_input_shape=True, show_progress=False):
+        _no_masks(self.model, "KernelShap")
         ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
         B, L = inputs.shape
         _A.check_ig_baselines(baselines, B, L)
@@ -199,6 +277,7 @@ class Lime(_Method):
 
     def attribute(self, inputs, baselines=None, target=None, additional_forward_args=None, feature_mask=None, n_samples=50,
                   perturbations_per_eval=1, return_input_shape=True, show_progress=False):
+        _no_masks(self.model, "Lime")
         ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
         B, L = inputs.shape
         _A.check_ig_baselines(baselines, B, L)
@@ -229,6 +308,7 @@ class FeaturePermutation(_Method):
 
     def attribute(self, inputs, target=None, additional_forward_args=None, feature_mask=None, perturbations_per_eval=1,
                   show_progress=False):
+        _no_masks(self.model, "FeaturePermutation")
         ibs = _perturbation_batch(inputs, target, perturbations_per_eval)
         B, L = inputs.shape
         _A.check_permutation_args(feature_mask, B, L)
@@ -239,6 +319,7 @@ def _layer_checks(model, inputs, target, layer, attribute_to_layer_input):
     """The checks every layer method shares, before the engine is touched: one output (``target`` None), a ``[B, L]`` input, the
     layer's output only (``attribute_to_layer_input=True`` raises NotImplementedError) and ``check_layer`` against the model's
     ``layer_index`` (ValueError)."""
+    _no_masks(model, "a layer or neuron method")
     _Method._check(inputs, target)
     if attribute_to_layer_input:
         raise NotImplementedError("the layer methods (HIP build) attribute to a layer's output, hidden_states[layer]; "
@@ -460,6 +541,7 @@ class NoiseTunnel:
 
     def attribute(self, inputs, nt_type="smoothgrad", nt_samples=5, nt_samples_batch_size=None, stdevs=1.0,
                   draw_baseline_from_distrib=False, **kwargs):
+        _no_masks(self.attribution_method.model, "NoiseTunnel")
         return_convergence_delta = kwargs.pop("return_convergence_delta", False)
         _A.check_noise_tunnel_args(nt_type, nt_samples, nt_samples_batch_size, stdevs, kwargs.pop("target", None))
         if not torch.is_tensor(inputs) or inputs.dim() != 2:

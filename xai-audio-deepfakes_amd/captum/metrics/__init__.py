@@ -73,6 +73,8 @@ def infidelity(forward_func, perturb_func, inputs, attributions, baselines=None,
     ``normalize``.  ``perturb_func(inputs[, baselines]) -> (perturbations, perturbed_inputs)``; a ``NoisyPerturbation`` runs
     fused on the device.  ``HipAttribution.infidelity`` states the arithmetic.  Bad arguments raise ValueError before any GPU
     work."""
+    if hasattr(forward_func, "hip_mask_attribution"):
+        raise NotImplementedError("infidelity over STFT masks is not implemented (HipSpectralAttribution)")
     if not hasattr(forward_func, "hip_attribution"):
         raise TypeError("captum.metrics (HIP build) only scores captum_saliency.Wav2vec2LogReg models")
     B, L, _, _ = _A.check_metric_args(inputs, n_perturb_samples, max_examples_per_batch, target, additional_forward_args,

@@ -17,6 +17,8 @@ __all__ = ["FGSM", "PGD"]
 
 
 def _check_model(forward_func, additional_forward_args):
+    if hasattr(forward_func, "hip_mask_attribution"):
+        raise NotImplementedError("attacks over STFT masks are not implemented (HipSpectralAttribution)")
     if not hasattr(forward_func, "hip_robust"):
         raise TypeError("captum.robust (HIP build) only attacks captum_saliency.Wav2vec2LogReg models")
     if additional_forward_args is not None:

@@ -79,6 +79,94 @@ class Wav2vec2LogReg(nn.Module):
         return self._rob
 
 
+class MaskedSpectrogramLogReg(nn.Module):
+    """STFT mask -> logit: ``F(m)[b] = logit(embedder(istft(X_b * g(m, |X_b|) / |X_b|)))`` over the clips ``waves [B, L]``
+    (``domain``: ``"linear"`` loss_function.py:36-45, or ``"log1p"`` LMAC_metrics.py:136-153; mask-in branch, bins outside the
+    mask's crop count as 0).  ``model`` is the ``Wav2vec2LogReg`` whose classifier is attributed.  The ``captum.attr`` methods
+    given this model attribute ``[B, Fm, Tm]`` masks (usually ``torch.ones(B, Fm, Tm)``, the clip itself, or the U-Net's mask)
+    on ``addvisor_hip.spectral_attribution.HipSpectralAttribution``."""
+
+    def __init__(self, model, waves, domain="linear"):
+        super().__init__()
+        from addvisor_hip import spectral_attribution as _S
+        if not hasattr(model, "hip_attribution"):
+            raise TypeError("MaskedSpectrogramLogReg wraps a captum_saliency.Wav2vec2LogReg")
+        if domain not in _S.DOMAINS:
+            raise ValueError(f"domain must be one of {_S.DOMAINS}, not {domain!r}")
+        if not torch.is_tensor(waves) or waves.dim() not in (1, 2):
+            raise ValueError("waves must be a [B, L] (or [L]) tensor")
+        self.model, self.domain = model, domain
+        self.waves = waves[None] if waves.dim() == 1 else waves
+        self.hop, self.win = 322, 644
+        self._eng = None
+
+    def num_clips(self):
+        return self.waves.shape[0]
+
+    def mask_frames(self):
+        """``T``: the frames of the clips' spectrograms, the largest ``Tm`` a mask may have."""
+        return 1 + self.waves.shape[1] // self.hop
+
+    def forward(self, mask):
+        return self.hip_mask_attribution().logits(mask).view(-1, 1)
+
+    def hip_mask_attribution(self):
+        if self._eng is None:
+            from addvisor_hip.spectral_attribution import HipSpectralAttribution
+            self._eng = HipSpectralAttribution(self.model.hip_attribution(), self.waves, self.domain, self.hop, self.win)
+        return self._eng
+
+
+def tf_feature_mask(Fm, Tm, band_bins=64, seg_frames=None):
+    """Feature ids ``[1, Fm, Tm]`` for FeatureAblation / ShapleyValueSampling over STFT masks: one per 1 kHz band
+    (``band_bins = 64`` of the 513 bins) and, with ``seg_frames``, per time segment (``id = band * n_seg + segment``)."""
+    from addvisor_hip.spectral_attribution import tf_feature_mask as _tf
+    return _tf(Fm, Tm, band_bins, seg_frames)
+
+
+SPECTRAL_METHODS = ("saliency", "input_x_gradient", "integrated_gradients", "occlusion", "feature_ablation",
+                    "shapley_value_sampling")
+
+
+def explain_spectrogram(model, waves, method="input_x_gradient", mask=None, baselines=None, n_steps=50, window=(64, 8),
+                        stride=(64, 4), band_bins=64, seg_frames=16, n_samples=25, domain="linear"):
+    """``explain_waves`` in the time-frequency domain for a batch ``[B, L]``: ``method`` (one of ``SPECTRAL_METHODS``) attributes
+    the classifier to the STFT mask ``mask`` (default ``ones(B, 513, T)``: the clip itself) through ``F`` of
+    ``MaskedSpectrogramLogReg(model, waves, domain)``; the explanation mask is ``|attr| / (max|attr| + 1e-8)`` per clip, and the
+    mask-in / mask-out signals are resynthesised from it in the ``log1p`` domain (``ops.istft_masked_c64``, LMAC_metrics.py:136-153).
+    ``"occlusion"`` uses ``window`` / ``stride`` (bins, frames); ``"feature_ablation"`` and ``"shapley_value_sampling"`` the
+    features of ``tf_feature_mask(Fm, Tm, band_bins, seg_frames)``; ``baselines`` as the engine's methods take them (for
+    ``"integrated_gradients"`` pass a mask baseline, not the zero mask: HipSpectralAttribution).  Three classifier passes in one
+    forward; returns ``(predictions, theta_out, masked_predictions)``, each ``[B, 1]``, ready for ``compute_faithfulness``,
+    ``compute_fidelity`` and ``lmac_metrics``."""
+    from addvisor_hip import ops as _ops
+    if method not in SPECTRAL_METHODS:
+        raise ValueError(f"method must be one of {SPECTRAL_METHODS}, not {method!r}")
+    if not torch.is_tensor(waves) or waves.dim() != 2:
+        raise ValueError("waves must be a [B, L] tensor")
+    eng = MaskedSpectrogramLogReg(model, waves, domain).hip_mask_attribution()
+    B, T = eng.B, eng.T
+    m = torch.ones((B, 513, T), dtype=torch.float32, device=eng.waves.device) if mask is None else mask.to(eng.waves.device, torch.float32)
+    Fm, Tm = m.shape[1], m.shape[2]
+    if method == "saliency":
+        attr = eng.saliency(m)
+    elif method == "input_x_gradient":
+        attr = eng.input_x_gradient(m)
+    elif method == "integrated_gradients":
+        attr = eng.integrated_gradients(m, n_steps=n_steps, baselines=baselines)
+    elif method == "occlusion":
+        attr = eng.occlusion(m, window, stride, baselines=baselines)
+    else:
+        ids = tf_feature_mask(Fm, Tm, band_bins, seg_frames)
+        attr = (eng.feature_ablation(m, baselines=baselines, feature_mask=ids) if method == "feature_ablation" else
+                eng.shapley_value_sampling(m, baselines=baselines, feature_mask=ids, n_samples=n_samples))
+    att = model.hip_attribution()
+    rel = att.time_mask(attr.reshape(B, Fm * Tm)).view(B, Fm, Tm)
+    w_rel, w_irr = _ops.istft_masked_c64(eng.spec, rel, eng.L, "log1p", hop=eng.hop, win=eng.win)
+    _, _, p = att.emb.forward(torch.cat([eng.waves, w_rel, w_irr], 0), want_hidden=False)
+    return p[:B], p[B:2 * B], p[2 * B:]
+
+
 def extract_wavs(metadata):
     """captum_saliency.py:103-109."""
     audio_files = []

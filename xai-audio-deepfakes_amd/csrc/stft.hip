@@ -117,7 +117,18 @@ __device__ __forceinline__ float mask_factor(float m, float M, int mode) {
 // (c_k = 1 for k = 0, N/2 where the C2R transform ignores the imaginary part, else 2).  The epilogue chains to the
 // mask: X = a e^{i phi}, a = m M (mask-in) or (1-m) M (mask-out) [linear] / expm1(m log1p M) [log1p]; it reads
 // `mag`, `phase` (and `X` = the mask for log1p) and writes dmask[b][k][t] for k < Fm, t < Tm.
-struct AdjArgs { const float* mask; float* dmask; int Fm, Tm, mode, which; };
+// Row map of the row-mapped entry points (SRC = 4, ADJ = 2): launch row r holds mask / waveform row r and reads the spectrogram
+// of clip c = (row0 + r) % B (clip_major = 0: rows s * B + b) or (row0 + r) / S (clip_major = 1: rows b * S + s), clamped to
+// [0, B).  The clip is computed here from the rule: no index array reaches the device.
+struct RowMap { long row0; int B, S, clip_major; };
+__device__ __forceinline__ int row_clip(const RowMap& rm, int r) {
+    const long g = rm.row0 + r;
+    const long c = rm.clip_major ? g / rm.S : g % rm.B;
+    return (int)(c < 0 ? 0 : c >= rm.B ? rm.B - 1 : c);
+}
+// ADJ = 2: the same adjoint over rows, from the COMPLEX spectrogram (passed in `X`, read at the row's clip) instead of
+// (|X|, angle X) -- no sincosf; mask-in branch only.  linear: dm = sc (Re G Re X + Im G Im X); log1p: cos, sin = X / |X|.
+struct AdjArgs { const float* mask; float* dmask; int Fm, Tm, mode, which; RowMap rm; };
 
 template <int FB, int ADJ>
 __global__ __launch_bounds__(THREADS, 6) void stft_fwd_kernel(
@@ -257,6 +268,24 @@ __global__ __launch_bounds__(THREADS, 6) void stft_fwd_kernel(
             if (k >= adj.Fm || t >= adj.Tm) continue;
             const bool edge = k == 0 || k == NFFT / 2;
             const float sc = (edge ? 1.f : 2.f) / NFFT;
+            if constexpr (ADJ == 2) {
+                const float2 xs = reinterpret_cast<const float2*>(X)[((long)row_clip(adj.rm, b) * NBIN + k) * T + t];
+                const long omr = ((long)b * adj.Fm + k) * adj.Tm + t;
+                float dmr;
+                if (adj.mode == ADVH_MASK_LINEAR) {
+                    dmr = sc * (xr * xs.x + (edge ? 0.f : xi * xs.y));
+                } else {
+                    const float Ms = __builtin_sqrtf(fmaf(xs.x, xs.x, xs.y * xs.y));
+                    if (Ms < 1e-12f) dmr = 0.f;
+                    else {
+                        const float das = sc * (xr * (xs.x / Ms) + (edge ? 0.f : xi * (xs.y / Ms)));
+                        const float lg = log1pf(Ms);
+                        dmr = lg * expf(adj.mask[omr] * lg) * das;
+                    }
+                }
+                adj.dmask[omr] = dmr;
+                continue;
+            }
             float sn, cs;
             sincosf(phase[o], &sn, &cs);
             const float da = sc * (xr * cs + (edge ? 0.f : xi * sn));       // dL/da, a = |X| after masking
@@ -286,6 +315,8 @@ __global__ __launch_bounds__(THREADS, 6) void stft_fwd_kernel(
 // SRC 3: complex64 spectrogram X (in `mag`) + mask: X' = X * g(m, |X|) / |X| -- the mask application of SRC 0 without the
 // polar round trip (no atan2 in the forward, no sincos here); what the explanation pipeline runs.
 // SRC 0 / 3 with both outputs requested: grid z = 2, one workgroup per branch (the second branch's tile reads hit L2).
+// SRC 4: SRC 3's mask-in branch over ROWS: grid y = row r, whose mask row r is applied to the spectrogram of clip row_clip(rm, r)
+// and whose waveform goes to out0 + r * wave_stride (the path and perturbation batches of the mask-domain attributions).
 // SRC 0: mag/phase (+ optional mask, mode), SRC 1: complex64 spectrogram, SRC 2: band swap of two complex64
 // spectrograms (hifigan.py:208-222, train_logReg_swapping.py:70-81): grid z = band, bins [Fm + z*Tm, Fm + (z+1)*Tm)
 // come from `phase` (the vocoded signal), all others from `mag` (the original); output z at out0 + z * out1_stride.
@@ -293,7 +324,7 @@ template <int SRC, int FB>
 __global__ __launch_bounds__(THREADS, 4) void istft_kernel(
     const float* __restrict__ mag, const float* __restrict__ phase, const float* __restrict__ mask,
     int Fm, int Tm, int mode, int which0, float* __restrict__ out0, float* __restrict__ out1,
-    long wave_stride, int T, int L, int hop, int win, int R, const float* __restrict__ window, long zstride) {
+    long wave_stride, int T, int L, int hop, int win, int R, const float* __restrict__ window, long zstride, RowMap rm) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int ROWP = RowPitch<FB>::value;
     float *re, *im, *unused_scratch;
@@ -301,6 +332,8 @@ __global__ __launch_bounds__(THREADS, 4) void istft_kernel(
     (void)unused_scratch;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int b = blockIdx.y, g = blockIdx.x;
+    int bs = b;                                       // the clip whose spectrogram the workgroup reads
+    if constexpr (SRC == 4) bs = row_clip(rm, b);
     const int left = (NFFT - win) / 2;
     const int S = FB - R + 1;                         // complete hop-segments this workgroup emits
     const int tA = g * S - (R - 1);                   // first frame it transforms (may be < 0)
@@ -322,13 +355,13 @@ __global__ __launch_bounds__(THREADS, 4) void istft_kernel(
         ld0[it] = make_float2(0.f, 0.f);
         ldm[it] = 0.f;
         if (valid[it]) {
-            const long o = ((long)b * NBIN + k) * T + t;
+            const long o = ((long)bs * NBIN + k) * T + t;
             if (SRC == 0) ld0[it] = make_float2(mag[o], phase[o]);
             else if (SRC == 2) {
                 const int lo = Fm + (int)blockIdx.z * Tm;
                 ld0[it] = reinterpret_cast<const float2*>((k >= lo && k < lo + Tm) ? phase : mag)[o];
             } else ld0[it] = reinterpret_cast<const float2*>(mag)[o];
-            if ((SRC == 0 || SRC == 3) && mode != ADVH_MASK_NONE && k < Fm && t < Tm) ldm[it] = mask[((long)b * Fm + k) * Tm + t];
+            if ((SRC == 0 || SRC == 3 || SRC == 4) && mode != ADVH_MASK_NONE && k < Fm && t < Tm) ldm[it] = mask[((long)b * Fm + k) * Tm + t];
         }
     }
     const int which = which0 + (SRC == 2 ? 0 : pass);  // 0: mask-in, 1: mask-out
@@ -343,7 +376,7 @@ __global__ __launch_bounds__(THREADS, 4) void istft_kernel(
         if (idx >= NBIN * FB) break;
         const int tl = idx & (FB - 1), k = idx / FB;
         float xr = ld0[it].x, xi = ld0[it].y;
-        if (SRC == 3) {
+        if (SRC == 3 || SRC == 4) {
             float m = ldm[it];
             if (which == 1) m = 1.f - m;
             const float f = valid[it] ? mask_factor(m, __builtin_sqrtf(fmaf(xr, xr, xi * xi)), mode) : 0.f;
@@ -494,7 +527,9 @@ extern "C" int advh_init(void) {
                          (const void*)stft_fwd_kernel<8, 1>, (const void*)istft_kernel<0, 16>,
                          (const void*)istft_kernel<2, 16>, (const void*)istft_kernel<2, 8>,
                          (const void*)istft_kernel<1, 16>, (const void*)istft_kernel<0, 8>, (const void*)istft_kernel<1, 8>,
-                         (const void*)istft_kernel<3, 16>, (const void*)istft_kernel<3, 8>};
+                         (const void*)istft_kernel<3, 16>, (const void*)istft_kernel<3, 8>,
+                         (const void*)istft_kernel<4, 16>, (const void*)istft_kernel<4, 8>, (const void*)stft_fwd_kernel<16, 2>,
+                         (const void*)stft_fwd_kernel<8, 2>};
     for (const void* f : big)
         if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds) != hipSuccess) return ADVH_ELAUNCH;
     int rc = advh_init_rest();
@@ -539,7 +574,7 @@ extern "C" int advh_stft_forward(const float* wave, int64_t wave_stride, int n_i
     if (!wave || n_in <= 0 || wave_stride < (n_in < L ? n_in : L)) return ADVH_EINVAL;
     const int FB = g_stft_fb;
     dim3 grid((T + FB - 1) / FB, B);
-    const AdjArgs none = {nullptr, nullptr, 0, 0, 0, 0};
+    const AdjArgs none = {nullptr, nullptr, 0, 0, 0, 0, RowMap{0, 1, 1, 0}};
     if (FB == 8)
         hipLaunchKernelGGL((stft_fwd_kernel<8, 0>), grid, dim3(THREADS), lds_rows_bytes(8), (hipStream_t)stream, wave,     // the plain forward stages no samples: rows only
                            (long)wave_stride, n_in, L, hop, win, window, X, mag, phase, T, none);
@@ -560,7 +595,7 @@ extern "C" int advh_istft_masked_bwd(const float* g_wave, int64_t g_stride, cons
     if (which != 0 && which != 1) return ADVH_EINVAL;
     const int FB = g_stft_fb;
     dim3 grid((Tm + FB - 1) / FB, B);
-    const AdjArgs adj = {mask, dmask, Fm, Tm, mode, which};
+    const AdjArgs adj = {mask, dmask, Fm, Tm, mode, which, RowMap{0, 1, 1, 0}};
     float* magp = const_cast<float*>(mag);
     float* php = const_cast<float*>(phase);
     if (FB == 8)
@@ -574,7 +609,8 @@ extern "C" int advh_istft_masked_bwd(const float* g_wave, int64_t g_stride, cons
 
 static int launch_istft(int src, const float* a, const float* ph, const float* mask, int Fm, int Tm, int mode,
                         float* o0, float* o1, int64_t ws, int B, int T, int L, int hop, int win,
-                        const float* window, advh_stream_t stream, int nbands = 0, int64_t zstride = 0) {
+                        const float* window, advh_stream_t stream, int nbands = 0, int64_t zstride = 0,
+                        RowMap rm = RowMap{0, 1, 1, 0}) {
     int rc = check_frame_args(B, T, L, hop, win);
     if (rc) return rc;
     const int R = (win + hop - 1) / hop;
@@ -593,10 +629,11 @@ static int launch_istft(int src, const float* a, const float* ph, const float* m
     dim3 grid(nG, B, nz);
 #define ISTFT_LAUNCH(SRC_, FB_)                                                                                          \
     hipLaunchKernelGGL((istft_kernel<SRC_, FB_>), grid, dim3(THREADS), lds_rows_bytes(FB_), (hipStream_t)stream, a, ph,  \
-                       mask, Fm, Tm, mode, which0, p0, p1, (long)ws, T, L, hop, win, R, window, (long)zstride)
+                       mask, Fm, Tm, mode, which0, p0, p1, (long)ws, T, L, hop, win, R, window, (long)zstride, rm)
     if (src == 0) { if (FB == 8) ISTFT_LAUNCH(0, 8); else ISTFT_LAUNCH(0, 16); }
     else if (src == 1) { if (FB == 8) ISTFT_LAUNCH(1, 8); else ISTFT_LAUNCH(1, 16); }
     else if (src == 3) { if (FB == 8) ISTFT_LAUNCH(3, 8); else ISTFT_LAUNCH(3, 16); }
+    else if (src == 4) { if (FB == 8) ISTFT_LAUNCH(4, 8); else ISTFT_LAUNCH(4, 16); }
     else { if (FB == 8) ISTFT_LAUNCH(2, 8); else ISTFT_LAUNCH(2, 16); }
 #undef ISTFT_LAUNCH
     return hipGetLastError() == hipSuccess ? ADVH_OK : ADVH_ELAUNCH;
@@ -618,6 +655,60 @@ extern "C" int advh_istft_masked_c64(const float* spec, const float* mask, int F
     if (!spec || !mask || wave_stride < L || Fm <= 0 || Tm <= 0 || Fm > NBIN || Tm > T) return ADVH_EINVAL;
     if (mode != ADVH_MASK_LINEAR && mode != ADVH_MASK_LOG1P) return ADVH_EINVAL;
     return launch_istft(3, spec, nullptr, mask, Fm, Tm, mode, wave_in, wave_out, wave_stride, B, T, L, hop, win, window, stream);
+}
+
+// The row-mapped pair: arguments are checked before any HIP call; a launch covers at most 65535 rows (grid y), more rows go out
+// in slices with row0 advanced.
+static int check_rows_args(const void* spec, const void* mask, bool need_mask, const void* io, int64_t stride, int Fm, int Tm, int mode,
+                           int rows, int64_t row0, int clip_major, int S, int B, int T, int L) {
+    if (!spec || !io || rows <= 0 || row0 < 0 || B <= 0 || S <= 0 || (clip_major != 0 && clip_major != 1)) return ADVH_EINVAL;
+    if (L <= 0 || stride < L || Fm <= 0 || Tm <= 0 || Fm > NBIN || Tm > T) return ADVH_EINVAL;
+    if (mode != ADVH_MASK_LINEAR && mode != ADVH_MASK_LOG1P) return ADVH_EINVAL;
+    if (need_mask && !mask) return ADVH_EINVAL;
+    return ADVH_OK;
+}
+constexpr int ROWS_PER_LAUNCH = 65535;
+
+extern "C" int advh_istft_masked_rows(const float* spec, const float* mask, int Fm, int Tm, int mode, float* wave, int64_t wave_stride,
+                                      int rows, int64_t row0, int clip_major, int S, int B, int T, int L, int hop, int win,
+                                      const float* window, advh_stream_t stream) {
+    int rc = check_rows_args(spec, mask, true, wave, wave_stride, Fm, Tm, mode, rows, row0, clip_major, S, B, T, L);
+    if (rc) return rc;
+    for (int r0 = 0; r0 < rows; r0 += ROWS_PER_LAUNCH) {
+        const int n = rows - r0 < ROWS_PER_LAUNCH ? rows - r0 : ROWS_PER_LAUNCH;
+        rc = launch_istft(4, spec, nullptr, mask + (long)r0 * Fm * Tm, Fm, Tm, mode, wave + (long)r0 * wave_stride, nullptr, wave_stride,
+                          n, T, L, hop, win, window, stream, 0, 0, RowMap{(long)row0 + r0, B, S, clip_major});
+        if (rc) return rc;
+    }
+    return ADVH_OK;
+}
+
+extern "C" int advh_istft_masked_rows_bwd(const float* g_wave, int64_t g_stride, const float* spec, const float* mask, int Fm, int Tm,
+                                          int mode, float* dmask, int rows, int64_t row0, int clip_major, int S, int B, int T, int L,
+                                          int hop, int win, const float* window, advh_stream_t stream) {
+    // `mask` is read in the log1p domain only; the linear adjoint takes NULL
+    int rc = check_rows_args(spec, mask, mode == ADVH_MASK_LOG1P, g_wave, g_stride, Fm, Tm, mode, rows, row0, clip_major, S, B, T, L);
+    if (rc) return rc;
+    if (!dmask) return ADVH_EINVAL;
+    rc = check_frame_args(B, T, L, hop, win);
+    if (rc) return rc;
+    const int FB = g_stft_fb;
+    float* X = const_cast<float*>(spec);
+    for (int r0 = 0; r0 < rows; r0 += ROWS_PER_LAUNCH) {
+        const int n = rows - r0 < ROWS_PER_LAUNCH ? rows - r0 : ROWS_PER_LAUNCH;
+        const long mo = (long)r0 * Fm * Tm;
+        const AdjArgs adj = {mask ? mask + mo : nullptr, dmask + mo, Fm, Tm, mode, 0, RowMap{(long)row0 + r0, B, S, clip_major}};
+        const float* gw = g_wave + (long)r0 * g_stride;
+        dim3 grid((Tm + FB - 1) / FB, n);
+        if (FB == 8)
+            hipLaunchKernelGGL((stft_fwd_kernel<8, 2>), grid, dim3(THREADS), lds_bytes(8, hop, win), (hipStream_t)stream, gw,
+                               (long)g_stride, L, L, hop, win, window, X, (float*)nullptr, (float*)nullptr, T, adj);
+        else
+            hipLaunchKernelGGL((stft_fwd_kernel<16, 2>), grid, dim3(THREADS), lds_bytes(16, hop, win), (hipStream_t)stream, gw,
+                               (long)g_stride, L, L, hop, win, window, X, (float*)nullptr, (float*)nullptr, T, adj);
+        if (hipGetLastError() != hipSuccess) return ADVH_ELAUNCH;
+    }
+    return ADVH_OK;
 }
 
 extern "C" int advh_istft_bandswap(const float* spec_a, const float* spec_b, int k0, int kw, int nbands, float* waves,
