@@ -791,6 +791,28 @@ int advh_attention_bwd_split(const void* qkv, int64_t qkv_lo, const void* dctx, 
                              int B, int T, int H, int heads, advh_stream_t stream);
 int advh_pool_logreg_bwd_split(const float* coef, const float* dlogit, float* dh, void* dh16, int64_t dh16_lo, int B, int T, int H,
                                advh_stream_t stream);
+/* Attention maps and rollout (csrc/attention_maps.hip; Abnar & Zuidema 2020, Chefer et al. 2021 -- restated from the publications,
+ * neither Captum nor the reference has them).  The attention kernels never write the T x T probabilities; this one recomputes them
+ * from the saved qkv [B*T][3H] (q | k | v) of one layer, on v_mfma_f32_16x16x4_f32 for both operand formats:
+ *   dctx == NULL : out = P = softmax(Q K^T / sqrt(d))            (rows are queries)
+ *   dctx != NULL : out = max(P * (dO V^T * dscale), 0)           (dO = the head's slice of dctx [B*T][H]; dscale = 1 / loss_scale)
+ * qkv_lo == 0: plain fp16 operands (dctx_lo must be 0 too); otherwise split plane pairs, lo planes qkv_lo / dctx_lo elements behind
+ * (positive multiples of 8; dctx_lo is ignored when dctx is NULL).  fuse: 0 = none, out [B][heads][T][T]; 1 = mean, 2 = max, 3 = min
+ * over heads, out [B][T][T] -- reduced inside the kernel in head order (no atomics, no per-head buffer: results are bit-identical
+ * from run to run and do not depend on B).  out is fp32 and every element is written; NaN in gives NaN out, and there is no range
+ * flag to raise.  T <= 256, head dim a multiple of 8 up to 128 (ADVH_EUNSUPPORTED otherwise); NULL qkv / out, B, T, heads <= 0,
+ * H % heads, a fuse outside [0, 3], a bad plane distance and a non-finite dscale return ADVH_EINVAL before any HIP call.  */
+int advh_attention_maps(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, float dscale, int fuse, float* out,
+                        int B, int T, int H, int heads, advh_stream_t stream);
+/* One rollout step on fp32 [B][T][T] matrices, row i of Y:
+ *   (alpha * X[i,:] + beta * sum_k M[i,k] X[k,:] + gamma * M[i,:]) / (normalize ? alpha + beta * sum_k M[i,k] : 1)
+ * plain rollout R <- rownorm(R + M R): (1, 1, 0, 1); gradient rollout on D = R - I, D <- D + A + A D: (1, 1, 1, 0).  The product runs
+ * on v_mfma_f32_16x16x4_f32 with X tiled through LDS.  T <= 256 (ADVH_EUNSUPPORTED above); NULL pointers, Y == X, Y == M and
+ * B, T <= 0 return ADVH_EINVAL before any HIP call.  */
+int advh_rollout_step(const float* M, const float* X, float* Y, float alpha, float beta, float gamma, int normalize, int B, int T,
+                      advh_stream_t stream);
+/* rel [B][T]: rel[b][j] = (1/T) sum_i X[b][i][j] (the classifier mean-pools over time), rows summed in order.  Same checks.  */
+int advh_rollout_relevance(const float* X, float* rel, int B, int T, advh_stream_t stream);
 /* fp32 -> split format on the device: dst[i] = hi, dst[dst_lo + i] = lo of src[i], i < n (csrc/device_math.h split_f32: saturates
  * and raises the sticky range flag above 65 504, NaN stays NaN unflagged; any n, the n % 4 tail converted one by one).  The per-step weight refresh of the training path (train_addvisor.py:376-378
  * steps the fp32 parameters with Adam; addvisor_hip/gemm.py GemmPlan.load_weights re-packs them).  src 16-byte aligned. */

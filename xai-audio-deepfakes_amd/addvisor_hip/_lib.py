@@ -163,6 +163,9 @@ SIGNATURES = {
     "advh_layernorm_bwd_split": (_i, [_p, _i, _i64, _p, _i, _i64, _p, _p, _i, _p, _p, _i64, _p, _p, _i64, _i, _i, _f, _i, _i, _p]),
     "advh_attention_bwd_split": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _i, _p]),
     "advh_pool_logreg_bwd_split": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    "advh_attention_maps": (_i, [_p, _i64, _p, _i64, _f, _i, _p, _i, _i, _i, _i, _p]),
+    "advh_rollout_step": (_i, [_p, _p, _p, _f, _f, _f, _i, _i, _i, _p]),
+    "advh_rollout_relevance": (_i, [_p, _p, _i, _i, _p]),
     "advh_posconv_gather_bwd_split": (_i, [_p, _p, _i64, _i, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "advh_w2v2_frontend_bwd_group_split": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p]),
 }

@@ -101,6 +101,37 @@ def draw_seed() -> int:
     return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
 
 
+HEAD_FUSIONS = {None: 0, "mean": 1, "max": 2, "min": 3}    # advh_attention_maps' fuse codes
+
+
+def check_head_fusion(head_fusion, allow_none: bool = True) -> int:
+    """``head_fusion`` of the attention methods as advh_attention_maps' ``fuse`` code.  Raises ValueError."""
+    ok = (None, "mean", "max", "min") if allow_none else ("mean", "max", "min")
+    if not (head_fusion is None or isinstance(head_fusion, str)) or head_fusion not in ok:
+        raise ValueError(f"head_fusion must be one of {ok}, not {head_fusion!r}")
+    return HEAD_FUSIONS[head_fusion]
+
+
+def check_attention_target(target, B: int):
+    """``target`` of the gradient-weighted attention methods: None or 1 explains ``+F``, 0 explains ``-F``, ``"predicted"``
+    explains ``sign(F(x_b)) F`` per clip, a ``[B]`` tensor of 0 / 1 picks per clip.  Returns None (``+F``), ``"predicted"`` or
+    the per-clip signs ``[B]`` (fp32, on the CPU).  Raises ValueError."""
+    if target is None:
+        return None
+    if isinstance(target, str):
+        if target != "predicted":
+            raise ValueError(f"target must be None, 0, 1, 'predicted' or a [B] tensor of 0 / 1, not {target!r}")
+        return target
+    if torch.is_tensor(target):
+        t = target.detach().cpu()
+        if t.dtype == torch.bool or t.dim() != 1 or t.shape[0] != B or not bool(((t == 0) | (t == 1)).all()):
+            raise ValueError(f"a target tensor must be [{B}] with values 0 / 1")
+        return t.to(torch.float32) * 2.0 - 1.0
+    if isinstance(target, bool) or not isinstance(target, (int, np.integer)) or target not in (0, 1):
+        raise ValueError(f"target must be None, 0, 1, 'predicted' or a [B] tensor of 0 / 1, not {target!r}")
+    return None if target == 1 else torch.full((B,), -1.0)
+
+
 def _dims(waves) -> Tuple[int, int]:
     if not torch.is_tensor(waves) or waves.dim() not in (1, 2):
         raise ValueError("waves must be a [B, L] (or [L]) tensor")
@@ -1742,6 +1773,107 @@ class HipAttribution:
         rel = torch.empty(B * T, dtype=torch.float32, device=attr.device)
         self.eg.layer_tap(attr.view(B * T, H), 1.0, want_out=False, row_sum=rel)
         return self.frames_to_wave(rel.view(B, T), L)
+
+    # ------------------------------------------------------------------ attention maps and rollout
+    # Abnar & Zuidema 2020 (rollout) and the self-attention rule of Chefer et al. 2021 (gradient rollout), restated from the
+    # publications: Captum has no class for them.  csrc/attention_maps.hip recomputes the T x T maps the attention kernels never write.
+    def check_attention_layer(self, layer, what: str = "layer") -> int:
+        """An encoder layer with an attention block: ``check_layer`` and ``layer < nl``.  Raises ValueError."""
+        nl = self.eg.emb.nl
+        l = check_layer(layer, nl)
+        if l >= nl:
+            raise ValueError(f"{what} must name an encoder layer with an attention block, 0 <= layer < {nl}; got {layer!r}")
+        return l
+
+    def _attention_args(self, waves) -> Tuple[int, int, int]:
+        """``(B, L, T)`` before any GPU work; the maps kernel takes ``T <= 256`` frames and head dims ``8, 16, .. 128``."""
+        B, L = _dims(waves)
+        cfg = self.eg.emb.cfg
+        T, dm = self.eg.emb._lengths(L)[-1], cfg.hidden_size // cfg.num_attention_heads
+        if T > 256 or dm % 8 or dm > 128:
+            raise ValueError(f"attention maps need T <= 256 frames and a head dim that is a multiple of 8 up to 128; got T = {T}, head dim {dm}")
+        return B, L, T
+
+    def _target_seed(self, spec, logits: torch.Tensor) -> Optional[torch.Tensor]:
+        if spec is None:
+            return None
+        if isinstance(spec, str):                              # "predicted": the sign of the forward's logit, on the device
+            return torch.sign(logits.view(-1))
+        return spec.to(self.emb.dev)
+
+    def _rollout_step(self, M, X, Y, alpha, beta, gamma, normalize):
+        B, T = X.shape[0], X.shape[1]
+        _lib.check(_lib.lib().advh_rollout_step(M.data_ptr(), X.data_ptr(), Y.data_ptr(), alpha, beta, gamma, int(normalize), B, T, _st()),
+                   "advh_rollout_step")
+
+    def _rollout_relevance(self, X: torch.Tensor) -> torch.Tensor:
+        B, T = X.shape[0], X.shape[1]
+        rel = torch.empty((B, T), dtype=torch.float32, device=X.device)
+        _lib.check(_lib.lib().advh_rollout_relevance(X.data_ptr(), rel.data_ptr(), B, T, _st()), "advh_rollout_relevance")
+        return rel
+
+    def attention_maps(self, waves, layer: int, head_fusion: Optional[str] = None, grad: bool = False, target=None):
+        """The attention maps of encoder layer ``layer`` (``0 <= layer < nl``), fp32, rows = queries: the probabilities
+        ``A = softmax(Q K^T / sqrt(d))``, or with ``grad=True`` the gradient-weighted maps ``(dF/dA * A)^+`` of Chefer et al. 2021
+        (``target``: None / 1 explains ``+F``, 0 ``-F``, ``"predicted"`` ``sign(F(x_b)) F``, or a ``[B]`` tensor of 0 / 1).
+        ``head_fusion=None``: ``[B, heads, T, T]``; ``"mean"`` / ``"max"`` / ``"min"`` reduce over heads: ``[B, T, T]``."""
+        l = self.check_attention_layer(layer)
+        fuse = check_head_fusion(head_fusion)
+        B, _, T = self._attention_args(waves)
+        if not isinstance(grad, bool):
+            raise ValueError(f"grad must be a bool, not {grad!r}")
+        if target is not None and not grad:
+            raise ValueError("target picks the explained output of the gradient-weighted maps: pass grad=True")
+        spec = check_attention_target(target, B)
+        x = self._prep(waves)
+        if not grad:
+            self.eg.forward(x, to_layer=l + 1)
+            return self._checked(self.eg.attention_probs(l, fuse), "attention map", "the forward pass produced a non-finite activation")
+        logits, _ = self.eg.forward(x)
+        heads = self.eg.cfg.num_attention_heads
+        out = torch.empty((1, B, T, T) if fuse else (1, B, heads, T, T), dtype=torch.float32, device=x.device)
+        self.eg.backward(self.loss_scale, seed=self._target_seed(spec, logits), to_layer=l, attention_maps=(out, fuse))
+        return self._checked(out[0], "attention map")
+
+    def attention_rollout(self, waves, head_fusion: str = "mean", start_layer: int = 0, return_joint: bool = False):
+        """Attention rollout (Abnar & Zuidema 2020): ``R = I``; for ``l = start_layer .. nl-1`` with ``M`` the head-fused
+        probabilities of layer ``l``, ``R <- rownorm(R + M R)`` (row ``i`` divided by ``1 + sum_k M[i,k]``; ``"mean"``: ``0.5 A +
+        0.5 I``).  The classifier mean-pools over time: the per-frame relevance is ``rel[b, j] = (1/T) sum_i R[b, i, j]``,
+        ``[B, T]`` fp32, rows summing to 1 (``frames_to_wave`` spreads it to the samples).  ``return_joint``: ``(rel, R [B, T, T])``."""
+        fuse = check_head_fusion(head_fusion, allow_none=False)
+        s0 = self.check_attention_layer(start_layer, "start_layer")
+        B, _, T = self._attention_args(waves)
+        x = self._prep(waves)
+        self.eg.forward(x)
+        R = torch.eye(T, dtype=torch.float32, device=x.device).expand(B, T, T).contiguous()
+        Y = torch.empty_like(R)
+        for l in range(s0, self.eg.emb.nl):
+            self._rollout_step(self.eg.attention_probs(l, fuse), R, Y, 1.0, 1.0, 0.0, True)
+            R, Y = Y, R
+        rel = self._checked(self._rollout_relevance(R), "attention rollout", "the forward pass produced a non-finite activation")
+        return (rel, R) if return_joint else rel
+
+    def attention_grad_rollout(self, waves, target=None, start_layer: int = 0, return_joint: bool = False):
+        """Gradient-weighted attention rollout (the self-attention rule of Chefer et al. 2021): ``Abar_l = mean_h (dF/dA_l^h *
+        A_l^h)^+`` and ``R <- R + Abar_l R`` from ``R = I``, carried as ``D = R - I`` (``D <- D + Abar_l + Abar_l D`` from 0: the
+        identity is never added and subtracted again).  One forward, one backward stopped at ``start_layer`` that writes every
+        layer's map on its way.  ``rel[b, j] = (1/T) sum_i D[b, i, j]``, ``[B, T]`` fp32 -- without the identity, which would add a
+        constant ``1/T`` that dwarfs the relevance.  ``target`` as ``attention_maps``; ``return_joint``: ``(rel, D [B, T, T])``."""
+        s0 = self.check_attention_layer(start_layer, "start_layer")
+        B, _, T = self._attention_args(waves)
+        spec = check_attention_target(target, B)
+        x = self._prep(waves)
+        logits, _ = self.eg.forward(x)
+        nl = self.eg.emb.nl
+        maps = torch.empty((nl - s0, B, T, T), dtype=torch.float32, device=x.device)
+        self.eg.backward(self.loss_scale, seed=self._target_seed(spec, logits), to_layer=s0, attention_maps=(maps, 1))
+        D = torch.zeros((B, T, T), dtype=torch.float32, device=x.device)
+        Y = torch.empty_like(D)
+        for l in range(s0, nl):
+            self._rollout_step(maps[l - s0], D, Y, 1.0, 1.0, 1.0, False)
+            D, Y = Y, D
+        rel = self._checked(self._rollout_relevance(D), "attention gradient rollout")
+        return (rel, D) if return_joint else rel
 
     # ------------------------------------------------------------------ neuron attributions (captum.attr.Neuron*)
     def _neuron_args(self, waves, layer, neuron):

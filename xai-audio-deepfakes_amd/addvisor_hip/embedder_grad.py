@@ -391,6 +391,32 @@ class EmbedderGrad:
             _lib.check(lib.advh_attention_bwd_f16(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), B, T, H, heads, st),
                        "advh_attention_bwd_f16")
 
+    def _att_maps(self, qkv, dctx, out, fuse, dscale, B, T, H, heads, st):
+        """advh_attention_maps on one layer's saved ``qkv`` (``dctx=None``: the probabilities) into the fp32 view ``out``."""
+        lo = lambda t: t.stride(0) if (self.split and t is not None) else 0
+        _lib.check(_lib.lib().advh_attention_maps(qkv.data_ptr(), lo(qkv), None if dctx is None else dctx.data_ptr(), lo(dctx), dscale,
+                                                  fuse, out.data_ptr(), B, T, H, heads, st), "advh_attention_maps")
+
+    def attention_probs(self, layer: int, fuse: int = 0) -> torch.Tensor:
+        """The attention probabilities ``softmax(Q K^T / sqrt(d))`` of encoder layer ``layer`` (``0 <= layer < nl``) at the clips
+        of the last pass, recomputed from its saved ``qkv`` (read-only: no state of the chain changes): ``[B, heads, T, T]``
+        fp32 (``fuse=0``) or fused over heads, ``[B, T, T]`` (``fuse`` 1 mean, 2 max, 3 min), rows = queries."""
+        l = check_layer(layer, self.emb.nl - 1)
+        if fuse not in (0, 1, 2, 3):
+            raise ValueError("fuse must be 0 (none), 1 (mean), 2 (max) or 3 (min)")
+        if getattr(self, "_last", None) is None:
+            raise RuntimeError("attention_probs() needs a forward pass first")
+        if self._start is not None and l < self._start:
+            raise ValueError(f"the last pass started at layer {self._start}: layer {l}'s attention did not run")
+        if self._stop is not None and l >= self._stop:
+            raise ValueError(f"the last pass stopped at layer {self._stop}: layer {l}'s attention did not run")
+        _, B, _, L = self._last
+        w = self._workspace(B, L)
+        T, H, heads = w["f"]["T"], self.cfg.hidden_size, self.cfg.num_attention_heads
+        out = torch.empty((B, T, T) if fuse else (B, heads, T, T), dtype=torch.float32, device=self.dev)
+        self._att_maps(w["qkv"][l], None, out, fuse, 1.0, B, T, H, heads, torch.cuda.current_stream().cuda_stream)
+        return out
+
     def neuron_values(self, v: torch.Tensor, box) -> torch.Tensor:
         """advh_neuron_values: ``out[r]`` = the sum over the selection box of the contiguous fp32 rows ``v [R, T, H]``."""
         R, T, H = v.shape
@@ -428,7 +454,7 @@ class EmbedderGrad:
 
     def backward(self, loss_scale: float = 4096.0, seed: Optional[torch.Tensor] = None, to_layer: Optional[int] = None,
                  from_layer: Optional[int] = None, neuron=None, layer_seed: Optional[torch.Tensor] = None,
-                 row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 row_scale: Optional[torch.Tensor] = None, attention_maps=None) -> torch.Tensor:
         """d logit / d wave for the clips of the last ``forward`` call: ``[B, n_in]`` fp32.  With ``seed [B]``
         (dL/d logit per clip) the result is dL/d wave instead (vector-Jacobian product: LMACLoss backward).
         ``to_layer=l``: the chain stops once ``d logit / d hidden_states[l]`` is in the residual-stream buffer and returns it,
@@ -442,7 +468,12 @@ class EmbedderGrad:
         (advh_layer_seed) -- and runs layers ``l-1 .. 0`` and the lower chain: ``[B, n_in]`` fp32, the vector-Jacobian product
         ``seed . d hidden_states[l] / d wave`` (divided by ``loss_scale``).  Nothing above the layer is launched.  It works after
         ``forward(...)`` with ``to_layer`` None or ``>= l``, also after a ``backward(to_layer=...)`` of the same pass (the saves
-        are read-only); at ``l == nl`` of a full-depth pre-LN model the seed passes through the final LayerNorm's backward."""
+        are read-only); at ``l == nl`` of a full-depth pre-LN model the seed passes through the final LayerNorm's backward.
+        ``attention_maps=(out, fuse)``: every layer ``l`` the chain passes also writes its gradient-weighted attention map
+        ``(dF/dA_l * A_l)^+`` (advh_attention_maps on the layer's saved ``qkv`` and the gradient at its attention context, divided
+        by ``loss_scale``) into ``out[l - to_layer]``: ``out`` is a contiguous CUDA fp32 tensor ``[layers, B, T, T]`` (``fuse`` 1
+        mean, 2 max, 3 min over heads) or ``[layers, B, heads, T, T]`` (``fuse=0``); ``layers`` is at most the number of layers the
+        chain runs, and the lowest ``layers`` of them write.  The maps only read the chain's buffers: the gradient is the same with and without them."""
         if getattr(self, "_last", None) is None:
             raise RuntimeError("backward() needs a forward pass first")
         _w = self._workspace(self._last[1], self._last[3])["f"]
@@ -465,6 +496,15 @@ class EmbedderGrad:
         C, nfe, nl = cfg.conv_dim, len(f["Ls"]), emb.nl
         da, db, d16, t16 = w["da"], w["db"], w["d16"], w["t16"]
         heads = cfg.num_attention_heads
+        maps = None
+        if attention_maps is not None:                     # checked before the first launch
+            maps, fuse = attention_maps
+            n_run = (nl if top is None else top) - stop
+            shape = (B, T, T) if fuse else (B, heads, T, T)
+            if fuse not in (0, 1, 2, 3) or not torch.is_tensor(maps) or not maps.is_cuda or maps.dtype != torch.float32 \
+                    or not maps.is_contiguous() or tuple(maps.shape[1:]) != shape or not 1 <= maps.shape[0] <= n_run:
+                raise ValueError(f"attention_maps must be (out, fuse): fuse in 0..3 and out a contiguous CUDA fp32 tensor "
+                                 f"[1..{n_run}] + {list(shape)}")
         if top is not None:                                # da / d16 = the seed at hidden_states[top]: every element written
             p = lambda t: None if t is None else t.data_ptr()
             src = None if layer_seed is None else layer_seed.contiguous()
@@ -495,6 +535,8 @@ class EmbedderGrad:
                 bl["ff1"].run(w["dI"], out_h=t16)                                             # d LN2(m)
                 self._ln_bwd(emb.ln2[l], w["m"][l], t16, M, out_f=db, out_h=d16, add=da)      # db = d m
                 bl["out"].run(d16, out_h=w["dctx"])
+                if maps is not None and l - stop < maps.shape[0]:
+                    self._att_maps(w["qkv"][l], w["dctx"], maps[l - stop], fuse, 1.0 / loss_scale, B, T, H, heads, st)
                 self._att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
                 bl["qkv"].run(w["dqkv"], out_h=t16)                                           # d LN1(x_l)
                 self._ln_bwd(emb.ln1[l], w["x"][l], t16, M, out_f=da, out_h=d16, add=db)      # da = d x_l
@@ -504,6 +546,8 @@ class EmbedderGrad:
                 bl["ff1"].run(w["dI"], out_f=da, resid=db)                                    # da = d m
                 self._ln_bwd(emb.ln1[l], w["s1"][l], da, M, out_f=db, out_h=d16)              # db = d s1
                 bl["out"].run(d16, out_h=w["dctx"])
+                if maps is not None and l - stop < maps.shape[0]:
+                    self._att_maps(w["qkv"][l], w["dctx"], maps[l - stop], fuse, 1.0 / loss_scale, B, T, H, heads, st)
                 self._att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
                 bl["qkv"].run(w["dqkv"], out_f=da, resid=db)                                  # da = d x_l
         if to_layer is not None:                                                              # da = d hidden_states[stop]
