@@ -813,6 +813,36 @@ int advh_rollout_step(const float* M, const float* X, float* Y, float alpha, flo
                       advh_stream_t stream);
 /* rel [B][T]: rel[b][j] = (1/T) sum_i X[b][i][j] (the classifier mean-pools over time), rows summed in order.  Same checks.  */
 int advh_rollout_relevance(const float* X, float* rel, int B, int T, advh_stream_t stream);
+/* Conservative propagation through the encoder (csrc/lrp.hip; Ali et al., ICML 2022, and the GELU identity rule of AttnLRP,
+ * Achtibat et al. 2024 -- restated from the publications, neither Captum nor the reference has them): gradient x input through a
+ * copy of the network in which one factor of each nonlinearity is a constant of the backward pass.
+ * AH-rule, ctx = sg(P) V: dqkv [B*T][3H] from the saved qkv [B*T][3H] (q | k | v) and dctx [B*T][H] of one layer, in the chain's
+ * own format -- zeros in the Q and K thirds, dV[k,:] = sum_q P[q,k] dO[q,:] per (clip, head) in the V third, P = softmax(Q K^T /
+ * sqrt(d)) recomputed on v_mfma_f32_16x16x4_f32 for both operand formats.  Every element of dqkv is written.  qkv_lo == 0: plain
+ * fp16 (dctx_lo and dqkv_lo must be 0 too); otherwise split plane pairs, lo planes qkv_lo / dctx_lo / dqkv_lo elements behind
+ * (positive multiples of 8), the V third through the checked conversion (|x| > 65 504 saturates and raises the sticky range flag, NaN
+ * stays NaN planes, unflagged).  No atomics: results are bit-identical from run to run and do not depend on B.  T <= 256, head dim a
+ * multiple of 8 up to 128 (ADVH_EUNSUPPORTED otherwise); NULL pointers, B, T, H, heads <= 0, H % heads and a bad plane distance
+ * return ADVH_EINVAL before any HIP call.  */
+int advh_attention_bwd_value(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, void* dqkv, int64_t dqkv_lo, int B,
+                             int T, int H, int heads, advh_stream_t stream);
+/* LN-rule, y = gamma (x - mean(x)) / sg(sigma) + beta: dx = u - mean_C(u) (+ add), u = gamma dy rstd, rows [M][C]; the encoder-side
+ * subset of advh_layernorm_bwd(_split)'s arguments (no gelu_fwd, dact_src or remap), the same row statistics recomputed from x in
+ * the same order (rstd is the same bits).  x / dy fp32 or fp16 (_split: plane pairs, x_lo / dy_lo / out_lo positive multiples of 4
+ * for every fp16-side tensor), add fp32 or NULL, at least one of out_f (fp32) / out_h.  C % 4 == 0, C <= 2048 (ADVH_EUNSUPPORTED
+ * above); NULL x / dy / gamma, no output, M, C <= 0 and a bad plane distance return ADVH_EINVAL before any HIP call.  */
+int advh_layernorm_bwd_frozen(const void* x, int x_is_f32, const void* dy, int dy_is_f32, const float* gamma, const float* add,
+                              float* out_f, void* out_h, int M, int C, float eps, advh_stream_t stream);
+int advh_layernorm_bwd_frozen_split(const void* x, int x_is_f32, int64_t x_lo, const void* dy, int dy_is_f32, int64_t dy_lo,
+                                    const float* gamma, const float* add, float* out_f, void* out_h, int64_t out_lo, int M, int C,
+                                    float eps, advh_stream_t stream);
+/* GELU identity rule, GELU(x) = x sg(Phi(x)): out[i] = d[i] * Phi(g1[i]), i < n, Phi = (1 + erf(x / sqrt 2)) / 2 from the kernels'
+ * fast_erf.  d_lo == 0: fp16 (g1_lo and out_lo must be 0 too); otherwise plane pairs (lo planes >= n elements behind) joined,
+ * multiplied in fp32 and re-split through the checked conversion.  out may be d.  Any n: eight elements per thread when every
+ * pointer and plane distance is 16-byte aligned, the n % 8 tail (or everything) one by one.  NULL pointers, n <= 0 and a bad
+ * plane distance return ADVH_EINVAL before any HIP call.  */
+int advh_gelu_identity_bwd(const void* d, int64_t d_lo, const void* g1, int64_t g1_lo, void* out, int64_t out_lo, int64_t n,
+                           advh_stream_t stream);
 /* fp32 -> split format on the device: dst[i] = hi, dst[dst_lo + i] = lo of src[i], i < n (csrc/device_math.h split_f32: saturates
  * and raises the sticky range flag above 65 504, NaN stays NaN unflagged; any n, the n % 4 tail converted one by one).  The per-step weight refresh of the training path (train_addvisor.py:376-378
  * steps the fp32 parameters with Adam; addvisor_hip/gemm.py GemmPlan.load_weights re-packs them).  src 16-byte aligned. */

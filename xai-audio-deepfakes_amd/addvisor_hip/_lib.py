@@ -166,6 +166,10 @@ SIGNATURES = {
     "advh_attention_maps": (_i, [_p, _i64, _p, _i64, _f, _i, _p, _i, _i, _i, _i, _p]),
     "advh_rollout_step": (_i, [_p, _p, _p, _f, _f, _f, _i, _i, _i, _p]),
     "advh_rollout_relevance": (_i, [_p, _p, _i, _i, _p]),
+    "advh_attention_bwd_value": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _i, _p]),
+    "advh_layernorm_bwd_frozen": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _f, _p]),
+    "advh_layernorm_bwd_frozen_split": (_i, [_p, _i, _i64, _p, _i, _i64, _p, _p, _p, _p, _i64, _i, _i, _f, _p]),
+    "advh_gelu_identity_bwd": (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p]),
     "advh_posconv_gather_bwd_split": (_i, [_p, _p, _i64, _i, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "advh_w2v2_frontend_bwd_group_split": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p]),
 }

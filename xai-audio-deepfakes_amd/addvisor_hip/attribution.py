@@ -47,7 +47,7 @@ import torch
 
 from . import _lib
 from .embedder import HipEmbedder
-from .embedder_grad import EmbedderGrad, check_layer  # noqa: F401  (check_layer(layer, nl): the Layer* methods' layer check)
+from .embedder_grad import EmbedderGrad, LrpRules, check_layer  # noqa: F401  (check_layer(layer, nl): the Layer* methods' layer check)
 
 
 def _st():
@@ -1874,6 +1874,35 @@ class HipAttribution:
             D, Y = Y, D
         rel = self._checked(self._rollout_relevance(D), "attention gradient rollout")
         return (rel, D) if return_joint else rel
+
+    # ------------------------------------------------------------------ conservative LRP for the transformer encoder
+    # Ali et al., ICML 2022 (LN-rule, AH-rule) and the GELU identity rule of AttnLRP (Achtibat et al. 2024), restated from the
+    # publications: Captum's LRP has no rule for LayerNorm, softmax attention or GELU, and the reference has no such method.
+    def transformer_lrp(self, waves, target=None, start_layer: int = 0, ln_rule: bool = True, attention_rule: bool = True,
+                        gelu_rule: str = "gradient", return_hidden: bool = False):
+        """Conservative propagation through the encoder: gradient x input at ``x = hidden_states[start_layer]`` of ``F~``, the
+        logit with -- in the layers ``>= start_layer`` and the final LayerNorm of a full-depth pre-LN model -- ``ln_rule``: every
+        LayerNorm's ``1/sigma`` held constant (``LN(x) = gamma (x - mean(x)) / sg(sigma) + beta``); ``attention_rule``: the
+        attention probabilities held constant (``ctx = sg(P) V``); ``gelu_rule="identity"``: the FFN's ``GELU(x) = x sg(Phi(x))``
+        (``"gradient"``, the default of Ali et al., leaves GELU's backward alone).  ``R[b, t, h] = x[b, t, h] * d(+-F~)/dx[b, t, h]``
+        and ``rel[b, t] = sum_h R[b, t, h]``, ``[B, T]`` fp32 (``frames_to_wave`` spreads it to the samples); ``return_hidden``:
+        ``(rel, R [B, T, H])``.  With all three rules on ``x -> F~`` is affine: on a model without biases ``sum_t rel[b] = +-F(x_b)``.
+        With all rules off it is ``layer_gradient_x_activation(waves, start_layer)`` summed over the channels.  ``target`` as
+        ``attention_maps``.  One forward, one backward stopped at ``start_layer`` (``EmbedderGrad.backward(rules=...)``)."""
+        s0 = self.check_attention_layer(start_layer, "start_layer")
+        rules = LrpRules(ln_rule, attention_rule, gelu_rule)
+        if not isinstance(return_hidden, bool):
+            raise ValueError(f"return_hidden must be a bool, not {return_hidden!r}")
+        B, _, T = self._attention_args(waves)
+        spec = check_attention_target(target, B)
+        x = self._prep(waves)
+        logits, _ = self.eg.forward(x)
+        g = self.eg.backward(self.loss_scale, seed=self._target_seed(spec, logits), to_layer=s0, rules=rules)
+        H = g.shape[2]
+        rel = torch.empty(B * T, dtype=torch.float32, device=x.device)
+        R = self.eg.layer_tap(g.view(B * T, H), 1.0, act=self.eg.hidden(s0).view(B * T, H), want_out=return_hidden, row_sum=rel)
+        rel = self._checked(rel.view(B, T), "transformer LRP")
+        return (rel, R.view(B, T, H)) if return_hidden else rel
 
     # ------------------------------------------------------------------ neuron attributions (captum.attr.Neuron*)
     def _neuron_args(self, waves, layer, neuron):

@@ -21,6 +21,7 @@ the residual-stream gradient is fp32.
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -74,6 +75,25 @@ def check_box(box, T: int, H: int) -> Tuple[int, int, int, int, int, int]:
     if not ok:
         raise ValueError(f"a selection box is (t0, t1, tstep, h0, h1, hstep) inside [0, {T}) x [0, {H}), non-empty, steps > 0; got {box!r}")
     return t0, t1, ts, h0, h1, hs
+
+
+GELU_RULES = ("gradient", "identity")
+
+
+@dataclass(frozen=True)
+class LrpRules:
+    """The conservative-propagation rules of ``EmbedderGrad.backward(rules=...)`` (Ali et al. 2022; csrc/lrp.hip): ``ln`` -- a
+    LayerNorm's ``1/sigma`` is a constant of the backward pass; ``attention`` -- the attention probabilities are; ``gelu`` --
+    ``"gradient"`` leaves the FFN's GELU backward as it is, ``"identity"`` (AttnLRP) makes ``Phi(x) = GELU(x)/x`` a constant."""
+    ln: bool = True
+    attention: bool = True
+    gelu: str = "gradient"
+
+    def __post_init__(self):
+        if not isinstance(self.ln, bool) or not isinstance(self.attention, bool):
+            raise ValueError(f"the ln and attention rules are bools; got {self.ln!r}, {self.attention!r}")
+        if not isinstance(self.gelu, str) or self.gelu not in GELU_RULES:
+            raise ValueError(f"the gelu rule must be one of {GELU_RULES}, not {self.gelu!r}")
 
 
 class EmbedderGrad:
@@ -391,6 +411,34 @@ class EmbedderGrad:
             _lib.check(lib.advh_attention_bwd_f16(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), B, T, H, heads, st),
                        "advh_attention_bwd_f16")
 
+    def _ln_bwd_frozen(self, ln, x, dy, M, out_f=None, out_h=None, add=None):
+        """advh_layernorm_bwd_frozen(_split): ``_ln_bwd`` with ``1/sigma`` a constant (the LN-rule)."""
+        st = torch.cuda.current_stream().cuda_stream
+        x32, dy32 = int(x.dtype == torch.float32), int(dy.dtype == torch.float32)
+        p = lambda t: None if t is None else t.data_ptr()
+        if self.split:
+            lo = lambda t, is32=0: 0 if (t is None or is32) else t.stride(0)
+            _lib.check(_lib.lib().advh_layernorm_bwd_frozen_split(
+                x.data_ptr(), x32, lo(x, x32), dy.data_ptr(), dy32, lo(dy, dy32), ln.g.data_ptr(), p(add), p(out_f), p(out_h), lo(out_h),
+                M, ln.C, self.cfg.layer_norm_eps, st), "advh_layernorm_bwd_frozen_split")
+            return
+        _lib.check(_lib.lib().advh_layernorm_bwd_frozen(
+            x.data_ptr(), x32, dy.data_ptr(), dy32, ln.g.data_ptr(), p(add), p(out_f), p(out_h), M, ln.C, self.cfg.layer_norm_eps, st),
+            "advh_layernorm_bwd_frozen")
+
+    def _att_bwd_value(self, qkv, dctx, dqkv, B, T, H, heads, st):
+        """advh_attention_bwd_value: ``_att_bwd`` with the probabilities a constant (the AH-rule): dV alone, dQ = dK = 0."""
+        lo = lambda t: t.stride(0) if self.split else 0
+        _lib.check(_lib.lib().advh_attention_bwd_value(qkv.data_ptr(), lo(qkv), dctx.data_ptr(), lo(dctx), dqkv.data_ptr(), lo(dqkv),
+                                                       B, T, H, heads, st), "advh_attention_bwd_value")
+
+    def _gelu_identity_bwd(self, d, g1, st):
+        """advh_gelu_identity_bwd in place: ``d <- d * Phi(g1)`` (the GELU identity rule)."""
+        lo = lambda t: t.stride(0) if self.split else 0
+        n = d.numel() // (2 if self.split else 1)
+        _lib.check(_lib.lib().advh_gelu_identity_bwd(d.data_ptr(), lo(d), g1.data_ptr(), lo(g1), d.data_ptr(), lo(d), n, st),
+                   "advh_gelu_identity_bwd")
+
     def _att_maps(self, qkv, dctx, out, fuse, dscale, B, T, H, heads, st):
         """advh_attention_maps on one layer's saved ``qkv`` (``dctx=None``: the probabilities) into the fp32 view ``out``."""
         lo = lambda t: t.stride(0) if (self.split and t is not None) else 0
@@ -454,7 +502,7 @@ class EmbedderGrad:
 
     def backward(self, loss_scale: float = 4096.0, seed: Optional[torch.Tensor] = None, to_layer: Optional[int] = None,
                  from_layer: Optional[int] = None, neuron=None, layer_seed: Optional[torch.Tensor] = None,
-                 row_scale: Optional[torch.Tensor] = None, attention_maps=None) -> torch.Tensor:
+                 row_scale: Optional[torch.Tensor] = None, attention_maps=None, rules: Optional[LrpRules] = None) -> torch.Tensor:
         """d logit / d wave for the clips of the last ``forward`` call: ``[B, n_in]`` fp32.  With ``seed [B]``
         (dL/d logit per clip) the result is dL/d wave instead (vector-Jacobian product: LMACLoss backward).
         ``to_layer=l``: the chain stops once ``d logit / d hidden_states[l]`` is in the residual-stream buffer and returns it,
@@ -473,7 +521,22 @@ class EmbedderGrad:
         ``(dF/dA_l * A_l)^+`` (advh_attention_maps on the layer's saved ``qkv`` and the gradient at its attention context, divided
         by ``loss_scale``) into ``out[l - to_layer]``: ``out`` is a contiguous CUDA fp32 tensor ``[layers, B, T, T]`` (``fuse`` 1
         mean, 2 max, 3 min over heads) or ``[layers, B, heads, T, T]`` (``fuse=0``); ``layers`` is at most the number of layers the
-        chain runs, and the lowest ``layers`` of them write.  The maps only read the chain's buffers: the gradient is the same with and without them."""
+        chain runs, and the lowest ``layers`` of them write.  The maps only read the chain's buffers: the gradient is the same with and without them.
+        ``rules`` (an ``LrpRules``; None: the plain gradient, every launch as without the argument): the encoder layers the chain
+        runs, and the final LayerNorm of a full-depth pre-LN model, propagate conservatively (Ali et al. 2022; csrc/lrp.hip) --
+        ``ln``: the LayerNorm backwards hold ``1/sigma`` constant; ``attention``: the attention backward holds the probabilities
+        constant (``dV = P^T dO``, ``dQ = dK = 0``); ``gelu="identity"``: the FFN's GELU backward multiplies by ``Phi(g1)``
+        instead of ``GELU'(g1)``.  The chain below the encoder has no rules: ``to_layer`` is required, and ``rules`` does not
+        combine with ``from_layer`` (ValueError before any launch).  It combines with ``attention_maps``, which only reads."""
+        if rules is not None:
+            if not isinstance(rules, LrpRules):
+                raise ValueError(f"rules must be an LrpRules or None, not {rules!r}")
+            if from_layer is not None:
+                raise ValueError("rules does not combine with from_layer: the chain below a layer's seed has no propagation rules")
+            if to_layer is None:
+                raise ValueError("backward(rules=...) needs to_layer: the positional convolution, the feature encoder and the "
+                                 "waveform kernels have no propagation rules")
+            check_layer(to_layer, self.emb.nl)
         if getattr(self, "_last", None) is None:
             raise RuntimeError("backward() needs a forward pass first")
         _w = self._workspace(self._last[1], self._last[3])["f"]
@@ -525,30 +588,41 @@ class EmbedderGrad:
             else:
                 _lib.check(lib.advh_pool_logreg_bwd(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(), B, T, H, st),
                            "advh_pool_logreg_bwd")
+        # the rules swap a launch for its conservative form (csrc/lrp.hip); rules=None is the plain chain, launch for launch
+        ln_bwd = self._ln_bwd_frozen if (rules is not None and rules.ln) else self._ln_bwd
+        att_bwd = self._att_bwd_value if (rules is not None and rules.attention) else self._att_bwd
+        gelu_id = rules is not None and rules.gelu == "identity"
+
+        def ff2_bwd(bl, l):                                                                   # d16 -> w["dI"] = d(pre-GELU)
+            if gelu_id:
+                bl["ff2"].run(d16, out_h=w["dI"], dact_src=None)
+                self._gelu_identity_bwd(w["dI"], w["g1"][l], st)
+            else:
+                bl["ff2"].run(d16, out_h=w["dI"], dact_src=w["g1"][l])
         if self._final_ln and stop < nl and top == nl:
-            self._ln_bwd(emb.enc_ln, w["x"][nl], da, M, out_f=db, out_h=d16)
+            ln_bwd(emb.enc_ln, w["x"][nl], da, M, out_f=db, out_h=d16)
             da, db = db, da
         for l in range(top - 1, stop - 1, -1):
             bl = w["layers"][l]
             if self.stable:                                # da = d x_{l+1} (fp32), d16 its fp16 copy
-                bl["ff2"].run(d16, out_h=w["dI"], dact_src=w["g1"][l])
+                ff2_bwd(bl, l)
                 bl["ff1"].run(w["dI"], out_h=t16)                                             # d LN2(m)
-                self._ln_bwd(emb.ln2[l], w["m"][l], t16, M, out_f=db, out_h=d16, add=da)      # db = d m
+                ln_bwd(emb.ln2[l], w["m"][l], t16, M, out_f=db, out_h=d16, add=da)            # db = d m
                 bl["out"].run(d16, out_h=w["dctx"])
                 if maps is not None and l - stop < maps.shape[0]:
                     self._att_maps(w["qkv"][l], w["dctx"], maps[l - stop], fuse, 1.0 / loss_scale, B, T, H, heads, st)
-                self._att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
+                att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
                 bl["qkv"].run(w["dqkv"], out_h=t16)                                           # d LN1(x_l)
-                self._ln_bwd(emb.ln1[l], w["x"][l], t16, M, out_f=da, out_h=d16, add=db)      # da = d x_l
+                ln_bwd(emb.ln1[l], w["x"][l], t16, M, out_f=da, out_h=d16, add=db)            # da = d x_l
             else:
-                self._ln_bwd(emb.ln2[l], w["s2"][l], da, M, out_f=db, out_h=d16)              # db = d s2
-                bl["ff2"].run(d16, out_h=w["dI"], dact_src=w["g1"][l])                        # d(pre-GELU)
+                ln_bwd(emb.ln2[l], w["s2"][l], da, M, out_f=db, out_h=d16)                    # db = d s2
+                ff2_bwd(bl, l)                                                                # d(pre-GELU)
                 bl["ff1"].run(w["dI"], out_f=da, resid=db)                                    # da = d m
-                self._ln_bwd(emb.ln1[l], w["s1"][l], da, M, out_f=db, out_h=d16)              # db = d s1
+                ln_bwd(emb.ln1[l], w["s1"][l], da, M, out_f=db, out_h=d16)                    # db = d s1
                 bl["out"].run(d16, out_h=w["dctx"])
                 if maps is not None and l - stop < maps.shape[0]:
                     self._att_maps(w["qkv"][l], w["dctx"], maps[l - stop], fuse, 1.0 / loss_scale, B, T, H, heads, st)
-                self._att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
+                att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
                 bl["qkv"].run(w["dqkv"], out_f=da, resid=db)                                  # da = d x_l
         if to_layer is not None:                                                              # da = d hidden_states[stop]
             return self.layer_tap(da.view(B, T, H), 1.0 / loss_scale)

@@ -195,7 +195,9 @@ def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, n
     (``HipAttribution.layer_relevance``).  The neuron methods attribute the unit(s) ``neuron`` (a ``(t, h)`` tuple of ints or
     slices) of that layer to the waveform directly.  ``"attention_rollout"`` / ``"attention_grad_rollout"`` roll the encoder's
     attention maps out from ``layer`` (the ``start_layer``, default 0; checked here, before any GPU work) and spread the
-    per-frame relevance to the samples (``HipAttribution.frames_to_wave``); NoiseTunnel may wrap them."""
+    per-frame relevance to the samples (``HipAttribution.frames_to_wave``); NoiseTunnel may wrap them.  ``"transformer_lrp"``
+    (conservative propagation, Ali et al. 2022: ``HipAttribution.transformer_lrp`` with its default rules) takes ``layer`` as its
+    ``start_layer`` the same way; it stands for no Captum class."""
     if method in ("neuron_gradient", "neuron_integrated_gradients"):
         if nt_type is not None:
             raise ValueError("NoiseTunnel does not wrap the neuron methods")
@@ -213,11 +215,12 @@ def _explainer(att, method, n_steps=50, window=1600, stride=800, nt_type=None, n
             return lambda w: att.layer_relevance(att.layer_integrated_gradients(w, l, n_steps=n_steps), w.shape[-1])
         return lambda w: att.layer_relevance(att.layer_gradient_x_activation(w, l), w.shape[-1])
     s0 = 0
-    if method in ("attention_rollout", "attention_grad_rollout"):
-        s0 = att.check_attention_layer(0 if layer is None else layer, "layer (the rollout's start_layer)")
+    if method in ("attention_rollout", "attention_grad_rollout", "transformer_lrp"):
+        s0 = att.check_attention_layer(0 if layer is None else layer, "layer (the method's start_layer)")
     fn = {"saliency": att.saliency, "input_x_gradient": att.input_x_gradient,
           "attention_rollout": lambda w: att.frames_to_wave(att.attention_rollout(w, start_layer=s0), w.shape[-1]),
           "attention_grad_rollout": lambda w: att.frames_to_wave(att.attention_grad_rollout(w, start_layer=s0), w.shape[-1]),
+          "transformer_lrp": lambda w: att.frames_to_wave(att.transformer_lrp(w, start_layer=s0), w.shape[-1]),
           "integrated_gradients": lambda w: att.integrated_gradients(w, n_steps=n_steps),
           "occlusion": lambda w: att.occlusion(w, window, stride),
           "shapley_value_sampling": lambda w: att.shapley_value_sampling(w, feature_mask=_segments(w, window)),
@@ -244,6 +247,8 @@ def explain_waves(model, waves, method="input_x_gradient", n_steps=50, window=16
     ``method="attention_rollout"`` (Abnar & Zuidema 2020) / ``"attention_grad_rollout"`` (the self-attention rule of Chefer et al.
     2021) roll the encoder's head-fused attention maps out from ``layer`` (default 0) and mask the waveform with each frame's
     relevance (``HipAttribution.attention_rollout`` / ``attention_grad_rollout``).
+    ``method="transformer_lrp"`` (conservative propagation, Ali et al. 2022) masks it with gradient x input of the locally
+    linearised encoder at ``hidden_states[layer]`` (default 0), summed over the channels (``HipAttribution.transformer_lrp``).
     ``nt_type`` ("smoothgrad", "smoothgrad_sq", "vargrad") wraps the method in NoiseTunnel over ``nt_samples`` noisy copies
     of each clip; ``stdevs`` is the noise's standard deviation in waveform units (Captum's default of 1.0 would drown a
     waveform in [-1, 1]).  Returns ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``."""
@@ -286,7 +291,7 @@ def attack_waves(model, waves, labels, attack="pgd", explain=None, **attack_kwar
     ``step_num``, default 2e-3 / 5e-4 / 5), passing ``attack_kwargs`` (``loss_func``, ``lower_bound``, ``upper_bound`` go to the
     constructor, the rest to ``perturb``).  Returns ``{"adversarial": [B, L], "predictions": [B, 1], "adversarial_predictions":
     [B, 1]}`` (both from one forward over ``cat([x, x_adv])``) and, when ``explain`` names an ``explain_waves`` method (its
-    defaults, the attention rollouts included), ``"explanation_shift" [B]``: ``||a(x_adv) - a(x)||_2 / ||a(x)||_2`` (a zero norm counts as 1), reduced on the
+    defaults, the attention rollouts and ``"transformer_lrp"`` included), ``"explanation_shift" [B]``: ``||a(x_adv) - a(x)||_2 / ||a(x)||_2`` (a zero norm counts as 1), reduced on the
     device by sensitivity_max's row-norm kernels."""
     if attack not in ATTACKS:
         raise ValueError(f"attack must be one of {ATTACKS}, not {attack!r}")
@@ -317,8 +322,8 @@ def compute_camptum_saliency_metrics(model, metadata_path, target_class=None, ro
                                      method="input_x_gradient", batch_size=8, nt_type=None, nt_samples=5, stdevs=0.01,
                                      explanation_metrics=False):
     """captum_saliency.py:112-212 (name kept as in the reference); prints faithfulness and fidelity.  ``nt_type`` runs the
-    masks of NoiseTunnel over ``method`` (``explain_waves``: any of its waveform methods, ``"attention_rollout"`` and
-    ``"attention_grad_rollout"`` included).  ``explanation_metrics=True`` also prints the means of
+    masks of NoiseTunnel over ``method`` (``explain_waves``: any of its waveform methods, ``"attention_rollout"``,
+    ``"attention_grad_rollout"`` and ``"transformer_lrp"`` included).  ``explanation_metrics=True`` also prints the means of
     Captum's infidelity and sensitivity_max of the attributions (``score_explanations``)."""
     model.eval()
     wav_paths = extract_wavs(metadata_path)
