@@ -32,6 +32,25 @@ def _req(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _window(window, win: int, device) -> Optional[torch.Tensor]:
+    """The analysis / synthesis window of an STFT / ISTFT call: ``None`` (rectangular) or fp32, on ``device`` (the signal's or
+    spectrogram's), contiguous, ``win`` elements.  The kernels index it as ``window[0 .. win)`` through a raw pointer, so anything
+    else is refused here, before any library call."""
+    if window is None:
+        return None
+    if not isinstance(window, torch.Tensor):
+        raise ValueError(f"window must be a tensor or None, got {type(window).__name__}")
+    if window.dtype != torch.float32:
+        raise ValueError(f"window must be {torch.float32}, got {window.dtype}")
+    if window.device != device:
+        raise ValueError(f"window must be on {device}, got {window.device}")
+    if not window.is_contiguous():
+        raise ValueError("window must be contiguous")
+    if window.numel() != win:
+        raise ValueError(f"window must have win = {win} elements, got {window.numel()}")
+    return window
+
+
 def stft_forward(wave: torch.Tensor, length: int, hop: int = 322, win: int = 644,
                  window: Optional[torch.Tensor] = None, want_complex: bool = True,
                  want_mag: bool = True, want_phase: bool = True
@@ -49,10 +68,7 @@ def stft_forward(wave: torch.Tensor, length: int, hop: int = 322, win: int = 644
     X = torch.empty((B, NBIN, T, 2), dtype=torch.float32, device=dev) if want_complex else None
     mag = torch.empty((B, NBIN, T), dtype=torch.float32, device=dev) if want_mag else None
     ph = torch.empty((B, NBIN, T), dtype=torch.float32, device=dev) if want_phase else None
-    if window is not None:
-        window = _req(window, torch.float32, "window")
-        if window.numel() != win:
-            raise ValueError("window must have `win` elements")
+    window = _window(window, win, dev)
     rc = _lib.lib().advh_stft_forward(wave.data_ptr(), wave.stride(0), n_in, B, length, hop, win, _ptr(window),
                                       _ptr(X), _ptr(mag), _ptr(ph), T, _stream())
     _lib.check(rc, "advh_stft_forward")
@@ -84,6 +100,7 @@ def istft_masked(mag: torch.Tensor, phase: torch.Tensor, mask: Optional[torch.Te
         raise ValueError("domain='none' has no mask-out signal")
     if T != 1 + length // hop:
         raise ValueError("T does not match length // hop + 1")
+    window = _window(window, win, mag.device)
     w_in = torch.empty((B, length), dtype=torch.float32, device=mag.device) if want_in else None
     w_out = torch.empty((B, length), dtype=torch.float32, device=mag.device) if want_out else None
     rc = _lib.lib().advh_istft_masked(mag.data_ptr(), phase.data_ptr(), _ptr(mask) if mode else None, Fm, Tm, mode,
@@ -109,6 +126,7 @@ def istft_masked_c64(spec: torch.Tensor, mask: torch.Tensor, length: int, domain
         raise ValueError("mask must be [B, Fm<=513, Tm<=T]")
     if T != 1 + length // hop:
         raise ValueError("T does not match length // hop + 1")
+    window = _window(window, win, spec.device)
     w_in = torch.empty((B, length), dtype=torch.float32, device=spec.device) if want_in else None
     w_out = torch.empty((B, length), dtype=torch.float32, device=spec.device) if want_out else None
     rc = _lib.lib().advh_istft_masked_c64(sr.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[2], mode, _ptr(w_in), _ptr(w_out),
@@ -139,6 +157,7 @@ def istft_masked_bwd(g_wave: torch.Tensor, mag: torch.Tensor, phase: torch.Tenso
     if T != 1 + length // hop:
         raise ValueError("T does not match length // hop + 1")
     mode = {"linear": 1, "log1p": 2}[domain]
+    window = _window(window, win, mag.device)
     dmask = torch.empty_like(mask)
     rc = _lib.lib().advh_istft_masked_bwd(g_wave.data_ptr(), length, mag.data_ptr(), phase.data_ptr(), mask.data_ptr(),
                                           mask.shape[1], mask.shape[2], mode, int(which), dmask.data_ptr(), B, T, length, hop,
@@ -175,6 +194,7 @@ def istft_masked_rows(spec: torch.Tensor, mask: torch.Tensor, length: int, domai
     _lib.init()
     mask = _req(mask, torch.float32, "mask")
     sr, B, T = _rows_args(spec, mask, clip_major, S, row0, length, hop)
+    window = _window(window, win, spec.device)
     mode = {"linear": 1, "log1p": 2}[domain]
     rows = mask.shape[0]
     wave = torch.empty((rows, length), dtype=torch.float32, device=spec.device)
@@ -196,6 +216,7 @@ def istft_masked_rows_bwd(g_wave: torch.Tensor, spec: torch.Tensor, mask: torch.
         raise ValueError("g_wave must be [rows, length], one row per mask row")
     length = g_wave.shape[1]
     sr, B, T = _rows_args(spec, mask, clip_major, S, row0, length, hop, g_wave)
+    window = _window(window, win, spec.device)
     mode = {"linear": 1, "log1p": 2}[domain]
     dmask = torch.empty_like(mask)
     rc = _lib.lib().advh_istft_masked_rows_bwd(g_wave.data_ptr(), length, sr.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[2],
@@ -222,8 +243,7 @@ def istft_bandswap(spec_a: torch.Tensor, spec_b: torch.Tensor, length: int, k0: 
     B, _, T = spec_a.shape
     if T != 1 + length // hop:
         raise ValueError("T does not match length // hop + 1")
-    if window is not None:
-        window = _req(window, torch.float32, "window")
+    window = _window(window, win, spec_a.device)
     a = torch.view_as_real(spec_a.contiguous())
     b = torch.view_as_real(spec_b.contiguous())
     out = torch.empty((nbands, B, length), dtype=torch.float32, device=spec_a.device)
@@ -245,6 +265,7 @@ def istft_complex(spec: torch.Tensor, length: int, hop: int = 322, win: int = 64
     B, _, T, _ = sr.shape
     if T != 1 + length // hop:
         raise ValueError("T does not match length // hop + 1")
+    window = _window(window, win, spec.device)
     out = torch.empty((B, length), dtype=torch.float32, device=spec.device)
     rc = _lib.lib().advh_istft_c64(sr.data_ptr(), out.data_ptr(), length, B, T, length, hop, win, _ptr(window), _stream())
     _lib.check(rc, "advh_istft_c64")
