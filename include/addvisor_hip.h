@@ -179,8 +179,9 @@ typedef struct advh_gemm_desc {
     const void* dact_src;
     /* wide = 1: the rows of W are packed permuted inside every 32-row block -- packed row R holds output channel
        32 (R>>5) + 8 ((R>>2)&3) + 4 ((R>>4)&1) + (R&3) -- so that a lane's accumulators are 8 consecutive channels and
-       the epilogue moves 16 bytes of fp16 per lane.  Requires N, n_div, o_c0 and every o_s* stride % 8 == 0
-       (checked).  wide = 0: packed row R is channel R.                                                     */
+       the epilogue moves 16 bytes of fp16 per lane.  Requires N, n_div, o_c0 and every o_s* stride (o_sB, o_sH, o_sW, o_sNhi,
+       o_sNhh, o_sZ, o_sZ2) % 8 == 0: checked on the host, ADVH_EINVAL otherwise (a lane stores 8 columns, so N % 8 == 4 would
+       write past N).  wide = 0: packed row R is channel R.                                                 */
     int32_t wide;
     /* row pitch of W in elements; 0 = Ktot.  Lets a launch (or grid-z batch) reduce over a K-slice of a wider
        K-major matrix: the split-K weight-gradient GEMMs of the U-Net training step.                       */
@@ -192,8 +193,8 @@ typedef struct advh_gemm_desc {
        q = n / n_div, the offset is (q / n_sub)*o_sNhh + (q % n_sub)*o_sNhi instead of q*o_sNhi; n_sub <= 1 = off. */
     int32_t n_sub;
     int64_t o_sNhh;
-    /* two-level grid-z batch (256-thread kernels only; the other tiles return ADVH_EUNSUPPORTED): with nz_lo > 1 the
-       batch index z in [0, nz) splits into zh = z / nz_lo, zw = z % nz_lo and the operands advance by
+    /* two-level grid-z batch (every tile, the 512-thread ones included: they are instances of the same kernel): with nz_lo > 1
+       the batch index z in [0, nz) splits into zh = z / nz_lo, zw = z % nz_lo and the operands advance by
        a_sZ*zh + a_sZ2*zw (chunks) and o_sZ*zh + o_sZ2*zw (elements); W and bias still advance by w_sZ*z, bias_sZ*z.
        The four output-parity classes of a fused ConvTranspose2d(2,2)+Conv2d launch are such a batch.
        z_inner = 1: the nz batches of one tile are dispatched next to each other (z fastest in the workgroup order)
@@ -204,7 +205,10 @@ typedef struct advh_gemm_desc {
     /* plain = 1 (requires ktab_identity and one source): every row m in [0, M) -- valid or not -- may be read at chunk
        a_c0[0] + m * a_sW[0] (+ z * a_sZ[0]), K contiguous chunks; a_sB / a_sH / the window are then used for the OUTPUT
        addressing only.  Lets the 128x128 tile run its affine-row loader (Linear layers, feature-encoder Conv1d: the
-       caller guarantees that the last row's K chunks are inside the allocation).                                  */
+       caller guarantees that the last row's K chunks are inside the allocation).  The fp16 tiles without an affine-row
+       loader (256x64, 256x32 and the 512-thread ones; in split mode every tile has one) serve plain = 1 with the gathered
+       loader, which addresses valid rows by b*a_sB + h*a_sH + w*a_sW: a_sH must equal Wg*a_sW and a_sB must equal Hg*Wg*a_sW
+       (or the grid is one line / one item) so that both rules name the same chunk.                                 */
     int32_t plain;
     /* plain_out = 1 (with plain): every row is valid (the window is the whole grid), output row m starts at
        o_c0 + m * o_sW + the batch offset and the columns are one block (n_div >= N, no phases, no sub-pixel split):
@@ -215,7 +219,8 @@ typedef struct advh_gemm_desc {
        a_lo[s] chunks behind A_s, that of W w_lo elements behind W, that of out_h / out_h2 / a fp16 resid o_lo elements
        behind the hi plane, all addressed like the hi plane.  The kernel issues three MFMAs per fragment pair
        (Wh*Ah + (Wh*Al + Wl*Ah) * 2^-11, fp32 accumulate): the arithmetic class of the reference's fp32 layers.
-       Tiles: 128x128, 256x64, 256x32 (AUTO picks as for fp16); out_pre / dact_src are not supported.              */
+       Tiles: 128x128, 256x64, 256x32 (AUTO picks as for fp16; the 512-thread tiles return ADVH_EUNSUPPORTED); out_pre /
+       dact_src are plane pairs like out_h (the fp32-class gradient chain of the embedder uses them).               */
     int32_t split;
     int64_t a_lo[2];
     int64_t w_lo;

@@ -1104,6 +1104,11 @@ extern "C" int advh_gemm_f16(const advh_gemm_desc* d, int tile, advh_stream_t st
     if (d->n_div <= 0 || d->n_div % 4 || d->h0 < 0 || d->w0 < 0 || d->h1 > d->Hg || d->w1 > d->Wg || d->h0 >= d->h1 || d->w0 >= d->w1)
         return ADVH_EINVAL;
     if (d->act < ADVH_ACT_NONE || d->act > ADVH_ACT_LEAKY) return ADVH_EINVAL;
+    // wide: a lane moves 8 consecutive channels with 16-byte accesses, so the column count, the column block and every output
+    // offset must be multiples of 8 (N % 8 == 4 would store 4 columns past N)
+    if (d->wide && (d->N % 8 || d->n_div % 8 || d->o_c0 % 8 || d->o_sB % 8 || d->o_sH % 8 || d->o_sW % 8 || d->o_sNhi % 8 || d->o_sZ % 8 ||
+                    d->o_sNhh % 8 || d->o_sZ2 % 8))
+        return ADVH_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     // same rule as addvisor_hip/gemm.py pick_tile
     if (tile == ADVH_TILE_AUTO) tile = d->N > 64 ? ADVH_TILE_128x128 : (d->N > 32 ? ADVH_TILE_256x64 : ADVH_TILE_256x32);
