@@ -744,6 +744,57 @@ int advh_row_similarity(const float* rows_ptr, const float* x, int64_t row0, int
 int advh_lasso_cd(const double* X, const double* y, int S, int K, double alpha, double tol, int max_iter, double* coef, double* gap,
                   int* iters);
 
+/* Perturbation curves of an attribution map (csrc/attribution_curve.hip): the deletion / insertion curves of Petsiuk et al.
+ * (RISE, BMVC 2018, sec. 4.1) and the AOPC of Samek et al. (2017) in MoRF / LeRF order -- DeYoung et al.'s (2020)
+ * comprehensiveness / sufficiency -- restated from the papers (no Captum class exists).  Rows are [B][n] fp32; index[1 | B][n] in
+ * [0, K) is the feature of sample t; index == NULL is the identity (K == n, every sample its own feature).  All four entry points
+ * are deterministic: no atomics, a fixed order, bit-identical results from run to run.
+ *
+ * advh_feature_scores : score[b][k] = the fp32 sum, IN INCREASING t from 0.f, of attr[b][t] (use_abs: |attr[b][t]|) over the
+ *                       samples of feature k; mean != 0 divides once by the sample count (__fdiv_rn).  The order is the
+ *                       contract: a sequential fp32 replay on the host gives the same bits (so a lone -0 scores +0).  A feature
+ *                       with no sample in clip b scores -inf (last in MoRF, first in LeRF; the Python engine refuses such a
+ *                       mask).  Samples whose index is outside [0, K) belong to no feature.
+ * advh_feature_rank   : rank[b][k] (int32) = the number of features j of clip b that come before k.  descending != 0 (MoRF):
+ *                       j comes before k when s_j > s_k, or s_j == s_k && j < k; otherwise (LeRF): when s_j < s_k, or
+ *                       s_j == s_k && j < k.  -0 == +0, +-inf order as numbers; NaN scores are the caller's to refuse (they
+ *                       order as their bit patterns; the result is still a permutation).  Exact: every row of rank is a
+ *                       permutation of [0, K), any K >= 1.  K * K key comparisons per clip (counting rank over LDS tiles).
+ * advh_curve_points   : out[r] = curve row g = row0 + r ([rows][n]), step j = g / B of clip b = g % B (perturbation-major, as
+ *                       the ablation rows).  Sample t is switched when rank[b][index[t]] < counts[j].  mode 0 (deletion): a
+ *                       switched sample takes base[b or 0][t], the rest x[b][t]; mode 1 (insertion): a switched sample takes x,
+ *                       the rest base.  A feature index outside [0, K) writes NaN into that sample.  Rows g >= S1 * B copy
+ *                       x[g % B] (padding of a fixed-shape last chunk).  rows = 0 launches nothing.
+ * advh_curve_fold     : from fk [S1 * B] (the rows' fp32 logits), one thread per clip, steps in increasing j:
+ *                       y_j = fk[j * B + b], or 1 / (1 + expf(-fk)) with prob != 0; curve[b][j] = y_j; with f_j = counts[j] / K
+ *                       in fp64, accumulated in fp64 and rounded once to fp32:
+ *                         auc[b]  = sum_j (f_{j+1} - f_j) (y_j + y_{j+1}) / 2 / (f_last - f_0)
+ *                         aopc[b] = (1 / (S1 - 1)) sum_{j != ref} (y_ref - y_j),  ref = 0, or S1 - 1 with ref_last != 0
+ *                       (the row that equals x: step 0 of a deletion, the last step of an insertion).  S1 >= 2.
+ * counts [S1] int32 lives on the DEVICE: c_0 < c_1 < ... < c_{S1-1} inside [0, K].  Null pointers, non-positive sizes, K > n,
+ * B > 65535 (scores, rank), index_rows / base_rows not in {1, B}, index == NULL with K != n, a mode outside [0, 1] and an S1 that
+ * no strictly increasing counts inside [0, K] can have (S1 > K + 1; fold: S1 < 2) return ADVH_EINVAL before any HIP call.  The
+ * values of counts cannot be read before a HIP call: advh_curve_fold checks them on the device and writes NaN into auc and
+ * aopc when they are not strictly increasing inside [0, K]; the Python engine builds them on the host and refuses bad ones. */
+typedef struct advh_curve_desc {
+    const float* x;          /* [B][n] inputs                                                   */
+    const float* base;       /* [base_rows][n] baselines, base_rows = 1 or B                     */
+    const int32_t* index;    /* [index_rows][n] feature index, index_rows = 1 or B; NULL: identity */
+    const int32_t* rank;     /* [B][K] rank of each feature in each clip's order                 */
+    const int32_t* counts;   /* [S1] features switched at each step (device memory)              */
+    int64_t n;
+    int B, base_rows, index_rows;
+    int K;                   /* features                                                         */
+    int S1;                  /* steps of the curve (S + 1)                                       */
+    int mode;                /* 0: deletion, 1: insertion                                        */
+} advh_curve_desc;
+int advh_feature_scores(const float* attr, const int32_t* index, int index_rows, int B, int64_t n, int K, int use_abs, int mean,
+                        float* score, advh_stream_t stream);
+int advh_feature_rank(const float* score, int B, int K, int descending, int32_t* rank, advh_stream_t stream);
+int advh_curve_points(const advh_curve_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream);
+int advh_curve_fold(const float* fk, const int32_t* counts, int B, int S1, int K, int prob, int ref_last, float* curve, float* auc,
+                    float* aopc, advh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * fp32-class ("split") mode.  The reference computes the whole path in fp32 (addvisor.py:12-84,
  * transformers/models/wav2vec2/modeling_wav2vec2.py:254-802 under audioprocessor.py:69-77).  In this mode every tensor

@@ -94,6 +94,10 @@ SIGNATURES = {
     "advh_permutation_points": (_i, [_p, _i64, _i, _p, _p]),
     "advh_row_similarity": (_i, [_p, _p, _i64, _i, _i, _i64, _i, _f, _p, _p]),
     "advh_lasso_cd": (_i, [_p, _p, _i, _i, C.c_double, C.c_double, _i, _p, _p, _p]),
+    "advh_feature_scores": (_i, [_p, _p, _i, _i, _i64, _i, _i, _i, _p, _p]),
+    "advh_feature_rank": (_i, [_p, _i, _i, _i, _p, _p]),
+    "advh_curve_points": (_i, [_p, _i64, _i, _p, _p]),
+    "advh_curve_fold": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "advh_istft_masked_bwd": (_i, [_p, _i64, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "advh_istft_masked_rows": (_i, [_p, _p, _i, _i, _i, _p, _i64, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "advh_istft_masked_rows_bwd": (_i, [_p, _i64, _p, _p, _i, _i, _i, _p, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p]),

@@ -32,6 +32,11 @@ units, of ``hidden_states[l]`` to the waveform on the forward stopped at the lay
 ``captum.metrics.infidelity`` / ``sensitivity_max`` score any of them (``infidelity``, ``sensitivity_max``): the perturbed rows
 of each chunk of samples come from the same counter-based generator (or a Python perturb_func), and the per-row dot products,
 norms and per-clip folds run on csrc/attribution_metrics.hip.
+
+``perturbation_curve`` / ``curve_summary`` rank any of them on the scale the attribution literature uses: the deletion /
+insertion curves of Petsiuk et al. (2018) and the AOPC of Samek et al. (2017) in MoRF / LeRF / random order (restated from the
+papers; there is no Captum class).  Per-clip feature scores, a stable rank, the curve rows and the curve fold run on
+csrc/attribution_curve.hip; the rows go through the same forward seam as the perturbation attributions.
 """
 from __future__ import annotations
 
@@ -40,7 +45,7 @@ import inspect
 import itertools
 import math
 import warnings
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -926,6 +931,116 @@ def ablation_accumulate(d: AblationDesc, f0: torch.Tensor, fk: torch.Tensor, att
                "advh_ablation_accumulate")
 
 
+class CurveDesc(C.Structure):
+    """Mirror of ``advh_curve_desc`` (include/addvisor_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("base", C.c_void_p), ("index", C.c_void_p), ("rank", C.c_void_p), ("counts", C.c_void_p),
+                ("n", C.c_int64), ("B", C.c_int), ("base_rows", C.c_int), ("index_rows", C.c_int), ("K", C.c_int), ("S1", C.c_int),
+                ("mode", C.c_int)]
+
+
+CURVE_MODES = ("deletion", "insertion")                                # advh_curve_desc.mode: 0, 1
+CURVE_ORDERS = ("morf", "lerf", "random")
+CURVE_OUTPUTS = ("prob", "logit")
+CURVE_POOLS = ("sum", "mean")
+
+
+def curve_counts(steps, K: int) -> np.ndarray:
+    """The schedule of a perturbation curve: int32 ``[S + 1]`` counts of switched features, strictly increasing from 0 to K.
+    ``steps``: None (``S = min(K, 20)``), an int ``S`` in ``[1, K]`` (``c_j = (j * K + S // 2) // S``) or a strictly increasing
+    sequence of fractions from 0.0 to 1.0 (``c = floor(f * K + 0.5)``).  Raises ValueError on anything else and on counts that
+    collide after rounding."""
+    if steps is None:
+        steps = min(K, 20)
+    if isinstance(steps, (int, np.integer)) and not isinstance(steps, bool):
+        S = int(steps)
+        if not 1 <= S <= K:
+            raise ValueError(f"steps must be in [1, {K}] (the number of features), not {S}")
+        return np.array([(j * K + S // 2) // S for j in range(S + 1)], dtype=np.int32)
+    if isinstance(steps, (bool, str)) or not isinstance(steps, (list, tuple, np.ndarray, torch.Tensor)):
+        raise ValueError(f"steps must be None, an integer or a sequence of fractions, not {steps!r}")
+    f = np.asarray(steps.detach().cpu() if torch.is_tensor(steps) else steps, dtype=np.float64)
+    if f.ndim != 1 or f.size < 2 or not np.isfinite(f).all() or f[0] != 0.0 or f[-1] != 1.0 or not (np.diff(f) > 0).all():
+        raise ValueError("the fractions of steps must be strictly increasing, start at 0.0 and end at 1.0")
+    counts = np.floor(f * K + 0.5).astype(np.int64)
+    if not (np.diff(counts) > 0).all():
+        raise ValueError(f"the fractions of steps collide after rounding to counts of {K} features: {counts.tolist()}")
+    return counts.astype(np.int32)
+
+
+def _one_of(v, choices, what) -> int:
+    if v not in choices:
+        raise ValueError(f"{what} must be one of {choices}, not {v!r}")
+    return choices.index(v)
+
+
+def check_curve_features(index: torch.Tensor, K: int) -> None:
+    """Every clip must hold at least one sample of each of the K features (a ``[1, L]`` index does by construction): a feature
+    without samples has no score (advh_feature_scores gives it -inf)."""
+    if index.shape[0] > 1:
+        for b, row in enumerate(index):
+            if int(torch.unique(row).numel()) != K:
+                raise ValueError(f"clip {b} holds no sample of some of the {K} features of feature_mask; a perturbation curve "
+                                 "needs every feature in every clip")
+
+
+def feature_scores(attr: torch.Tensor, index: Optional[torch.Tensor], K: int, use_abs: bool = False, mean: bool = False) -> torch.Tensor:
+    """``score [B, K]``: the per-clip fp32 sum (``mean``: average) of ``attr [B, n]`` (``use_abs``: its magnitude) over the samples
+    of each feature of ``index [1 | B, n]`` (None: the identity, ``K == n``), in increasing sample order."""
+    B, n = attr.shape
+    _on_gpu(attr, *(() if index is None else (index,)))
+    score = torch.empty((B, K), dtype=torch.float32, device=attr.device)
+    _lib.check(_lib.lib().advh_feature_scores(attr.data_ptr(), None if index is None else index.data_ptr(),
+                                              0 if index is None else index.shape[0], B, n, K, int(use_abs), int(mean), score.data_ptr(),
+                                              _st()), "advh_feature_scores")
+    return score
+
+
+def feature_rank(score: torch.Tensor, descending: bool) -> torch.Tensor:
+    """``rank [B, K]`` int32: the position of each feature in its clip's order (``descending``: highest score first); ties go to
+    the lower feature number."""
+    B, K = score.shape
+    _on_gpu(score)
+    rank = torch.empty((B, K), dtype=torch.int32, device=score.device)
+    _lib.check(_lib.lib().advh_feature_rank(score.data_ptr(), B, K, int(descending), rank.data_ptr(), _st()), "advh_feature_rank")
+    return rank
+
+
+def curve_desc(x, base, index, rank, counts, mode: int) -> CurveDesc:
+    B, L = x.shape
+    d = CurveDesc(x.data_ptr(), base.data_ptr(), None if index is None else index.data_ptr(), rank.data_ptr(), counts.data_ptr(), L, B,
+                  base.shape[0], 0 if index is None else index.shape[0], rank.shape[1], counts.numel(), mode)
+    d.tensors = tuple(t for t in (x, base, index, rank, counts) if t is not None)     # kept alive as long as the desc
+    return d
+
+
+def curve_points(d: CurveDesc, row0: int, rows: int, out: torch.Tensor) -> None:
+    """Curve rows ``[row0, row0 + rows)`` (step-major ``j * B + b``, rows past ``S1 * B`` copy x) into ``out [rows, n]``."""
+    _on_gpu(*d.tensors, out)
+    _lib.check(_lib.lib().advh_curve_points(C.byref(d), row0, rows, out.data_ptr(), _st()), "advh_curve_points")
+
+
+def curve_fold(fk: torch.Tensor, counts: torch.Tensor, B: int, K: int, prob: bool, ref_last: bool):
+    """``(curve [B, S1], auc [B], aopc [B])`` from the rows' logits ``fk [S1 * B]`` and the device counts ``[S1]``."""
+    S1 = counts.numel()
+    _on_gpu(fk, counts)
+    curve = torch.empty((B, S1), dtype=torch.float32, device=fk.device)
+    auc, aopc = torch.empty(B, dtype=torch.float32, device=fk.device), torch.empty(B, dtype=torch.float32, device=fk.device)
+    _lib.check(_lib.lib().advh_curve_fold(fk.data_ptr(), counts.data_ptr(), B, S1, K, int(prob), int(ref_last), curve.data_ptr(),
+                                          auc.data_ptr(), aopc.data_ptr(), _st()), "advh_curve_fold")
+    return curve, auc, aopc
+
+
+class PerturbationCurve(NamedTuple):
+    """The result of ``HipAttribution.perturbation_curve``: ``curve [B, S + 1]`` (the output at each step), ``fractions [S + 1]``
+    (float64: the share of features switched), ``auc [B]``, ``aopc [B]`` and ``rank [B, K]`` (int32: the step order of each
+    clip's features)."""
+    curve: torch.Tensor
+    fractions: torch.Tensor
+    auc: torch.Tensor
+    aopc: torch.Tensor
+    rank: torch.Tensor
+
+
 class PermutationDesc(C.Structure):
     """Mirror of ``advh_permutation_desc`` (include/addvisor_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("index", C.c_void_p), ("perm", C.c_void_p), ("n", C.c_int64), ("B", C.c_int), ("K", C.c_int)]
@@ -1217,6 +1332,92 @@ class HipAttribution:
             points(row0 + c * chunk, pts)
             fk[c * chunk:(c + 1) * chunk] = self._row_logit(pts, row0 + c * chunk)
         return fk
+
+    def perturbation_curve(self, waves, attributions, mode: str = "deletion", order: str = "morf", feature_mask=None, steps=None,
+                           baselines=None, output: str = "prob", use_abs: bool = False, pool: str = "sum", seed: Optional[int] = None,
+                           internal_batch_size: Optional[int] = None) -> PerturbationCurve:
+        """The perturbation curve of an attribution map: features are removed (``mode="deletion"``: replaced by ``baselines``)
+        or restored (``"insertion"``: starting from the baseline) in the order of their relevance, and the classifier's output
+        is recorded along the way -- the deletion / insertion curves of Petsiuk et al. (RISE, 2018) and, through ``aopc``, the
+        AOPC of Samek et al. (2017), i.e. DeYoung et al.'s (2020) comprehensiveness (deletion) and sufficiency (insertion).
+        Restated from the papers: no Captum class exists, so parity is not pinned to one.
+
+        ``attributions``: a floating ``[B, L]`` map of any method.  ``feature_mask`` / ``baselines`` / ``internal_batch_size`` as
+        ``shapley_value_sampling`` (ids >= 0; every clip must hold every feature).  A feature's score is the sum (``pool="mean"``:
+        the average) of its samples' attributions (``use_abs``: magnitudes), in fp32 in increasing sample order.  ``order``:
+        ``"morf"`` most relevant first, ``"lerf"`` least relevant first -- equal scores go lower feature number first in both --
+        or ``"random"``: one uniform permutation per clip drawn on the host from ``seed`` (``shapley_permutations``' stream), the
+        chance-level curve the other two are read against.  ``steps``: see ``curve_counts``; step j switches the ``c_j`` first
+        features of each clip's own order, so row ``j * B + b`` is clip b with those features at the baseline (deletion) or only
+        those features present (insertion).  ``output``: ``"prob"`` (the sigmoid of the logit) or ``"logit"``.
+
+        Returns a ``PerturbationCurve``: ``curve [B, S + 1]``, ``fractions = c / K``, ``auc`` (trapezoid over the fractions,
+        divided by their span) and ``aopc = mean_j (y_ref - y_j)`` over the S steps other than the reference step, the one that
+        equals the clip itself (step 0 of a deletion, step S of an insertion) -- no separate ``F(x)`` forward is run.  The
+        ``(S + 1) * B`` rows go through the forward ``internal_batch_size`` (default 128) at a time."""
+        plan = self._curve_plan(waves, attributions, feature_mask, steps, baselines, use_abs, pool, internal_batch_size)
+        m, o, p = _one_of(mode, CURVE_MODES, "mode"), _one_of(order, CURVE_ORDERS, "order"), _one_of(output, CURVE_OUTPUTS, "output")
+        rank = None
+        if order == "random":
+            rank = torch.from_numpy(_permutation_stream(_check_seed(seed))(plan["B"], plan["K"]))
+        self._curve_upload(plan, waves, attributions)
+        if rank is None:
+            rank = self._curve_rank(plan, descending=o == 0)
+        return self._curve(plan, rank.to(plan["x"].device), m, p == 0)
+
+    def curve_summary(self, waves, attributions, feature_mask=None, steps=None, baselines=None, use_abs: bool = False, pool: str = "sum",
+                      internal_batch_size: Optional[int] = None) -> dict:
+        """Deletion and insertion curves in MoRF order on the probability, from one shared rank: ``{"deletion_auc",
+        "insertion_auc", "comprehensiveness", "sufficiency"}``, each ``[B]`` -- comprehensiveness is the deletion AOPC (how far
+        removing the most relevant features drops the output: higher is better), sufficiency the insertion AOPC (how far the
+        most relevant features alone fall short of it: lower is better).  Arguments as ``perturbation_curve``."""
+        plan = self._curve_plan(waves, attributions, feature_mask, steps, baselines, use_abs, pool, internal_batch_size)
+        self._curve_upload(plan, waves, attributions)
+        rank = self._curve_rank(plan, descending=True)
+        dele, ins = self._curve(plan, rank, 0, True), self._curve(plan, rank, 1, True)
+        return {"deletion_auc": dele.auc, "insertion_auc": ins.auc, "comprehensiveness": dele.aopc, "sufficiency": ins.aopc}
+
+    def _curve_plan(self, waves, attributions, feature_mask, steps, baselines, use_abs, pool, internal_batch_size) -> dict:
+        """Every argument check of the perturbation curve, on the host, before any GPU work."""
+        B, L = _dims(waves)
+        if _dims(_float_tensor(attributions, "attributions")) != (B, L):
+            raise ValueError(f"attributions must be [{B}, {L}] like the inputs; got {list(attributions.shape)}")
+        base = check_ig_baselines(baselines, B, L)
+        index, K = shapley_feature_indices(feature_mask, B, L)
+        check_curve_features(index, K)
+        chunk = check_internal_batch(internal_batch_size)
+        if not isinstance(use_abs, (bool, np.bool_)):
+            raise ValueError(f"use_abs must be a bool, not {use_abs!r}")
+        return {"B": B, "L": L, "K": K, "base": base, "index": None if feature_mask is None else index, "chunk": chunk,
+                "counts": curve_counts(steps, K), "use_abs": bool(use_abs), "mean": _one_of(pool, CURVE_POOLS, "pool") == 1}
+
+    def _curve_upload(self, plan: dict, waves, attributions) -> None:
+        x = self._prep(waves)
+        plan["x"], plan["attr"] = x, self._prep(attributions)
+        plan["base"] = plan["base"].to(x.device, torch.float32).contiguous()
+        if plan["index"] is not None:
+            plan["index"] = plan["index"].to(x.device).contiguous()
+        plan["counts_dev"] = torch.from_numpy(plan["counts"]).to(x.device)
+
+    def _curve_rank(self, plan: dict, descending: bool) -> torch.Tensor:
+        score = feature_scores(plan["attr"], plan["index"], plan["K"], plan["use_abs"], plan["mean"])
+        if not bool(torch.isfinite(score).all()):
+            raise ValueError("attributions must be finite: a feature's score is inf or NaN")
+        return feature_rank(score, descending)
+
+    def _curve(self, plan: dict, rank: torch.Tensor, mode: int, prob: bool) -> PerturbationCurve:
+        """The chunk loop of one curve: rows -> forward logits -> one fold launch."""
+        x, B, K, counts = plan["x"], plan["B"], plan["K"], plan["counts_dev"]
+        R = counts.numel() * B
+        chunk = min(plan["chunk"], R)
+        d = curve_desc(x, plan["base"], plan["index"], rank, counts, mode)
+        pts = torch.empty((chunk, x.shape[1]), dtype=torch.float32, device=x.device)
+        fk = self._row_logits(lambda row0, out: curve_points(d, row0, chunk, out), 0, R, pts)
+        curve, auc, aopc = curve_fold(fk, counts, B, K, prob, ref_last=mode == 1)
+        self._checked(curve, "perturbation curve", "a logit of the clips or of their perturbed rows is not finite (check the "
+                                                   "inputs and baselines)")
+        fractions = torch.from_numpy(plan["counts"].astype(np.float64) / K).to(x.device)
+        return PerturbationCurve(curve, fractions, auc, aopc, rank)
 
     def _shapley_args(self, waves, baselines, feature_mask, internal_batch_size):
         B, L = _dims(waves)

@@ -23,6 +23,10 @@ accepted for Captum compatibility, but a mask baseline is the meaningful choice:
 mask, or -- GradientShap -- a ``[N_b, Fm, Tm]`` distribution.  The same invariance gives Euler's identity
 ``sum_j m_j dF/dm_j = 0`` in the ``linear`` domain, a check on any gradient this engine returns.
 
+``perturbation_curve`` / ``curve_summary`` score a mask-domain attribution (the U-Net's mask included) by its deletion / insertion
+curves over the features of ``tf_feature_mask`` (attribution.py; csrc/attribution_curve.hip).  There too a mask baseline, such as
+a constant 0.5, is the meaningful choice: the zero mask resynthesises silence.
+
 Not in this engine: KernelShap, Lime, FeaturePermutation, NoiseTunnel, the metrics and the attacks over masks
 (NotImplementedError)."""
 from __future__ import annotations
@@ -302,6 +306,33 @@ class HipSpectralAttribution:
         fm = flat_feature_mask(feature_mask, B, Fm, Tm)
         return self._rows.shapley_value_sampling(self._rows._prep(masks), baselines=base, feature_mask=fm, n_samples=n_samples, seed=seed,
                                                  internal_batch_size=internal_batch_size).view(masks.shape)
+
+    def _curve_args(self, masks, attributions, feature_mask, baselines):
+        B, Fm, Tm = self._enter(masks)
+        if not torch.is_tensor(attributions) or tuple(attributions.shape) != (B, Fm, Tm):
+            raise ValueError(f"attributions must be a [{B}, {Fm}, {Tm}] tensor like the masks")
+        base = check_mask_baselines(baselines, B, Fm, Tm)
+        # flat views only: the rows engine checks the remaining arguments before it moves anything to the device
+        return masks.reshape(B, Fm * Tm), attributions.reshape(B, Fm * Tm), base, flat_feature_mask(feature_mask, B, Fm, Tm)
+
+    def perturbation_curve(self, masks, attributions, mode: str = "deletion", order: str = "morf", feature_mask=None, steps=None,
+                           baselines=None, output: str = "prob", use_abs: bool = False, pool: str = "sum", seed: Optional[int] = None,
+                           internal_batch_size: Optional[int] = None):
+        """``HipAttribution.perturbation_curve`` over the STFT bins: ``attributions [B, Fm, Tm]`` ranks the features of
+        ``feature_mask`` (None: every bin; ``tf_feature_mask`` is the natural grouping), and each step's masks are resynthesised
+        on their clip's spectrogram.  The zero-mask baseline (``baselines=None``) resynthesises silence, the point the module
+        docstring warns about (see "The zero baseline" there): prefer a mask baseline, e.g. a constant 0.5 mask."""
+        x, attr, base, fm = self._curve_args(masks, attributions, feature_mask, baselines)
+        return self._rows.perturbation_curve(x, attr, mode=mode, order=order, feature_mask=fm, steps=steps, baselines=base, output=output,
+                                             use_abs=use_abs, pool=pool, seed=seed, internal_batch_size=internal_batch_size)
+
+    def curve_summary(self, masks, attributions, feature_mask=None, steps=None, baselines=None, use_abs: bool = False, pool: str = "sum",
+                      internal_batch_size: Optional[int] = None) -> dict:
+        """``HipAttribution.curve_summary`` over the STFT bins; baselines as ``perturbation_curve`` (prefer a mask baseline to the
+        zero mask: module docstring)."""
+        x, attr, base, fm = self._curve_args(masks, attributions, feature_mask, baselines)
+        return self._rows.curve_summary(x, attr, feature_mask=fm, steps=steps, baselines=base, use_abs=use_abs, pool=pool,
+                                        internal_batch_size=internal_batch_size)
 
     def pool(self, attr, band_bins: int = 64, seg_frames: Optional[int] = None) -> torch.Tensor:
         """``tf_pool``: the per-band (x per-segment) relevance of an attribution map."""

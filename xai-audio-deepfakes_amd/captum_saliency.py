@@ -281,6 +281,37 @@ def score_explanations(model, waves, method="input_x_gradient", n_steps=50, wind
                                                norm_ord=norm_ord)}
 
 
+def evaluate_explanation(model, waves, attributions, domain="wave", mask=None, segment=1600, **kw):
+    """Deletion / insertion curves of an attribution map for a batch ``[B, L]`` (Petsiuk et al. 2018; Samek et al. 2017; DeYoung
+    et al. 2020): ``{"deletion_auc", "insertion_auc", "comprehensiveness", "sufficiency"}``, each ``[B]``
+    (``HipAttribution.curve_summary``).  ``domain="wave"``: ``attributions [B, L]`` of any waveform method, features =
+    ``segment``-sample segments (``arange(L) // segment``, default 100 ms).  ``domain="spectrogram"``: ``attributions
+    [B, Fm, Tm]`` over the STFT mask ``mask`` (default ``ones(B, Fm, Tm)``), features = ``tf_feature_mask(Fm, Tm, band_bins,
+    seg_frames)`` (keywords ``band_bins=64``, ``seg_frames=16``, ``mask_domain="linear"``); pass a mask baseline
+    (``baselines=0.5``), not the zero mask.  The other keywords (``steps``, ``baselines``, ``use_abs``, ``pool``,
+    ``internal_batch_size``) go to ``curve_summary``."""
+    if domain not in ("wave", "spectrogram"):
+        raise ValueError(f"domain must be 'wave' or 'spectrogram', not {domain!r}")
+    if not torch.is_tensor(waves) or waves.dim() != 2:
+        raise ValueError("waves must be a [B, L] tensor")
+    if not torch.is_tensor(attributions):
+        raise ValueError("attributions must be a tensor")
+    if domain == "wave":
+        if mask is not None:
+            raise ValueError("mask belongs to domain='spectrogram'")
+        if isinstance(segment, bool) or not isinstance(segment, int) or segment < 1:
+            raise ValueError(f"segment must be an integer >= 1, not {segment!r}")
+        return model.hip_attribution().curve_summary(waves, attributions, feature_mask=_segments(waves, segment).cpu(), **kw)
+    band_bins, seg_frames, mask_domain = kw.pop("band_bins", 64), kw.pop("seg_frames", 16), kw.pop("mask_domain", "linear")
+    if attributions.dim() != 3:
+        raise ValueError("attributions must be [B, Fm, Tm] for domain='spectrogram'")
+    Fm, Tm = attributions.shape[1], attributions.shape[2]
+    ids = tf_feature_mask(Fm, Tm, band_bins, seg_frames)
+    eng = MaskedSpectrogramLogReg(model, waves, mask_domain).hip_mask_attribution()
+    m = torch.ones((eng.B, Fm, Tm), dtype=torch.float32, device=eng.waves.device) if mask is None else mask.to(eng.waves.device, torch.float32)
+    return eng.curve_summary(m, attributions, feature_mask=ids, **kw)
+
+
 ATTACKS = ("fgsm", "pgd")
 PGD_DEFAULTS = dict(radius=2e-3, step_size=5e-4, step_num=5)            # waveform units: a clip lives in [-1, 1]
 
