@@ -1168,6 +1168,33 @@ typedef struct advh_resblock_desc {
 int advh_resblock_pair_lds_bytes(int C, int k, int dil);
 int advh_resblock_pair_f16(const advh_resblock_desc* d, int C, advh_stream_t stream);
 
+/* Concept activation vectors (TCAV, Kim et al. 2018; captum.concept) on flattened activations -- csrc/concept.hip.  All inputs are fp32,
+ * row-major with a row stride in floats; every result is bit-identical from run to run (no atomics, one fixed summation order).
+ *
+ * advh_concept_gram: G[i][j] = sum_f X[i][f] * Y[j][f] for X [M][F] (row stride ldx >= F) and Y [N][F] (ldy >= F); G is double [M][N],
+ * contiguous.  F is cut into slabs of S floats, S = max(512, ceil(F / max(1, 1024 / (ceil(M/64) * ceil(N/64)))) rounded up to a multiple
+ * of 64): each slab's fp32 partial -- one k-ordered fmaf chain per entry on v_mfma_f32_16x16x4_f32 -- goes to `workspace`
+ * (advh_concept_gram_workspace(M, N, F) BYTES, = ceil(F / S) * M * N * 4), and a second launch adds the slabs in ascending order in
+ * fp64.  Tails in M, N, F and inside a slab are handled in the kernel.  symmetric = 1 needs Y == X, M == N, ldy == ldx: only the 64 x 64
+ * blocks on or above the diagonal are computed and G[i][j], i > j, is G[j][i] bit for bit.  Base pointers and strides that are
+ * 16-byte aligned are read with 16-byte loads; anything else (4-byte aligned) with 4-byte loads.
+ * ADVH_EINVAL: a null pointer, M, N, F <= 0, M or N > 2^20, F > 2^40, a stride < F, symmetric not in {0, 1} or without Y == X / M == N /
+ * ldy == ldx, X / Y / workspace not 4-byte or G not 8-byte aligned.  advh_concept_gram_workspace returns ADVH_EINVAL (negative) for sizes
+ * the kernel refuses.
+ *
+ * advh_concept_combine: W[c][f] = sum_i A[c][i] * X[i][f] for A [C][N] (contiguous) and X [N][F] (stride ldx), W [C][F] (stride ldw):
+ * the CAV from the dual coefficients.  One fp32 fmaf chain per output, i ascending from 0.f.  X is read once per group of 8 rows of A.
+ * ADVH_EINVAL: a null or misaligned pointer, C, N, F <= 0, a stride < F.
+ *
+ * advh_concept_time_pool: out[r][h] = sum_t X[r][t][h] for contiguous X [R][T][H], t ascending in fp32 from 0.f; mode 0 = the sum,
+ * mode 1 = the sum times float(1 / T).  ADVH_EINVAL: a null pointer, R, T, H <= 0, any other mode.
+ * Every argument check precedes the first HIP call.                                                                                  */
+int64_t advh_concept_gram_workspace(int M, int N, int64_t F);
+int advh_concept_gram(const float* X, int64_t ldx, const float* Y, int64_t ldy, int M, int N, int64_t F, int symmetric, float* workspace,
+                      double* G, advh_stream_t stream);
+int advh_concept_combine(const float* A, const float* X, int64_t ldx, int C, int N, int64_t F, float* W, int64_t ldw, advh_stream_t stream);
+int advh_concept_time_pool(const float* X, int64_t R, int T, int H, int mode, float* out, advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

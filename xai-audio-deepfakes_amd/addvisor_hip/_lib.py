@@ -176,6 +176,10 @@ SIGNATURES = {
     "advh_gelu_identity_bwd": (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p]),
     "advh_posconv_gather_bwd_split": (_i, [_p, _p, _i64, _i, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "advh_w2v2_frontend_bwd_group_split": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    "advh_concept_gram_workspace": (_i64, [_i, _i, _i64]),
+    "advh_concept_gram": (_i, [_p, _i64, _p, _i64, _i, _i, _i64, _i, _p, _p, _p]),
+    "advh_concept_combine": (_i, [_p, _p, _i64, _i, _i, _i64, _p, _i64, _p]),
+    "advh_concept_time_pool": (_i, [_p, _i64, _i, _i, _i, _p, _p]),
 }
 
 _lib = None
