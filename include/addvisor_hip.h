@@ -349,7 +349,9 @@ int advh_mel_log(const float* mag, const float* fb, float* out, int B, int F, in
  * advh_layernorm_bwd : dx of y = LN(x)*gamma+beta [then GELU if gelu_fwd] given dy; optionally times
  *                      GELU'(dact_src) and plus `add`; out_f (fp32) and/or out_h (fp16), all [M][C]; with
  *                      remap_P > 0 output row b*remap_T + t is written at row b*remap_P + t.
- * advh_attention_bwd_f16 : dqkv [B*T][3H] from qkv and dctx [B*T][H] (fp16), T <= 256, head_dim 32 / 64.
+ * advh_attention_bwd_f16 : dqkv [B*T][3H] from qkv and dctx [B*T][H] (fp16); head dim a multiple of 8 up to 128;
+ *                      T <= 256, but T <= 208 for head dims above 64 (the whole-clip tiles of a wider head need more
+ *                      than the 160 KiB of LDS): ADVH_EUNSUPPORTED otherwise, dqkv untouched.
  * advh_pool_logreg_bwd   : dh[b][t][:] = coef * dlogit[b] / T  (fp32 and/or fp16).
  * advh_w2v2_frontend_bwd_group : dz0 [B][P0][C0] fp16 from dy0 for the GroupNorm front end (z0 recomputed).
  * advh_wave_bwd      : g [B][P0][16] fp32 (= dz0 . w0, columns 0..9) -> dx [B][dx_stride] through the

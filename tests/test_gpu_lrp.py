@@ -25,8 +25,8 @@ from addvisor_hip.embedder_grad import LrpRules
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
-VALUE_BAR = 5e-6             # tests/test_gpu_backward.py::test_attention_bwd_split: dV of that computation
-LN_BAR = 2e-5                # tests/test_gpu_backward.py::test_layernorm_bwd_split's fp32 bar
+VALUE_BAR = 5e-6             # tests/test_gpu_backward_kernels.py::test_attention_bwd_split: dV of that computation
+LN_BAR = 2e-5                # tests/test_gpu_backward_kernels.py::test_layernorm_bwd's fp32 bar
 GELU_BAR = 1e-6              # fp32 product of two 22-bit values re-split to 22 bits
 TOL = {"f32": (1e-4, 0.999999), "f16": (3e-2, 0.999)}      # tests/test_gpu_layer_attr.py: every attribution map
 SPLIT_MAX, SAT_MAX = 65504.0, 65504.0 + 65504.0 / 2048.0   # csrc/device_math.h: hi saturates, lo carries the clamped remainder

@@ -78,6 +78,7 @@ def check_box(box, T: int, H: int) -> Tuple[int, int, int, int, int, int]:
 
 
 GELU_RULES = ("gradient", "identity")
+F16_WIDE_HEAD_MAX_T = 208       # advh_attention_bwd_f16: frames it holds for head dims above 64 (include/addvisor_hip.h)
 
 
 @dataclass(frozen=True)
@@ -408,6 +409,9 @@ class EmbedderGrad:
             _lib.check(lib.advh_attention_bwd_split(qkv.data_ptr(), qkv.stride(0), dctx.data_ptr(), dctx.stride(0), dqkv.data_ptr(),
                                                     dqkv.stride(0), B, T, H, heads, st), "advh_attention_bwd_split")
         else:
+            if H // heads > 64 and T > F16_WIDE_HEAD_MAX_T:
+                raise _lib.AdvhError(f"advh_attention_bwd_f16: ADVH_EUNSUPPORTED: head dim {H // heads} > 64 is held for T <= {F16_WIDE_HEAD_MAX_T} frames only "
+                                     f"(T = {T}: its whole-clip tiles exceed the 160 KiB of LDS); shorten the clip or use precision='f32'")
             _lib.check(lib.advh_attention_bwd_f16(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), B, T, H, heads, st),
                        "advh_attention_bwd_f16")
 

@@ -86,6 +86,18 @@ __device__ __forceinline__ f16x8 gfrag(const _Float16* p, bool in) {
         accm = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, accm, 0, 0, 0);        \
         accx = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, accx, 0, 0, 0);        \
     } while (0)
+// The same product with the operand ROLES exchanged (pass B computes S = Q K^T where pass A computed S^T = K Q^T): the cross
+// terms enter accx in pass A's order (first the product that holds A's ah, which is b here), so the recomputed S and dP are
+// bit-equal to the values behind pass A's row statistics.  dS_ii = P_ii (dP_ii - delta_i) relies on it: delta_i contains
+// P_ii dP_ii, and for a peaked row (P_ii ~ 1) the difference keeps only what is left after dP_ii cancels -- a dP_ii that differs
+// in its last bits of accx (a rounding of ~2^-24 sum|dO v|) does not cancel (5 % of dS_ii, 2.4e-5 of max|dk| in
+// tests/test_gpu_backward_kernels.py::test_attention_bwd_peaked_softmax before this order was fixed).
+#define MFMA_X3_SWAPPED(accm, accx, ah, al, bh, bl)                                  \
+    do {                                                                             \
+        accx = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, accx, 0, 0, 0);        \
+        accm = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, accm, 0, 0, 0);        \
+        accx = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, accx, 0, 0, 0);        \
+    } while (0)
 
 template <int NT, int D, int NW>
 __global__ __launch_bounds__(64 * NW) void attention_bwd_x3_kernel(const _Float16* __restrict__ qkv, long qkv_lo, const _Float16* __restrict__ dctx,
@@ -265,8 +277,8 @@ __global__ __launch_bounds__(64 * NW) void attention_bwd_x3_kernel(const _Float1
                     const int o = sb + h * 16 * D + rowoff[kk];             // rows >= T are zero in LDS
                     const f16x8 qah = *(const f16x8*)(P0h + o), qal = *(const f16x8*)(P0l + o);
                     const f16x8 oah = *(const f16x8*)(P1h + o), oal = *(const f16x8*)(P1l + o);
-                    MFMA_X3(sm_, sx, qah, qal, kh[kk], kl[kk]);     // S  [q][key]
-                    MFMA_X3(pm, px, oah, oal, vh[kk], vl[kk]);      // dP [q][key]
+                    MFMA_X3_SWAPPED(sm_, sx, qah, qal, kh[kk], kl[kk]);     // S  [q][key], bit-equal to pass A's S^T
+                    MFMA_X3_SWAPPED(pm, px, oah, oal, vh[kk], vl[kk]);      // dP [q][key], bit-equal to pass A's dP^T
                 }
                 const int q0 = ss * 32 + h * 16 + g * 4;            // this lane's four query rows; its key column = krow
                 const float4 mx4 = *(const float4*)(rmax + q0), iv4 = *(const float4*)(rinv + q0), dl4 = *(const float4*)(rdel + q0);
