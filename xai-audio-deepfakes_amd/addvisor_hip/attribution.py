@@ -5,10 +5,10 @@
 GradientShap ``n_samples=5``, ``stdevs=0.0``, expanded inputs clip-major).
 
 IntegratedGradients is path-batched: the ``n_steps * B`` interpolation points are pushed through one
-forward + dgrad-only backward in chunks of ``internal_batch_size`` rows (whole steps per chunk).  With a baseline (or a
-Riemann rule, ``multiply_by_inputs=False``, a convergence delta) the path points and the weighted, baseline-aware sums run
-on csrc/attribution_paths.hip; so does GradientShap, whose Gaussian input noise comes from the same counter-based generator
-(``philox_normal``) on the device.
+forward + dgrad-only backward in chunks of ``internal_batch_size`` rows (whole steps per chunk).  The path points and the
+weighted, baseline-aware sums of every baseline, rule and option (the default zero baseline included) run on
+csrc/attribution_paths.hip, in one loop that the layer and neuron path methods share (``_integrate_path``); so does
+GradientShap, whose Gaussian input noise comes from the same counter-based generator (``philox_normal``) on the device.
 
 The perturbation attributions ``captum.attr.Occlusion / FeatureAblation`` need no gradient: the ablated batch is built on the
 device (csrc/attribution_ablation.hip), pushed through the classifier forward in chunks, and the logit differences are
@@ -41,6 +41,7 @@ csrc/attribution_curve.hip; the rows go through the same forward seam as the per
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import inspect
 import itertools
 import math
@@ -282,6 +283,16 @@ def _check_seed(seed) -> int:
     if not 0 <= seed < 2 ** 64:
         raise ValueError("seed must be in [0, 2**64)")
     return seed
+
+
+def _check_delta(return_convergence_delta, multiply_by_inputs) -> None:
+    if return_convergence_delta and not multiply_by_inputs:
+        raise NotImplementedError("the convergence delta needs multiply_by_inputs=True")
+
+
+def _device_base(base: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """A checked baseline (or baseline distribution) as contiguous fp32 rows on the device of ``x``."""
+    return base.to(x.device, torch.float32).contiguous()
 
 
 def _permutation_stream(seed: int):
@@ -912,6 +923,7 @@ class AblationDesc(C.Structure):
 
 
 ABL_OCCLUSION, ABL_FEATURE = 0, 1                                      # advh_ablation_desc.mode
+_ABLATION_CAUSE = "a logit of the clips or of their ablations is not finite (check the inputs and baselines)"
 
 
 def ablation_desc(x, base, mode, K, win=0, stride=0, mask=None) -> AblationDesc:
@@ -1094,6 +1106,16 @@ def _accumulate(d, grad, w, mode, row0, rows, total, row_sum=None):
                "advh_attr_path_accumulate")
 
 
+def _steps_per_chunk(B: int, n_points: int, internal_batch_size: Optional[int]) -> int:
+    """Whole path steps (B rows each) per chunk of ``internal_batch_size`` (default 128) rows: at least one, at most all."""
+    return min(max(1, (internal_batch_size or 128) // B), n_points)
+
+
+def _step_major(alphas: np.ndarray, B: int, device) -> torch.Tensor:
+    """One value per step (the alphas, or the step sizes) as the fp32 device vector of the step-major rows ``s * B + b``."""
+    return torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=device)
+
+
 def philox_normal(seed: int, row0: int, rows: int, n: int, device, raw: bool = False) -> torch.Tensor:
     """``[rows, n]`` fp32 standard normals N(seed, row0 + r, j): exactly the noise GradientShap adds to expanded row g
     (``stdevs * N(seed, g, :)``).  ``raw=True``: the Philox words instead, ``[rows, n]`` int32 (bit patterns).
@@ -1178,45 +1200,60 @@ class HipAttribution:
                              method: str = "gausslegendre", multiply_by_inputs: bool = True, return_convergence_delta: bool = False):
         """Captum's IntegratedGradients.  ``baselines``: None (zero), a number, ``[1, L]`` or ``[B, L]``; ``method``: one of
         ``METHODS``.  With ``return_convergence_delta`` returns ``(attr, delta)``, ``delta[b] = sum_j attr[b, j] -
-        (F(x_b) - F(base_b))`` ``[B]`` (F from one extra forward over x and the baselines).  The zero baseline with the
-        default rule and no delta runs the original zero-baseline path.  A constant clip (the alpha = 0 point of a number
-        baseline under ``riemann_left`` / ``riemann_trapezoid``) is where the classifier's per-clip normalisation has no
-        scale: its gradient can leave the chain's range, and the call then raises FloatingPointError."""
-        if baselines is None and method == "gausslegendre" and multiply_by_inputs and not return_convergence_delta:
-            return self._ig_zero(waves, n_steps, internal_batch_size)
+        (F(x_b) - F(base_b))`` ``[B]`` (F from one extra forward over x and the baselines).  A constant clip (the alpha = 0
+        point of a number baseline under ``riemann_left`` / ``riemann_trapezoid``) is where the classifier's per-clip
+        normalisation has no scale: its gradient can leave the chain's range, and the call then raises FloatingPointError."""
         B, L = _dims(waves)
         base = check_ig_baselines(baselines, B, L)
         alphas, steps = approximation(method, n_steps)
-        if return_convergence_delta and not multiply_by_inputs:
-            raise NotImplementedError("the convergence delta needs multiply_by_inputs=True")
+        _check_delta(return_convergence_delta, multiply_by_inputs)
         x = self._prep(waves)
-        base = base.to(x.device, torch.float32).contiguous()
-        per = min(max(1, (internal_batch_size or 128) // B), n_steps)          # whole steps per chunk, as _ig_zero
-        npad = -(-n_steps // per) * per
-        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
-        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
-        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
-        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
-        d = _desc(x, base, None, npad, 0)
-        total = torch.zeros_like(x)
-        pts = torch.empty((per * B, L), dtype=torch.float32, device=x.device)
-        for s0 in range(0, npad, per):
-            _points(d, a_all, s0 * B, per * B, pts)
-            g = self._row_gradient(pts, s0 * B)                                 # [per*B, L], step-major
-            _accumulate(d, g, w_all, ACC_IG, s0 * B, per * B, total)
-        out = torch.empty_like(x)
-        sums = torch.empty(B, dtype=torch.float32, device=x.device) if return_convergence_delta else None
-        if multiply_by_inputs:
-            _accumulate(d, total, None, FIN_IG, 0, B, out, sums)
-        else:
-            d.S = 1                                                             # FIN_MEAN with S = 1: the sum itself
-            _accumulate(d, total, None, FIN_MEAN, 0, B, out)
+        base = _device_base(base, x)
+        out, sums = self._integrate_path(x, base, alphas, steps, internal_batch_size, self._row_gradient,
+                                         FIN_IG if multiply_by_inputs else FIN_MEAN, return_convergence_delta)
         out = self._checked(out)
         if not return_convergence_delta:
             return out
         f = self.logits(torch.cat([x, base])).double()
         fb = f[B:].expand(B) if base.shape[0] == 1 else f[B:]
         return out, (sums.double() - (f[:B] - fb)).float()
+
+    def _integrate_path(self, x, base, alphas, steps, internal_batch_size, point_gradient, finalize=None, want_sums: bool = False):
+        """The one straight-path loop: ``sum_k steps[k] * point_gradient(base + alphas[k] (x - base))`` over ``x [B, ...]`` and
+        ``base [1 | B, ...]`` (flattened to rows), then the optional finalize -- ``FIN_IG``: times ``x - base``, with the per-clip
+        sums of the result when ``want_sums`` (the convergence deltas); ``FIN_MEAN``: the sum itself through the kernel; None:
+        the sum as accumulated.  Returns ``(out, sums)``, unchecked.
+
+        ``point_gradient(pts, row0) -> [rows, ...]`` is the gradient at the step-major rows ``pts`` (row ``row0 + r`` is step
+        ``(row0 + r) // B`` of clip ``(row0 + r) % B``).  Whole steps per chunk (``_steps_per_chunk``); the schedule is padded
+        with zero-weight copies of the last step to whole chunks, so every chunk has the same shape: one ``pts`` workspace that
+        every chunk fills completely (hence ``torch.empty``), and one accumulate launch per chunk.  The gradient's rows need not
+        have the points' shape (InternalInfluence: waveform points, layer gradients): the sum takes the gradient's."""
+        B, n_steps = x.shape[0], len(alphas)
+        per = _steps_per_chunk(B, n_steps, internal_batch_size)
+        npad = -(-n_steps // per) * per
+        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
+        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
+        a_all, w_all = _step_major(alphas, B, x.device), _step_major(steps, B, x.device)
+        d = _desc(x.view(B, -1), base.view(base.shape[0], -1), None, npad, 0)
+        pts = torch.empty((per * B,) + x.shape[1:], dtype=torch.float32, device=x.device)
+        total = dt = None
+        for s0 in range(0, npad, per):
+            _points(d, a_all, s0 * B, per * B, pts)
+            g = point_gradient(pts, s0 * B)                                     # [per*B, ...], step-major
+            if total is None:
+                total = torch.zeros_like(g[:B])
+                flat = total.view(B, -1)
+                dt = d if flat.shape[1] == d.n else _desc(flat, flat, None, npad, 0)   # ACC_IG reads neither x nor the baseline
+            _accumulate(dt, g, w_all, ACC_IG, s0 * B, per * B, total)
+        if finalize is None:
+            return total, None
+        out = torch.empty_like(total)
+        sums = torch.empty(B, dtype=torch.float32, device=x.device) if want_sums else None
+        if finalize == FIN_MEAN:
+            d.S = 1                                                             # FIN_MEAN with S = 1: the sum itself
+        _accumulate(d, total, None, finalize, 0, B, out, sums)
+        return out, sums
 
     def gradient_shap(self, waves, baselines, n_samples: int = 5, stdevs: float = 0.0, multiply_by_inputs: bool = True,
                       return_convergence_delta: bool = False, seed: Optional[int] = None, internal_batch_size: Optional[int] = None):
@@ -1231,37 +1268,17 @@ class HipAttribution:
         and the noise ``philox_normal(seed, ...)``, so a seed fixes the result bit for bit.  Captum's RNG stream is not
         reproduced (captum is absent)."""
         B, L = _dims(waves)
-        if callable(baselines) and not torch.is_tensor(baselines):
-            baselines = baselines(waves) if inspect.signature(baselines).parameters else baselines()
-        base = check_shap_args(baselines, B, L, n_samples, stdevs)
-        if return_convergence_delta and not multiply_by_inputs:
-            raise NotImplementedError("the convergence delta needs multiply_by_inputs=True")
-        seed = draw_seed() if seed is None else int(seed)
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError("seed must be in [0, 2**64)")
-        S, nb = int(n_samples), base.shape[0]
-        idx, alpha = shap_draws(seed, B, S, nb)
+        base, S, seed, draws = self._shap_args(waves, baselines, B, L, n_samples, stdevs, seed, return_convergence_delta,
+                                               multiply_by_inputs)
         x = self._prep(waves)
         dev = x.device
-        base = base.to(dev, torch.float32).contiguous()
-        bidx = torch.from_numpy(idx).to(dev)
-        a_all = torch.from_numpy(alpha).to(dev)
+        base = _device_base(base, x)
         R = B * S
-        chunk = min(internal_batch_size or 128, R)
-        d = _desc(x, base, bidx, S, 1, float(stdevs), seed)
-        total = torch.zeros_like(x)
         row_sum = torch.empty(R, dtype=torch.float32, device=dev) if return_convergence_delta else None
-        # one workspace shape: a short last chunk leaves the previous chunk's (finite) points in the rows it does not use
-        pts = torch.zeros((chunk, L), dtype=torch.float32, device=dev)
-        mode = ACC_SHAP if multiply_by_inputs else ACC_SHAP_GRAD
-        for row0 in range(0, R, chunk):
-            rows = min(chunk, R - row0)
-            _points(d, a_all, row0, rows, pts)
-            g = self._row_gradient(pts, row0, 1, S)                             # [chunk, L], clip-major
-            _accumulate(d, g, None, mode, row0, rows, total, row_sum)
-        out = torch.empty_like(x)
-        _accumulate(d, total, None, FIN_MEAN, 0, B, out)
+        out, bidx, pts = self._expanded_samples(x, base, draws, S, stdevs, seed, multiply_by_inputs, internal_batch_size,
+                                                self._row_gradient, row_sum)
         out = self._checked(out)
+        chunk = pts.shape[0]
         if not return_convergence_delta:
             return out
         fb = self.logits(base).double()[bidx.long()]
@@ -1278,6 +1295,46 @@ class HipAttribution:
                 fx[row0:row0 + rows] = self.logits(pts)[:rows].double()
         return out, (row_sum.double() - (fx - fb)).float()
 
+    @staticmethod
+    def _shap_args(waves, baselines, B: int, L: int, n_samples, stdevs, seed, return_convergence_delta: bool = False,
+                   multiply_by_inputs: bool = True, internal_batch_size: Optional[int] = None):
+        """The arguments of the expanded-sample methods after their own first checks, in the order the errors are promised:
+        a callable ``baselines`` unwrapped, ``check_shap_args``, the delta and ``internal_batch_size`` checks of the method that
+        passes them, the seed, then the host draws.  Returns ``(baselines [N_b, L], S, seed, shap_draws(...))``."""
+        if callable(baselines) and not torch.is_tensor(baselines):
+            baselines = baselines(waves) if inspect.signature(baselines).parameters else baselines()
+        base = check_shap_args(baselines, B, L, n_samples, stdevs)
+        _check_delta(return_convergence_delta, multiply_by_inputs)
+        if internal_batch_size is not None:
+            _positive_int(internal_batch_size, "internal_batch_size")
+        seed, S = _check_seed(seed), int(n_samples)
+        return base, S, seed, shap_draws(seed, B, S, base.shape[0])
+
+    def _expanded_samples(self, x, base, draws, S: int, stdevs, seed: int, multiply_by_inputs: bool, internal_batch_size, row_gradient,
+                          row_sum=None):
+        """The one expanded-sample (GradientShap) loop over the clip-major rows ``b * S + s``: the mean over a clip's samples of
+        ``(x~ - b) * row_gradient(b + alpha (x~ - b))`` (the gradient alone without ``multiply_by_inputs``), ``draws = (idx,
+        alpha)`` from ``shap_draws``; ``row_sum [B * S]`` takes the per-row sums for the convergence delta.
+        ``row_gradient(pts, row0, 1, S)`` as ``_row_gradient``.  Returns ``(out, bidx, pts)``, unchecked: the device copy of
+        ``idx`` and the ``[chunk, L]`` workspace, which the delta reuses."""
+        B, L = x.shape
+        bidx, a_all = (torch.from_numpy(v).to(x.device) for v in draws)
+        R = B * S
+        chunk = min(internal_batch_size or 128, R)
+        d = _desc(x, base, bidx, S, 1, float(stdevs), seed)
+        total = torch.zeros_like(x)
+        # one workspace shape: a short last chunk leaves the previous chunk's (finite) points in the rows it does not use
+        # (unlike the path integrator, whose padded schedule fills every chunk whole)
+        pts = torch.zeros((chunk, L), dtype=torch.float32, device=x.device)
+        for row0 in range(0, R, chunk):
+            rows = min(chunk, R - row0)
+            _points(d, a_all, row0, rows, pts)
+            g = row_gradient(pts, row0, 1, S)                                   # [chunk, L], clip-major
+            _accumulate(d, g, None, ACC_SHAP if multiply_by_inputs else ACC_SHAP_GRAD, row0, rows, total, row_sum)
+        out = torch.empty_like(x)
+        _accumulate(d, total, None, FIN_MEAN, 0, B, out)
+        return out, bidx, pts
+
     def occlusion(self, waves, window, stride=1, baselines=None, internal_batch_size: Optional[int] = None):
         """Captum's Occlusion (restated: captum is absent).  ``window``, ``stride``: ints (or 1-tuples); ``baselines``: None
         (zero), a number, ``[1, L]`` or ``[B, L]``.  ``K = occlusion_windows(L, window, stride)`` ablated rows per clip, row
@@ -1290,8 +1347,10 @@ class HipAttribution:
         base = check_ig_baselines(baselines, B, L)
         chunk = check_internal_batch(internal_batch_size)
         x = self._prep(waves)
-        base = base.to(x.device, torch.float32).contiguous()
-        return self._ablate(ablation_desc(x, base, ABL_OCCLUSION, K, win, stride), x, K, chunk, "occlusion")
+        base = _device_base(base, x)                          # a local: the descriptor holds the pointer only
+        d = ablation_desc(x, base, ABL_OCCLUSION, K, win, stride)
+        return self._ablate(x, K * B, chunk, functools.partial(ablation_points, d), functools.partial(ablation_accumulate, d),
+                            "occlusion")
 
     def feature_ablation(self, waves, baselines=None, feature_mask=None, internal_batch_size: Optional[int] = None):
         """Captum's FeatureAblation (restated: captum is absent).  ``feature_mask``: None (each sample its own feature: L
@@ -1303,34 +1362,36 @@ class HipAttribution:
         index, K = feature_indices(feature_mask, B, L)
         chunk = check_internal_batch(internal_batch_size)
         x = self._prep(waves)
-        base = base.to(x.device, torch.float32).contiguous()
-        index = index.to(x.device).contiguous()
-        return self._ablate(ablation_desc(x, base, ABL_FEATURE, K, mask=index), x, K, chunk, "feature ablation")
+        base, index = _device_base(base, x), index.to(x.device).contiguous()   # locals: the descriptor holds the pointers only
+        d = ablation_desc(x, base, ABL_FEATURE, K, mask=index)
+        return self._ablate(x, K * B, chunk, functools.partial(ablation_points, d), functools.partial(ablation_accumulate, d),
+                            "feature ablation")
 
-    def _ablate(self, d: AblationDesc, x, K: int, chunk: int, what: str, points=None):
-        """The shared chunk loop: ablated rows -> forward logits -> ``fk``; then ``F(x)`` and one accumulate launch.  Every
-        chunk has ``chunk`` rows (the last one padded with copies of x), so one forward workspace serves them all.
-        ``points(row0, out)``: the rows' builder when it is not ``advh_ablation_points`` (FeaturePermutation)."""
-        B, L = x.shape
-        R = K * B
+    def _ablate(self, x, R: int, chunk: int, points, accumulate, what: str, cause: str = _ABLATION_CAUSE, value=None):
+        """The one "perturbed rows -> values -> one accumulate launch" loop: ``points(row0, rows, out)`` builds the rows
+        ``[row0, row0 + rows)`` of the ``R``, ``value(rows, row0) -> [rows]`` scores them (None: ``_row_logit``) and
+        ``accumulate(f0, fk, attr)`` turns ``f0 = value(x) [B]`` and ``fk [R]`` into the attribution.  Every chunk has
+        ``min(chunk, R)`` rows (the last one padded by ``points`` with copies of x), so one forward workspace serves them all.
+        The tensors a descriptor behind ``points`` / ``accumulate`` points into are the caller's to keep alive."""
         chunk = min(chunk, R)
-        pts = torch.empty((chunk, L), dtype=torch.float32, device=x.device)
-        fk = self._row_logits(points or (lambda row0, out: ablation_points(d, row0, chunk, out)), 0, R, pts)
-        f0 = self._row_logit(x)
+        pts = torch.empty((chunk, x.shape[1]), dtype=torch.float32, device=x.device)
+        fk = self._row_logits(lambda row0, out: points(row0, chunk, out), 0, R, pts, value)
+        f0 = (value or self._row_logit)(x)
         attr = torch.empty_like(x)
-        ablation_accumulate(d, f0, fk, attr)
-        return self._checked(attr, what, "a logit of the clips or of their ablations is not finite (check the inputs and baselines)")
+        accumulate(f0, fk, attr)
+        return self._checked(attr, what, cause)
 
-    def _row_logits(self, points, row0: int, R: int, pts: torch.Tensor) -> torch.Tensor:
-        """Logits of the perturbed rows ``[row0, row0 + R)``: ``points(first_row, pts)`` fills the ``[chunk, L]`` workspace, the
-        classifier forward runs on it, and the logits land in ``fk[:R]`` (``fk`` has whole chunks: the rows past ``R`` of the
-        last chunk are the kernels' padding, copies of x)."""
+    def _row_logits(self, points, row0: int, R: int, pts: torch.Tensor, value=None) -> torch.Tensor:
+        """Values of the perturbed rows ``[row0, row0 + R)``: ``points(first_row, pts)`` fills the ``[chunk, L]`` workspace,
+        ``value(pts, first_row)`` (None: the classifier forward, ``_row_logit``) runs on it, and the values land in ``fk[:R]``
+        (``fk`` has whole chunks: the rows past ``R`` of the last chunk are the kernels' padding, copies of x)."""
+        value = value or self._row_logit
         chunk = pts.shape[0]
         nchunk = -(-R // chunk)
         fk = torch.empty(nchunk * chunk, dtype=torch.float32, device=pts.device)
         for c in range(nchunk):
             points(row0 + c * chunk, pts)
-            fk[c * chunk:(c + 1) * chunk] = self._row_logit(pts, row0 + c * chunk)
+            fk[c * chunk:(c + 1) * chunk] = value(pts, row0 + c * chunk)
         return fk
 
     def perturbation_curve(self, waves, attributions, mode: str = "deletion", order: str = "morf", feature_mask=None, steps=None,
@@ -1394,7 +1455,7 @@ class HipAttribution:
     def _curve_upload(self, plan: dict, waves, attributions) -> None:
         x = self._prep(waves)
         plan["x"], plan["attr"] = x, self._prep(attributions)
-        plan["base"] = plan["base"].to(x.device, torch.float32).contiguous()
+        plan["base"] = _device_base(plan["base"], x)
         if plan["index"] is not None:
             plan["index"] = plan["index"].to(x.device).contiguous()
         plan["counts_dev"] = torch.from_numpy(plan["counts"]).to(x.device)
@@ -1457,7 +1518,7 @@ class HipAttribution:
         x = self._prep(waves)
         B, L = x.shape
         dev = x.device
-        base = base.to(dev, torch.float32).contiguous()
+        base = _device_base(base, x)
         index = index.to(dev).contiguous()
         kb = K * B
         G = max(1, min(P, max(GROUP_ROWS, chunk) // kb))
@@ -1514,7 +1575,7 @@ class HipAttribution:
             table[b::B, :Ks[b]] = zb                                                        # row s * B + b
         x = self._prep(waves)
         dev = x.device
-        base = base.to(dev, torch.float32).contiguous()
+        base = _device_base(base, x)
         present = torch.from_numpy(table).to(dev)
         index = index.to(dev).contiguous()
         d = coalition_desc(x, base, index, Kmax, present=present)
@@ -1582,7 +1643,7 @@ class HipAttribution:
         seed = _check_seed(seed)
         x = self._prep(waves)
         dev = x.device
-        base = base.to(dev, torch.float32).contiguous()
+        base = _device_base(base, x)
         index = index.to(dev).contiguous()
         base_of = lambda b: base[0 if base.shape[0] == 1 else b][None]
         index_of = lambda b: index[0 if index.shape[0] == 1 else b][None].long()
@@ -1680,8 +1741,8 @@ class HipAttribution:
         index = index.to(x.device).contiguous()
         pd = permutation_desc(x, index, torch.from_numpy(perm).to(x.device))
         ad = ablation_desc(x, x, ABL_FEATURE, K, mask=index)                  # the accumulate reads the mask only
-        return self._ablate(ad, x, K, chunk, "feature permutation",
-                            points=lambda row0, out: permutation_points(pd, row0, out.shape[0], out))
+        return self._ablate(x, K * B, chunk, functools.partial(permutation_points, pd), functools.partial(ablation_accumulate, ad),
+                            "feature permutation")
 
     def noise_tunnel(self, waves, attribute, nt_type: str = "smoothgrad", nt_samples: int = 5,
                      nt_samples_batch_size: Optional[int] = None, stdevs: float = 1.0, draw_baseline_from_distrib: bool = False,
@@ -1767,7 +1828,7 @@ class HipAttribution:
         attr = attributions.to(dev, torch.float32).contiguous()
         base = baselines.to(dev, torch.float32) if torch.is_tensor(baselines) else baselines
         if fused and perturb_func.multiply_by_inputs and base is not None:
-            base = check_ig_baselines(baselines, B, L).to(dev, torch.float32).contiguous()      # a number -> [1, L]
+            base = _device_base(check_ig_baselines(baselines, B, L), x)                         # a number -> [1, L]
 
         def generic(pp):
             """The chunk's ``(perturbation, perturbed rows)`` from the Python perturb_func, shapes checked."""
@@ -1827,9 +1888,6 @@ class HipAttribution:
                                max_examples_per_batch, seed, **kwargs)
 
     # ------------------------------------------------------------------ layer attributions (captum.attr.Layer*, InternalInfluence)
-    def _layer_chunks(self, B: int, n_points: int, internal_batch_size: Optional[int]) -> int:
-        return min(max(1, (internal_batch_size or 128) // B), n_points)           # whole steps per chunk, as integrated_gradients
-
     def _expand_base(self, base, x):
         return base.to(x.device, torch.float32).expand(x.shape[0], -1).contiguous()
 
@@ -1861,36 +1919,20 @@ class HipAttribution:
         ``delta[b] = sum attr[b] - (F(x_b) - F(b_b))`` with F from the two full forwards."""
         B, L = _dims(waves)
         l, base, alphas, steps = check_layer_path_args(layer, self.eg.emb.nl, baselines, B, L, n_steps, method, internal_batch_size)
-        if return_convergence_delta and not multiply_by_inputs:
-            raise NotImplementedError("the convergence delta needs multiply_by_inputs=True")
+        _check_delta(return_convergence_delta, multiply_by_inputs)
         x = self._prep(waves)
         eg = self.eg
         fx = eg.forward(x)[0].view(-1)
         hx = eg.hidden(l)
         fb = eg.forward(self._expand_base(base, x))[0].view(-1)
         hb = eg.hidden(l)
-        T, H = hx.shape[1:]
-        n = T * H
-        per = self._layer_chunks(B, n_steps, internal_batch_size)
-        npad = -(-n_steps // per) * per
-        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
-        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
-        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
-        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
-        d = _desc(hx.view(B, n), hb.view(B, n), None, npad, 0)
-        total = torch.zeros((B, n), dtype=torch.float32, device=x.device)
-        pts = torch.empty((per * B, T, H), dtype=torch.float32, device=x.device)
-        for s0 in range(0, npad, per):
-            _points(d, a_all, s0 * B, per * B, pts)
+
+        def point_gradient(pts, row0):                                          # pts [rows, T, H]: nothing below the layer runs
             eg.forward_from(l, pts)
-            g = eg.backward(self.loss_scale, to_layer=l)                        # [per*B, T, H], step-major
-            _accumulate(d, g, w_all, ACC_IG, s0 * B, per * B, total)
-        if not multiply_by_inputs:
-            return self._checked(total.view(B, T, H))
-        out = torch.empty_like(total)
-        sums = torch.empty(B, dtype=torch.float32, device=x.device) if return_convergence_delta else None
-        _accumulate(d, total, None, FIN_IG, 0, B, out, sums)
-        out = self._checked(out.view(B, T, H))
+            return eg.backward(self.loss_scale, to_layer=l)
+        out, sums = self._integrate_path(hx, hb, alphas, steps, internal_batch_size, point_gradient,
+                                         FIN_IG if multiply_by_inputs else None, return_convergence_delta)
+        out = self._checked(out)
         if not return_convergence_delta:
             return out
         return out, (sums.double() - (fx.double() - fb.double())).float()
@@ -1900,7 +1942,7 @@ class HipAttribution:
         l, base, alphas, steps = check_layer_path_args(layer, self.eg.emb.nl, baselines, B, L, n_steps, method, internal_batch_size,
                                                        extra_point)
         x = self._prep(waves)
-        return x, base.to(x.device, torch.float32).contiguous(), l, alphas, steps
+        return x, _device_base(base, x), l, alphas, steps
 
     def layer_conductance(self, waves, layer: int, baselines=None, n_steps: int = 50, method: str = "gausslegendre",
                           internal_batch_size: Optional[int] = None):
@@ -1912,8 +1954,8 @@ class HipAttribution:
         B, L = x.shape
         eg, lib = self.eg, _lib.lib()
         npts = n_steps + 1
-        per = self._layer_chunks(B, npts, internal_batch_size)
-        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
+        per = _steps_per_chunk(B, npts, internal_batch_size)
+        a_all = _step_major(alphas, B, x.device)
         d = _desc(x, base, None, npts, 0)
         # one workspace shape: a short last chunk leaves the previous chunk's (finite) points in the rows it does not use
         pts = torch.zeros((per * B, L), dtype=torch.float32, device=x.device)
@@ -1937,27 +1979,12 @@ class HipAttribution:
         """Captum's InternalInfluence: ``attr = sum_k w_k g_k`` ``[B, T, H]``, ``g_k = dF/dh_l`` at the ``n_steps`` waveform-space
         points ``b + alpha_k (x - b)`` (a full forward and a backward stopped at the layer each)."""
         x, base, l, alphas, steps = self._wave_path(waves, layer, baselines, n_steps, method, internal_batch_size, False)
-        B, L = x.shape
         eg = self.eg
-        per = self._layer_chunks(B, n_steps, internal_batch_size)
-        npad = -(-n_steps // per) * per
-        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
-        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
-        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
-        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
-        d = _desc(x, base, None, npad, 0)
-        pts = torch.empty((per * B, L), dtype=torch.float32, device=x.device)
-        total = dl = None
-        for s0 in range(0, npad, per):
-            _points(d, a_all, s0 * B, per * B, pts)
+
+        def point_gradient(pts, row0):                                          # [rows, L] -> [rows, T, H]
             eg.forward(pts)
-            g = eg.backward(self.loss_scale, to_layer=l)                        # [per*B, T, H], step-major
-            if total is None:
-                total = torch.zeros_like(g[:B])
-                flat = total.view(B, -1)
-                dl = _desc(flat, flat, None, npad, 0)                           # ACC_IG reads neither x nor the baseline
-            _accumulate(dl, g, w_all, ACC_IG, s0 * B, per * B, total)
-        return self._checked(total)
+            return eg.backward(self.loss_scale, to_layer=l)
+        return self._checked(self._integrate_path(x, base, alphas, steps, internal_batch_size, point_gradient)[0])
 
     def frames_to_wave(self, rel: torch.Tensor, L: int) -> torch.Tensor:
         """Per-frame relevance ``[B, T]`` spread to the ``L`` samples of each clip (``frame_index``): ``[B, L]`` fp32."""
@@ -2127,30 +2154,6 @@ class HipAttribution:
         self.eg.forward(x, to_layer=l)
         return self._checked_neuron(self.eg.backward(self.neuron_loss_scale, from_layer=l, neuron=box))
 
-    def _neuron_path(self, x, base, alphas, steps, n_steps, internal_batch_size, multiply_by_inputs, point_gradient):
-        """The path loop of ``integrated_gradients`` with ``point_gradient(pts) -> [rows, L]`` in the place of the logit's
-        gradient: whole steps per chunk, step-major rows, zero-weight padding steps."""
-        B, L = x.shape
-        per = self._layer_chunks(B, n_steps, internal_batch_size)
-        npad = -(-n_steps // per) * per
-        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
-        steps = np.concatenate([steps, np.zeros(npad - n_steps)])               # padding steps carry zero weight
-        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
-        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
-        d = _desc(x, base, None, npad, 0)
-        total = torch.zeros_like(x)
-        pts = torch.empty((per * B, L), dtype=torch.float32, device=x.device)
-        for s0 in range(0, npad, per):
-            _points(d, a_all, s0 * B, per * B, pts)
-            _accumulate(d, point_gradient(pts), w_all, ACC_IG, s0 * B, per * B, total)
-        out = torch.empty_like(x)
-        if multiply_by_inputs:
-            _accumulate(d, total, None, FIN_IG, 0, B, out)
-        else:
-            d.S = 1                                                             # FIN_MEAN with S = 1: the sum itself
-            _accumulate(d, total, None, FIN_MEAN, 0, B, out)
-        return self._checked_neuron(out)
-
     def _neuron_path_args(self, waves, layer, neuron, baselines, n_steps, method, internal_batch_size):
         B, L, l, box = self._neuron_args(waves, layer, neuron)
         base = check_ig_baselines(baselines, B, L)
@@ -2168,11 +2171,11 @@ class HipAttribution:
         x = self._prep(waves)
         eg, scale = self.eg, self.neuron_loss_scale
 
-        def point_gradient(pts):
+        def point_gradient(pts, row0):
             eg.forward(pts, to_layer=l)
             return eg.backward(scale, from_layer=l, neuron=box)
-        return self._neuron_path(x, base.to(x.device, torch.float32).contiguous(), alphas, steps, n_steps, internal_batch_size,
-                                 multiply_by_inputs, point_gradient)
+        return self._checked_neuron(self._integrate_path(x, _device_base(base, x), alphas, steps, internal_batch_size, point_gradient,
+                                                         FIN_IG if multiply_by_inputs else FIN_MEAN)[0])
 
     def neuron_conductance(self, waves, layer: int, neuron, baselines=None, n_steps: int = 50, method: str = "gausslegendre",
                            internal_batch_size: Optional[int] = None, multiply_by_inputs: bool = True):
@@ -2187,49 +2190,27 @@ class HipAttribution:
         x = self._prep(waves)
         eg = self.eg
 
-        def point_gradient(pts):
+        def point_gradient(pts, row0):
             eg.forward(pts)
             m = eg.neuron_values(eg.backward(self.loss_scale, to_layer=l), box)        # dF/dh_n of every row
             return eg.backward(self.neuron_loss_scale, from_layer=l, neuron=box, row_scale=m)
-        return self._neuron_path(x, base.to(x.device, torch.float32).contiguous(), alphas, steps, n_steps, internal_batch_size,
-                                 multiply_by_inputs, point_gradient)
+        return self._checked_neuron(self._integrate_path(x, _device_base(base, x), alphas, steps, internal_batch_size, point_gradient,
+                                                         FIN_IG if multiply_by_inputs else FIN_MEAN)[0])
 
     def neuron_gradient_shap(self, waves, layer: int, neuron, baselines, n_samples: int = 5, stdevs: float = 0.0,
                              multiply_by_inputs: bool = True, seed: Optional[int] = None, internal_batch_size: Optional[int] = None):
         """Captum's NeuronGradientShap: ``gradient_shap`` with ``s_n`` in the place of the logit, on the same draws
         (``shap_draws(seed, ...)``, ``philox_normal(seed, ...)``).  ``[B, L]``."""
         B, L, l, box = self._neuron_args(waves, layer, neuron)
-        if callable(baselines) and not torch.is_tensor(baselines):
-            baselines = baselines(waves) if inspect.signature(baselines).parameters else baselines()
-        base = check_shap_args(baselines, B, L, n_samples, stdevs)
-        if internal_batch_size is not None:
-            _positive_int(internal_batch_size, "internal_batch_size")
-        seed = draw_seed() if seed is None else int(seed)
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError("seed must be in [0, 2**64)")
-        S = int(n_samples)
-        idx, alpha = shap_draws(seed, B, S, base.shape[0])
+        base, S, seed, draws = self._shap_args(waves, baselines, B, L, n_samples, stdevs, seed, internal_batch_size=internal_batch_size)
         x = self._prep(waves)
-        dev = x.device
-        base = base.to(dev, torch.float32).contiguous()
-        bidx = torch.from_numpy(idx).to(dev)
-        a_all = torch.from_numpy(alpha).to(dev)
-        R = B * S
-        chunk = min(internal_batch_size or 128, R)
-        d = _desc(x, base, bidx, S, 1, float(stdevs), seed)
-        total = torch.zeros_like(x)
-        # one workspace shape: a short last chunk leaves the previous chunk's (finite) points in the rows it does not use
-        pts = torch.zeros((chunk, L), dtype=torch.float32, device=dev)
-        mode = ACC_SHAP if multiply_by_inputs else ACC_SHAP_GRAD
-        for row0 in range(0, R, chunk):
-            rows = min(chunk, R - row0)
-            _points(d, a_all, row0, rows, pts)
-            self.eg.forward(pts, to_layer=l)
-            g = self.eg.backward(self.neuron_loss_scale, from_layer=l, neuron=box)      # [chunk, L], clip-major
-            _accumulate(d, g, None, mode, row0, rows, total)
-        out = torch.empty_like(x)
-        _accumulate(d, total, None, FIN_MEAN, 0, B, out)
-        return self._checked_neuron(out)
+        eg = self.eg
+
+        def row_gradient(pts, row0, clip_major, S):
+            eg.forward(pts, to_layer=l)
+            return eg.backward(self.neuron_loss_scale, from_layer=l, neuron=box)
+        return self._checked_neuron(self._expanded_samples(x, _device_base(base, x), draws, S, stdevs, seed, multiply_by_inputs,
+                                                           internal_batch_size, row_gradient)[0])
 
     def neuron_feature_ablation(self, waves, layer: int, neuron, baselines=None, feature_mask=None,
                                 internal_batch_size: Optional[int] = None):
@@ -2239,49 +2220,15 @@ class HipAttribution:
         B, L, l, box = self._neuron_args(waves, layer, neuron)
         base = check_ig_baselines(baselines, B, L)
         index, K = feature_indices(feature_mask, B, L)
-        chunk = min(check_internal_batch(internal_batch_size), K * B)
+        chunk = check_internal_batch(internal_batch_size)
         x = self._prep(waves)
         eg = self.eg
-        base = base.to(x.device, torch.float32).contiguous()
-        index = index.to(x.device).contiguous()
+        base, index = _device_base(base, x), index.to(x.device).contiguous()   # locals: the descriptor holds the pointers only
         d = ablation_desc(x, base, ABL_FEATURE, K, mask=index)
-        value = lambda rows: eg.neuron_values(eg.forward(rows, to_layer=l), box)
-        pts = torch.empty((chunk, L), dtype=torch.float32, device=x.device)
-        nchunk = -(-K * B // chunk)
-        fk = torch.empty(nchunk * chunk, dtype=torch.float32, device=x.device)     # whole chunks: the last one padded with copies of x
-        for c in range(nchunk):
-            ablation_points(d, c * chunk, chunk, pts)
-            fk[c * chunk:(c + 1) * chunk] = value(pts)
-        attr = torch.empty_like(x)
-        ablation_accumulate(d, value(x), fk, attr)
-        return self._checked(attr, "neuron feature ablation",
-                             "the neuron's activation of the clips or of their ablations is not finite (check the inputs and baselines)")
-
-    def _ig_zero(self, waves, n_steps: int, internal_batch_size: Optional[int]):
-        x = self._prep(waves)
-        B, L = x.shape
-        alphas, steps = gauss_legendre(n_steps)
-        per = max(1, (internal_batch_size or 128) // B)            # whole steps per chunk
-        total = torch.zeros_like(x)
-        lib = _lib.lib()
-        per = min(per, n_steps)
-        npad = -(-n_steps // per) * per                              # every chunk has the same shape: one workspace
-        alphas = np.concatenate([alphas, np.full(npad - n_steps, alphas[-1])])
-        steps = np.concatenate([steps, np.zeros(npad - n_steps)])    # padding steps carry zero weight
-        a_all = torch.tensor(np.repeat(alphas, B), dtype=torch.float32, device=x.device)
-        w_all = torch.tensor(np.repeat(steps, B), dtype=torch.float32, device=x.device)
-        scaled = torch.empty((per * B, L), dtype=torch.float32, device=x.device)
-        for s0 in range(0, npad, per):
-            ns = per
-            a = a_all[s0 * B:(s0 + ns) * B]
-            _lib.check(lib.advh_scale_rows(x.data_ptr(), B, a.data_ptr(), scaled.data_ptr(), ns * B, L, 0, _st()), "advh_scale_rows")
-            self.eg.forward(scaled)
-            g = self.eg.backward(self.loss_scale)                    # [ns*B, L], step-major
-            for k in range(ns):
-                wk = w_all[(s0 + k) * B:(s0 + k + 1) * B]
-                _lib.check(lib.advh_scale_rows(g[k * B:(k + 1) * B].data_ptr(), B, wk.data_ptr(), total.data_ptr(), B, L, 1, _st()),
-                           "advh_scale_rows")
-        return self._finalize(total, x, 1)
+        return self._ablate(x, K * B, chunk, functools.partial(ablation_points, d), functools.partial(ablation_accumulate, d),
+                            "neuron feature ablation",
+                            "the neuron's activation of the clips or of their ablations is not finite (check the inputs and baselines)",
+                            value=lambda rows, row0=0: eg.neuron_values(eg.forward(rows, to_layer=l), box))
 
     def time_mask(self, attr: torch.Tensor, waves: Optional[torch.Tensor] = None):
         """``|attr| / (max|attr| + 1e-8)`` per clip and, with ``waves``, the relevant / irrelevant waveforms

@@ -32,6 +32,7 @@ Not in this engine: KernelShap, Lime, FeaturePermutation, NoiseTunnel, the metri
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Optional, Tuple
 
 import torch
@@ -278,17 +279,11 @@ class HipSpectralAttribution:
         base = check_mask_baselines(baselines, B, Fm, Tm)
         chunk = A.check_internal_batch(internal_batch_size)
         x = self._rows._prep(masks)
-        base = base.to(x.device, torch.float32).contiguous()
-        d = occlusion2d_desc(x, base, Fm, Tm, w, s, K)
-        R = K[0] * K[1] * B
-        chunk = min(chunk, R)
-        pts = torch.empty((chunk, Fm * Tm), dtype=torch.float32, device=x.device)
-        fk = self._rows._row_logits(lambda row0, out: occlusion2d_points(d, row0, chunk, out), 0, R, pts)
-        f0 = self._rows._row_logit(x)
-        attr = torch.empty_like(x)
-        occlusion2d_accumulate(d, f0, fk, attr)
-        return self._rows._checked(attr, "occlusion", "a logit of the masks or of their occlusions is not finite (check the inputs "
-                                                      "and baselines)").view(masks.shape)
+        d = occlusion2d_desc(x, A._device_base(base, x), Fm, Tm, w, s, K)
+        return self._rows._ablate(x, K[0] * K[1] * B, chunk, functools.partial(occlusion2d_points, d),
+                                  functools.partial(occlusion2d_accumulate, d), "occlusion",
+                                  "a logit of the masks or of their occlusions is not finite (check the inputs and baselines)"
+                                  ).view(masks.shape)
 
     def feature_ablation(self, masks, baselines=None, feature_mask=None, internal_batch_size: Optional[int] = None):
         """Captum's FeatureAblation; ``feature_mask``: None or integer ids ``[1, Fm, Tm]`` / ``[B, Fm, Tm]`` (``tf_feature_mask``)."""
