@@ -215,7 +215,7 @@ def test_argument_errors_of_the_ablation_entry_points():
 
 def test_ablation_kernels_do_not_spill():
     res = resources("attribution_ablation.hip")
-    for nm, forms in (("ablation_points_kernel", 2), ("ablation_accumulate_kernel", 1)):
+    for nm, forms in (("build_rows_kernel", 2), ("ablation_accumulate_kernel", 1)):
         hit = {k: v for k, v in res.items() if nm in k}
         assert len(hit) == forms, (nm, sorted(res))                       # float4 and scalar forms of the points kernel
         for k, v in hit.items():

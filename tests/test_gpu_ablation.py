@@ -86,6 +86,22 @@ def test_points_equal_the_restatement(gpu_device):
                     assert torch.equal(tail.cpu(), want), (L, bname, name, view, "tail")
 
 
+@pytest.mark.parametrize("L,B", [(1000, 9), (1001, 3)])               # float4 and scalar forms
+def test_points_second_trip_of_the_grid_stride_loop(gpu_device, L, B):
+    """One call with more items than the capped grid covers in one trip (8192 blocks x 256 threads), so the row skeleton's loop
+    wraps: Occlusion with win = stride = 1 (K = L), the smallest shapes whose wrapped part holds real rows, plus a padding tail."""
+    dev = gpu_device
+    K, pad = AT.occlusion_windows(L, 1, 1), 4
+    assert K == L and (K * B + pad) * (L // 4 if L % 4 == 0 else L) > 8192 * 256
+    x, base = syn.make_clips(B, L, seed=L), noise(B, L, 3)
+    xd, bd = x.to(dev), base.to(dev)                                     # the descriptor holds their addresses
+    d = AT.ablation_desc(xd, bd, AT.ABL_OCCLUSION, K, 1, 1, None)
+    out = torch.full((K * B + pad, L), float("nan"), device=dev)
+    AT.ablation_points(d, 0, K * B + pad, out)
+    want = torch.cat([R.ablated_batch(x, base, R.occlusion_masks(L, 1, 1)), x[[(K * B + i) % B for i in range(pad)]]])
+    assert torch.equal(out.cpu(), want)
+
+
 def test_accumulate_bit_identical_to_the_restatement(gpu_device):
     dev = gpu_device
     B = 3

@@ -326,7 +326,7 @@ def test_argument_errors_of_the_lime_entry_points():
 
 def test_lime_kernels_do_not_spill():
     res = resources("attribution_lime.hip")
-    for nm, forms in (("permutation_points_kernel", 2), ("row_similarity_kernel", 4)):
+    for nm, forms in (("build_rows_kernel", 2), ("row_similarity_kernel", 4)):
         hit = {k: v for k, v in res.items() if nm in k}
         assert len(hit) == forms, (nm, sorted(res))                       # float4 and scalar forms (x two distance modes)
         for k, v in hit.items():

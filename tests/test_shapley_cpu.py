@@ -253,7 +253,7 @@ def test_argument_errors_of_the_shapley_entry_points():
 
 def test_shapley_kernels_do_not_spill():
     res = resources("attribution_shapley.hip")
-    for nm, forms in (("coalition_points_kernel", 2), ("shapley_accumulate_kernel", 1), ("coalition_scatter_kernel", 1)):
+    for nm, forms in (("build_rows_kernel", 2), ("shapley_accumulate_kernel", 1), ("coalition_scatter_kernel", 1)):
         hit = {k: v for k, v in res.items() if nm in k}
         assert len(hit) == forms, (nm, sorted(res))                       # float4 and scalar forms of the points kernel
         for k, v in hit.items():

@@ -1,9 +1,8 @@
 // Ablated batches and the attribution sums of the perturbation attributions (Captum's Occlusion and FeatureAblation):
 // include/addvisor_hip.h, advh_ablation_points / advh_ablation_accumulate.
 //
-// Both kernels are memory-bound and tiny next to the K classifier forwards they serve (one forward row is on the order of a
-// GFLOP; building it moves ~12 B per sample), so they stay simple: grid-stride loops, float4 access when every row pointer is
-// 16-byte aligned (base pointers aligned and n % 4 == 0), a scalar path otherwise.
+// The ablated rows are a rule of the row-building skeleton, csrc/attribution_rows.h; the accumulation is one grid-stride loop
+// with one thread per (clip, sample).  Both are memory-bound and tiny next to the K classifier forwards they serve.
 //
 // Order contract: the Occlusion sum of sample (b, t) adds diff[k][b] for k = k_lo .. k_hi sequentially in increasing k from
 // 0.f and divides by the count, as Captum's total_attrib += diff * mask; weights += mask; total_attrib / weights does (adding
@@ -12,6 +11,7 @@
 #include <math.h>
 
 #include "addvisor_hip.h"
+#include "attribution_rows.h"
 #include "common.h"
 
 namespace advh {
@@ -26,45 +26,46 @@ struct AblCtx {
     int B, base_rows, mask_rows, mode, win, stride, K;
 };
 
-// Which of the samples t .. t + N - 1 of ablated row (k, b) the baseline replaces (bit j: sample t + j); k < 0 is a padding
-// row, a copy of x.  The N = 4 form reads the feature indices as one int4 (t % 4 == 0, mask row 16-byte aligned).
-template <int N>
-__device__ __forceinline__ unsigned ablated(const AblCtx& c, long k, const int32_t* mr, long t) {
-    if (k < 0) return 0u;
-    unsigned bits = 0u;
-    if (c.mode == ABL_OCCLUSION) {
-        const long lo = k * c.stride;
+// The ablated rows (csrc/attribution_rows.h): row g = k * B + b is x[b] with the baseline where sample t is in window / feature k;
+// rows g >= K * B are padding, copies of x.
+struct AblationRule {
+    AblCtx c;
+    __host__ __device__ long n() const { return c.n; }
+    struct Row {
+        long k;   // < 0: a padding row
+        const float *xr, *br;
+        const int32_t* mr;
+    };
+    __device__ __forceinline__ Row row(long g) const {
+        const long b = g % c.B, k = g < (long)c.K * c.B ? g / c.B : -1L;
+        return {k, c.x + b * c.n, c.base + (c.base_rows == 1 ? 0L : b * c.n),
+                c.mode == ABL_FEATURE ? c.mask + (c.mask_rows == 1 ? 0L : b * c.n) : nullptr};
+    }
+    // Which of the samples t .. t + N - 1 the baseline replaces (bit j: sample t + j).  The N = 4 form reads the feature indices
+    // as one int4 (t % 4 == 0, mask row 16-byte aligned).
+    template <int N>
+    __device__ __forceinline__ unsigned ablated(const Row& w, long t) const {
+        if (w.k < 0) return 0u;
+        unsigned bits = 0u;
+        if (c.mode == ABL_OCCLUSION) {
+            const long lo = w.k * c.stride;
 #pragma unroll
-        for (int j = 0; j < N; ++j) bits |= (t + j >= lo && t + j < lo + c.win) ? 1u << j : 0u;
-    } else if (N == 4) {
-        const int4 m = *(const int4*)(mr + t);
-        bits = (m.x == k ? 1u : 0u) | (m.y == k ? 2u : 0u) | (m.z == k ? 4u : 0u) | (m.w == k ? 8u : 0u);
-    } else {
-        bits = mr[t] == k ? 1u : 0u;
-    }
-    return bits;
-}
-
-// out[r][:] = ablated row g = row0 + r: base where sample t is in window / feature k = g / B, x[g % B] elsewhere
-template <bool VEC>
-__global__ __launch_bounds__(256) void ablation_points_kernel(AblCtx c, long row0, int rows, float* __restrict__ out) {
-    const long per = VEC ? c.n / 4 : c.n, total = (long)rows * per, kb = (long)c.K * c.B;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long r = i / per, q = i - r * per, g = row0 + r;
-        const long b = g % c.B, k = g < kb ? g / c.B : -1L;
-        const float* xr = c.x + b * c.n;
-        const float* br = c.base + (c.base_rows == 1 ? 0L : b * c.n);
-        const int32_t* mr = c.mode == ABL_FEATURE ? c.mask + (c.mask_rows == 1 ? 0L : b * c.n) : nullptr;
-        if (VEC) {
-            const long t = q * 4;
-            const unsigned m = ablated<4>(c, k, mr, t);
-            const float4 xv = *(const float4*)(xr + t), bv = *(const float4*)(br + t);
-            *(float4*)(out + r * c.n + t) = make_float4(m & 1u ? bv.x : xv.x, m & 2u ? bv.y : xv.y, m & 4u ? bv.z : xv.z, m & 8u ? bv.w : xv.w);
+            for (int j = 0; j < N; ++j) bits |= (t + j >= lo && t + j < lo + c.win) ? 1u << j : 0u;
+        } else if (N == 4) {
+            const int4 m = *(const int4*)(w.mr + t);
+            bits = (m.x == w.k ? 1u : 0u) | (m.y == w.k ? 2u : 0u) | (m.z == w.k ? 4u : 0u) | (m.w == w.k ? 8u : 0u);
         } else {
-            out[r * c.n + q] = ablated<1>(c, k, mr, q) ? br[q] : xr[q];
+            bits = w.mr[t] == w.k ? 1u : 0u;
         }
+        return bits;
     }
-}
+    __device__ __forceinline__ float4 quad(const Row& w, long t) const {
+        const unsigned m = ablated<4>(w, t);
+        const float4 xv = *(const float4*)(w.xr + t), bv = *(const float4*)(w.br + t);
+        return make_float4(m & 1u ? bv.x : xv.x, m & 2u ? bv.y : xv.y, m & 4u ? bv.z : xv.z, m & 8u ? bv.w : xv.w);
+    }
+    __device__ __forceinline__ float one(const Row& w, long t) const { return ablated<1>(w, t) ? w.br[t] : w.xr[t]; }
+};
 
 // attr[b][t] from f0 = F(x) [B] and fk = F(ablated) [K * B], one thread per (b, t):
 //   Occlusion:       (sum_{k = k_lo..k_hi} (f0[b] - fk[k * B + b]), increasing k) / (k_hi - k_lo + 1)
@@ -94,13 +95,6 @@ __global__ __launch_bounds__(256) void ablation_accumulate_kernel(AblCtx c, cons
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 static int ablation_ctx(const advh_ablation_desc* d, AblCtx* c) {
     if (!d || !d->x || !d->base || d->B <= 0 || d->n <= 0 || d->K <= 0) return ADVH_EINVAL;
     if (d->base_rows != 1 && d->base_rows != d->B) return ADVH_EINVAL;
@@ -120,14 +114,8 @@ static int ablation_ctx(const advh_ablation_desc* d, AblCtx* c) {
 extern "C" int advh_ablation_points(const advh_ablation_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream) {
     AblCtx c;
     if (ablation_ctx(d, &c) != ADVH_OK || !out || row0 < 0 || rows < 0) return ADVH_EINVAL;
-    if (rows == 0) return ADVH_OK;
-    const bool vec = c.n % 4 == 0 && aligned16(c.x) && aligned16(c.base) && aligned16(out) && (!c.mask || aligned16(c.mask));
-    const unsigned grid = grid_for((long)rows * (vec ? c.n / 4 : c.n));
-    if (vec)
-        hipLaunchKernelGGL(ablation_points_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, (long)row0, rows, out);
-    else
-        hipLaunchKernelGGL(ablation_points_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, (long)row0, rows, out);
-    return ADVH_LAUNCH_CHECK();
+    const bool vec = c.n % 4 == 0 && aligned16(c.x) && aligned16(c.base) && aligned16(out) && aligned16(c.mask);
+    return build_rows(AblationRule{c}, vec, (long)row0, rows, out, (hipStream_t)stream);
 }
 
 extern "C" int advh_ablation_accumulate(const advh_ablation_desc* d, const float* f0, const float* fk, float* attr, advh_stream_t stream) {

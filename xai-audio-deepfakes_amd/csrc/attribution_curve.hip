@@ -1,8 +1,9 @@
 // Perturbation curves of any attribution map (deletion / insertion AUC, AOPC in MoRF / LeRF order): include/addvisor_hip.h,
 // advh_feature_scores / advh_feature_rank / advh_curve_points / advh_curve_fold.
 //
-// Like csrc/attribution_ablation.hip these kernels are tiny next to the classifier forwards they serve, so they stay simple and
-// deterministic: no atomics, every sum and count in a fixed order, bit-identical from run to run.
+// These kernels are tiny next to the classifier forwards they serve, so they stay simple and deterministic: no atomics, every
+// sum and count in a fixed order, bit-identical from run to run.  The curve rows are a rule of the row-building skeleton,
+// csrc/attribution_rows.h.
 //
 // Order contract of the scores: score[b][k] adds the samples of feature k sequentially in increasing t from 0.f, so that a
 // sequential fp32 replay on the host gives the same bits.  One thread owns one feature; the workgroup stages SC_TILE samples
@@ -20,6 +21,7 @@
 #include <stdint.h>
 
 #include "addvisor_hip.h"
+#include "attribution_rows.h"
 #include "common.h"
 
 namespace advh {
@@ -119,52 +121,39 @@ __global__ __launch_bounds__(256) void feature_rank_kernel(const float* __restri
     }
 }
 
-struct CurveCtx {
-    const float* x;
-    const float* base;
-    const int32_t* index;   // nullptr: the identity
-    const int32_t* rank;
-    const int32_t* counts;
-    long n;
-    int B, base_rows, index_rows, K, S1, mode;
-};
-
-// The value of sample t of a curve row of clip b at count c: feature f = index[t]; switched when rank[b][f] < c.
-__device__ __forceinline__ float curve_pick(const CurveCtx& c, const int32_t* rr, int f, int count, float xv, float bv) {
-    if (f < 0 || f >= c.K) return NAN;
-    const bool switched = rr[f] < count;
-    return (switched == (c.mode == CURVE_DELETION)) ? bv : xv;
-}
-
-// out[r][:] = curve row g = row0 + r: step j = g / B of clip b = g % B; rows g >= S1 * B copy x[g % B]
-template <bool VEC>
-__global__ __launch_bounds__(256) void curve_points_kernel(CurveCtx c, long row0, int rows, float* __restrict__ out) {
-    const long per = VEC ? c.n / 4 : c.n, total = (long)rows * per, end = (long)c.S1 * c.B;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long r = i / per, q = i - r * per, g = row0 + r;
-        const long b = g % c.B;
-        const bool pad = g >= end;
-        const float* xr = c.x + b * c.n;
-        const float* br = c.base + (c.base_rows == 1 ? 0L : b * c.n);
-        const int32_t* ir = c.index ? c.index + (c.index_rows == 1 ? 0L : b * c.n) : nullptr;
-        const int32_t* rr = c.rank + b * c.K;
-        const int count = pad ? 0 : c.counts[g / c.B];
-        if (VEC) {
-            const long t = q * 4;
-            const float4 xv = *(const float4*)(xr + t);
-            if (pad) {
-                *(float4*)(out + r * c.n + t) = xv;
-                continue;
-            }
-            const float4 bv = *(const float4*)(br + t);
-            const int4 id = ir ? *(const int4*)(ir + t) : make_int4((int)t, (int)t + 1, (int)t + 2, (int)t + 3);
-            *(float4*)(out + r * c.n + t) = make_float4(curve_pick(c, rr, id.x, count, xv.x, bv.x), curve_pick(c, rr, id.y, count, xv.y, bv.y),
-                                                        curve_pick(c, rr, id.z, count, xv.z, bv.z), curve_pick(c, rr, id.w, count, xv.w, bv.w));
-        } else {
-            out[r * c.n + q] = pad ? xr[q] : curve_pick(c, rr, ir ? ir[q] : (int)q, count, xr[q], br[q]);
-        }
+// The curve rows (csrc/attribution_rows.h): row g is step j = g / B of clip b = g % B; rows g >= S1 * B are padding.
+struct CurveRule {
+    advh_curve_desc c;
+    __host__ __device__ long n() const { return c.n; }
+    struct Row {
+        bool pad;
+        int count;   // features switched at this step
+        const float *xr, *br;
+        const int32_t *ir, *rr;   // ir == nullptr: the identity index
+    };
+    __device__ __forceinline__ Row row(long g) const {
+        const long j = g / c.B, b = g - j * c.B;
+        const bool pad = g >= (long)c.S1 * c.B;
+        return {pad, pad ? 0 : c.counts[j], c.x + b * c.n, c.base + (c.base_rows == 1 ? 0L : b * c.n),
+                c.index ? c.index + (c.index_rows == 1 ? 0L : b * c.n) : nullptr, c.rank + b * c.K};
     }
-}
+    // The value of a sample of feature f: switched when rank[b][f] < count.
+    __device__ __forceinline__ float pick(const Row& w, int f, float xv, float bv) const {
+        if (f < 0 || f >= c.K) return NAN;
+        const bool switched = w.rr[f] < w.count;
+        return (switched == (c.mode == CURVE_DELETION)) ? bv : xv;
+    }
+    __device__ __forceinline__ float4 quad(const Row& w, long t) const {
+        const float4 xv = *(const float4*)(w.xr + t);
+        if (w.pad) return xv;
+        const float4 bv = *(const float4*)(w.br + t);
+        const int4 id = w.ir ? *(const int4*)(w.ir + t) : make_int4((int)t, (int)t + 1, (int)t + 2, (int)t + 3);
+        return make_float4(pick(w, id.x, xv.x, bv.x), pick(w, id.y, xv.y, bv.y), pick(w, id.z, xv.z, bv.z), pick(w, id.w, xv.w, bv.w));
+    }
+    __device__ __forceinline__ float one(const Row& w, long t) const {
+        return w.pad ? w.xr[t] : pick(w, w.ir ? w.ir[t] : (int)t, w.xr[t], w.br[t]);
+    }
+};
 
 // One thread per clip, steps in increasing j: curve[b][j] = y_j, auc and aopc accumulated in fp64 and rounded once.  Counts that
 // are not strictly increasing inside [0, K] (they live on the device: the host cannot see them) give NaN in auc and aopc.
@@ -205,13 +194,6 @@ __global__ __launch_bounds__(64) void curve_fold_kernel(const float* __restrict_
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 extern "C" int advh_feature_scores(const float* attr, const int32_t* index, int index_rows, int B, int64_t n, int K, int use_abs, int mean,
                                    float* score, advh_stream_t stream) {
     if (!attr || !score || B <= 0 || n <= 0 || K <= 0 || K > n || B > 65535) return ADVH_EINVAL;
@@ -239,15 +221,8 @@ extern "C" int advh_curve_points(const advh_curve_desc* d, int64_t row0, int row
     if (d->index ? (d->index_rows != 1 && d->index_rows != d->B) : d->K != d->n) return ADVH_EINVAL;
     if (d->mode != CURVE_DELETION && d->mode != CURVE_INSERTION) return ADVH_EINVAL;
     if (d->S1 < 1 || d->S1 > d->K + 1 || row0 < 0 || rows < 0) return ADVH_EINVAL;     // S1 strictly increasing counts fit [0, K]
-    if (rows == 0) return ADVH_OK;
-    const CurveCtx c{d->x, d->base, d->index, d->rank, d->counts, (long)d->n, d->B, d->base_rows, d->index_rows, d->K, d->S1, d->mode};
-    const bool vec = c.n % 4 == 0 && aligned16(c.x) && aligned16(c.base) && aligned16(out) && (!c.index || aligned16(c.index));
-    const unsigned grid = grid_for((long)rows * (vec ? c.n / 4 : c.n));
-    if (vec)
-        hipLaunchKernelGGL(curve_points_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, (long)row0, rows, out);
-    else
-        hipLaunchKernelGGL(curve_points_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, (long)row0, rows, out);
-    return ADVH_LAUNCH_CHECK();
+    const bool vec = d->n % 4 == 0 && aligned16(d->x) && aligned16(d->base) && aligned16(out) && aligned16(d->index);
+    return build_rows(CurveRule{*d}, vec, (long)row0, rows, out, (hipStream_t)stream);
 }
 
 extern "C" int advh_curve_fold(const float* fk, const int32_t* counts, int B, int S1, int K, int prob, int ref_last, float* curve, float* auc,

@@ -160,13 +160,6 @@ __global__ __launch_bounds__(256) void layer_conductance_kernel(const float* __r
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 ADVH_SPLIT_FLAG_SETTER(advh_split_flag_attribution_layer)
 
 extern "C" int advh_layer_inject(const float* src, int rows, int64_t n, float* resid, void* op, int split, int64_t op_lo,

@@ -2,8 +2,8 @@
 // host: include/addvisor_hip.h, advh_permutation_points / advh_row_similarity / advh_lasso_cd.
 //
 // The two kernels are memory-bound and tiny next to the classifier forwards they serve (one forward row is on the order of a
-// GFLOP), so they stay simple, as in csrc/attribution_ablation.hip: float4 access when every row pointer is 16-byte aligned
-// (base pointers aligned and n % 4 == 0), a scalar path otherwise.
+// GFLOP), so they stay simple: float4 access when every row pointer is 16-byte aligned (base pointers aligned and n % 4 == 0),
+// a scalar path otherwise.  The permuted rows are a rule of the row-building skeleton, csrc/attribution_rows.h.
 //
 // Determinism contract of advh_row_similarity: one workgroup per row; thread t adds the quads t, t + 256, ... in order, the four
 // elements of a quad in order (the scalar path visits the same elements in the same order, so both paths give the same bits), in
@@ -13,50 +13,47 @@
 #include <math.h>
 
 #include "addvisor_hip.h"
+#include "attribution_rows.h"
 #include "common.h"
 
 namespace advh {
 
 enum { SIM_COSINE = 0, SIM_EUCLIDEAN = 1 };
 
-struct PermCtx {
-    const float* x;
-    const int32_t* index;
-    const int32_t* perm;
-    long n;
-    int B, K;
-};
-
-// out[r][:] = permuted row g = row0 + r, k = g / B, b = g % B: x[perm[k][b]][t] where index[t] == k, x[b][t] elsewhere; rows
-// g >= K * B copy x[b].  A perm entry outside [0, B) gives NaN on the samples of feature k (no read outside x).
-template <bool VEC>
-__global__ __launch_bounds__(256) void permutation_points_kernel(PermCtx c, long row0, int rows, float* __restrict__ out) {
-    const long per = VEC ? c.n / 4 : c.n, total = (long)rows * per, kb = (long)c.K * c.B;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long r = i / per, q = i - r * per, g = row0 + r;
-        const long b = g % c.B, k = g < kb ? g / c.B : -1L;
+// The permuted rows (csrc/attribution_rows.h): row g = k * B + b is x[b] with x[perm[k][b]][t] where index[t] == k; rows
+// g >= K * B are padding.  A perm entry outside [0, B) gives NaN on the samples of feature k (no read outside x).
+struct PermutationRule {
+    advh_permutation_desc c;
+    __host__ __device__ long n() const { return c.n; }
+    struct Row {
+        long k;     // < 0: a padding row
+        bool bad;   // the perm entry is outside [0, B)
+        const float *xr, *pr;
+    };
+    __device__ __forceinline__ Row row(long g) const {
+        const long b = g % c.B, k = g < (long)c.K * c.B ? g / c.B : -1L;
         const int src = k >= 0 ? c.perm[g] : (int)b;                             // the table is [K][B]: entry k * B + b = g
         const bool bad = src < 0 || src >= c.B;
-        const float* xr = c.x + b * c.n;
-        const float* pr = c.x + (bad ? b : (long)src) * c.n;
-        if (VEC) {
-            const long t = q * 4;
-            float4 v = *(const float4*)(xr + t);
-            if (k >= 0) {
-                const int4 id = *(const int4*)(c.index + t);
-                const bool m0 = id.x == k, m1 = id.y == k, m2 = id.z == k, m3 = id.w == k;
-                if (m0 || m1 || m2 || m3) {
-                    const float4 pv = bad ? make_float4(NAN, NAN, NAN, NAN) : *(const float4*)(pr + t);
-                    v = make_float4(m0 ? pv.x : v.x, m1 ? pv.y : v.y, m2 ? pv.z : v.z, m3 ? pv.w : v.w);
-                }
-            }
-            *(float4*)(out + r * c.n + t) = v;
-        } else {
-            const bool m = k >= 0 && c.index[q] == k;
-            out[r * c.n + q] = m ? (bad ? NAN : pr[q]) : xr[q];
-        }
+        return {k, bad, c.x + b * c.n, c.x + (bad ? b : (long)src) * c.n};
     }
-}
+    // the partner row is read only when one of the four samples belongs to feature k
+    __device__ __forceinline__ float4 quad(const Row& w, long t) const {
+        float4 v = *(const float4*)(w.xr + t);
+        if (w.k >= 0) {
+            const int4 id = *(const int4*)(c.index + t);
+            const bool m0 = id.x == w.k, m1 = id.y == w.k, m2 = id.z == w.k, m3 = id.w == w.k;
+            if (m0 || m1 || m2 || m3) {
+                const float4 pv = w.bad ? make_float4(NAN, NAN, NAN, NAN) : *(const float4*)(w.pr + t);
+                v = make_float4(m0 ? pv.x : v.x, m1 ? pv.y : v.y, m2 ? pv.z : v.z, m3 ? pv.w : v.w);
+            }
+        }
+        return v;
+    }
+    __device__ __forceinline__ float one(const Row& w, long t) const {
+        const bool m = w.k >= 0 && c.index[t] == w.k;
+        return m ? (w.bad ? NAN : w.pr[t]) : w.xr[t];
+    }
+};
 
 // Fixed-shape workgroup sum of N fp64 values per thread (256 threads): wave64 xor tree, then (w0 + w1) + (w2 + w3).  Valid in
 // thread 0.
@@ -135,24 +132,10 @@ __global__ __launch_bounds__(256) void row_similarity_kernel(const float* __rest
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 extern "C" int advh_permutation_points(const advh_permutation_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream) {
     if (!d || !d->x || !d->index || !d->perm || !out || d->n <= 0 || d->B < 2 || d->K <= 0 || row0 < 0 || rows < 0) return ADVH_EINVAL;
-    if (rows == 0) return ADVH_OK;
-    const PermCtx c{d->x, d->index, d->perm, (long)d->n, d->B, d->K};
-    const bool vec = c.n % 4 == 0 && aligned16(c.x) && aligned16(c.index) && aligned16(out);
-    const unsigned grid = grid_for((long)rows * (vec ? c.n / 4 : c.n));
-    if (vec)
-        hipLaunchKernelGGL(permutation_points_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, (long)row0, rows, out);
-    else
-        hipLaunchKernelGGL(permutation_points_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, (long)row0, rows, out);
-    return ADVH_LAUNCH_CHECK();
+    const bool vec = d->n % 4 == 0 && aligned16(d->x) && aligned16(d->index) && aligned16(out);
+    return build_rows(PermutationRule{*d}, vec, (long)row0, rows, out, (hipStream_t)stream);
 }
 
 extern "C" int advh_row_similarity(const float* rows_ptr, const float* x, int64_t row0, int rows, int B, int64_t n, int mode,

@@ -252,13 +252,6 @@ __global__ __launch_bounds__(256) void infidelity_finalize_kernel(const double* 
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 // B * p rows must index as int (one workgroup per row)
 static inline bool chunk_ok(int B, int p) { return B > 0 && p > 0 && (int64_t)B * p <= 0x7fffffff; }
 

@@ -102,13 +102,6 @@ __global__ __launch_bounds__(256) void neuron_values_kernel(const float* __restr
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 // a selection box inside [0, T) x [0, H): non-empty, positive steps
 static inline bool box_ok(const int* b, int T, int H) {
     return b && b[0] >= 0 && b[0] < b[1] && b[1] <= T && b[2] > 0 && b[3] >= 0 && b[3] < b[4] && b[4] <= H && b[5] > 0;

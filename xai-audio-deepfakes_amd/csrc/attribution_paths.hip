@@ -271,13 +271,6 @@ __global__ __launch_bounds__(256) void nt_finalize_kernel(const double* __restri
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 static int path_ctx(const advh_path_desc* d, PathCtx* c) {
     if (!d || !d->x || !d->base || d->B <= 0 || d->S <= 0 || d->n <= 0 || d->base_rows <= 0 || (d->clip_major != 0 && d->clip_major != 1))
         return ADVH_EINVAL;

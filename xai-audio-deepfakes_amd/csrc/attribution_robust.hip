@@ -224,8 +224,6 @@ __global__ __launch_bounds__(256) void robust_first_flip_kernel(const float* __r
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
 static inline bool rows_ok(int rows, int B, int p) { return rows == B || (int64_t)rows == (int64_t)B * p; }
 
 extern "C" int advh_robust_step(const advh_robust_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream) {

@@ -1,10 +1,8 @@
 // Coalition batches and the attribution sums of the Shapley attributions (Captum's ShapleyValueSampling, ShapleyValues and
 // KernelShap): include/addvisor_hip.h, advh_coalition_points / advh_shapley_accumulate / advh_coalition_scatter.
 //
-// Like csrc/attribution_ablation.hip these kernels are memory-bound and tiny next to the classifier forwards they serve (one
-// forward row is on the order of a GFLOP; building it moves ~12 B per sample plus a table lookup), so they stay simple:
-// grid-stride loops, float4 access when every row pointer is 16-byte aligned (base pointers aligned and n % 4 == 0), a scalar
-// path otherwise.
+// The coalition rows are a rule of the row-building skeleton, csrc/attribution_rows.h; the other two kernels are grid-stride
+// loops with one thread per (clip, sample).  All are memory-bound and tiny next to the classifier forwards they serve.
 //
 // Order contract: the Shapley sum of sample (b, t) adds diff[p][rank_p(id)][b] for p = p0 .. p0 + np - 1 sequentially in
 // increasing p onto the running total, and the last call divides once (__fdiv_rn), as Captum's total_attrib += eval_diff *
@@ -13,6 +11,7 @@
 #include <math.h>
 
 #include "addvisor_hip.h"
+#include "attribution_rows.h"
 #include "common.h"
 
 namespace advh {
@@ -29,46 +28,40 @@ struct CoalCtx {
     int B, base_rows, index_rows, mode, K, P;
 };
 
-// 1 when sample t of coalition row g keeps x (its feature is in the coalition), 0 for the baseline, -1 for a feature index
-// outside [0, K) (the row gets NaN there).  Rank mode: row g = ((p0 + pl) * K + j) * B + b keeps the features of rank <= j in
-// permutation pl of the table; presence mode: row g keeps the features whose byte in table row g is non-zero.
-__device__ __forceinline__ int keeps(const CoalCtx& c, long pl, long j, long g, int id) {
-    if (id < 0 || id >= c.K) return -1;
-    if (c.mode == COAL_RANK) return c.rank[pl * c.K + id] <= j ? 1 : 0;
-    return c.present[g * c.K + id] ? 1 : 0;
-}
-
-__device__ __forceinline__ float pick(int k, float xv, float bv) { return k > 0 ? xv : k == 0 ? bv : NAN; }
-
-// out[r][:] = coalition row g = row0 + r; rows past the end of the table (rank mode: (p0 + P) * K * B, presence mode: rows)
-// copy x[g % B]
-template <bool VEC>
-__global__ __launch_bounds__(256) void coalition_points_kernel(CoalCtx c, long row0, int rows, float* __restrict__ out) {
-    const long per = VEC ? c.n / 4 : c.n, total = (long)rows * per, kb = (long)c.K * c.B;
-    const long first = c.mode == COAL_RANK ? c.p0 * kb : 0L, end = c.mode == COAL_RANK ? (c.p0 + c.P) * kb : c.rows;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long r = i / per, q = i - r * per, g = row0 + r;
-        const long b = g % c.B, rel = g - first, pl = rel / kb, j = (rel / c.B) % c.K;
-        const bool pad = g >= end;
-        const float* xr = c.x + b * c.n;
-        const float* br = c.base + (c.base_rows == 1 ? 0L : b * c.n);
-        const int32_t* ir = c.index + (c.index_rows == 1 ? 0L : b * c.n);
-        if (VEC) {
-            const long t = q * 4;
-            const float4 xv = *(const float4*)(xr + t);
-            if (pad) {
-                *(float4*)(out + r * c.n + t) = xv;
-                continue;
-            }
-            const float4 bv = *(const float4*)(br + t);
-            const int4 id = *(const int4*)(ir + t);
-            *(float4*)(out + r * c.n + t) = make_float4(pick(keeps(c, pl, j, g, id.x), xv.x, bv.x), pick(keeps(c, pl, j, g, id.y), xv.y, bv.y),
-                                                        pick(keeps(c, pl, j, g, id.z), xv.z, bv.z), pick(keeps(c, pl, j, g, id.w), xv.w, bv.w));
-        } else {
-            out[r * c.n + q] = pad ? xr[q] : pick(keeps(c, pl, j, g, ir[q]), xr[q], br[q]);
-        }
+// The coalition rows (csrc/attribution_rows.h).  Rank mode: row g = ((p0 + pl) * K + j) * B + b keeps the features of rank <= j in
+// permutation pl of the table; presence mode: row g keeps the features whose byte in table row g is non-zero.  Rows past the end
+// of the table (rank mode: (p0 + P) * K * B, presence mode: rows) are padding.
+struct CoalitionRule {
+    CoalCtx c;
+    __host__ __device__ long n() const { return c.n; }
+    struct Row {
+        long pl, j, g;
+        bool pad;
+        const float *xr, *br;
+        const int32_t* ir;
+    };
+    __device__ __forceinline__ Row row(long g) const {
+        const long kb = (long)c.K * c.B;
+        const long first = c.mode == COAL_RANK ? c.p0 * kb : 0L, end = c.mode == COAL_RANK ? (c.p0 + c.P) * kb : c.rows;
+        const long b = g % c.B, rel = g - first;
+        return {rel / kb, (rel / c.B) % c.K, g, g >= end, c.x + b * c.n, c.base + (c.base_rows == 1 ? 0L : b * c.n),
+                c.index + (c.index_rows == 1 ? 0L : b * c.n)};
     }
-}
+    // x when the feature `id` of a sample is in the row's coalition, the baseline when it is not, NaN for an id outside [0, K)
+    __device__ __forceinline__ float pick(const Row& w, int id, float xv, float bv) const {
+        if (id < 0 || id >= c.K) return NAN;
+        const bool keep = c.mode == COAL_RANK ? c.rank[w.pl * c.K + id] <= w.j : c.present[w.g * c.K + id] != 0;
+        return keep ? xv : bv;
+    }
+    __device__ __forceinline__ float4 quad(const Row& w, long t) const {
+        const float4 xv = *(const float4*)(w.xr + t);
+        if (w.pad) return xv;
+        const float4 bv = *(const float4*)(w.br + t);
+        const int4 id = *(const int4*)(w.ir + t);
+        return make_float4(pick(w, id.x, xv.x, bv.x), pick(w, id.y, xv.y, bv.y), pick(w, id.z, xv.z, bv.z), pick(w, id.w, xv.w, bv.w));
+    }
+    __device__ __forceinline__ float one(const Row& w, long t) const { return w.pad ? w.xr[t] : pick(w, w.ir[t], w.xr[t], w.br[t]); }
+};
 
 // total[b][t] += sum_{p = p0 .. p0 + np - 1, increasing} (F(row p, j, b) - F(row p, j - 1, b)), j = rank_p(index[b][t]),
 // F(row p, -1, b) = fbase[b]; fk[((p - p0) * K + j) * B + b].  fdiv > 0: total /= fdiv afterwards (one rounded division).
@@ -110,13 +103,6 @@ __global__ __launch_bounds__(256) void coalition_scatter_kernel(CoalCtx c, const
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 // the fields every entry point reads (index map and shape); `tables`: also x, base and the mode's table
 static int coalition_ctx(const advh_coalition_desc* d, bool tables, CoalCtx* c) {
     if (!d || !d->index || d->B <= 0 || d->n <= 0 || d->K <= 0) return ADVH_EINVAL;
@@ -138,14 +124,8 @@ extern "C" int advh_coalition_points(const advh_coalition_desc* d, int64_t row0,
     CoalCtx c;
     if (coalition_ctx(d, true, &c) != ADVH_OK || !out || row0 < 0 || rows < 0) return ADVH_EINVAL;
     if (c.mode == COAL_RANK && row0 < c.p0 * c.K * c.B) return ADVH_EINVAL;           // rows before the table's permutations
-    if (rows == 0) return ADVH_OK;
     const bool vec = c.n % 4 == 0 && aligned16(c.x) && aligned16(c.base) && aligned16(c.index) && aligned16(out);
-    const unsigned grid = grid_for((long)rows * (vec ? c.n / 4 : c.n));
-    if (vec)
-        hipLaunchKernelGGL(coalition_points_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, (long)row0, rows, out);
-    else
-        hipLaunchKernelGGL(coalition_points_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, (long)row0, rows, out);
-    return ADVH_LAUNCH_CHECK();
+    return build_rows(CoalitionRule{c}, vec, (long)row0, rows, out, (hipStream_t)stream);
 }
 
 extern "C" int advh_shapley_accumulate(const advh_coalition_desc* d, const float* fbase, const float* fk, int64_t p0, int np,

@@ -1,7 +1,8 @@
 // Time-frequency attributions over the STFT mask (include/addvisor_hip.h): Captum's Occlusion for a (Fm, Tm) input --
 // advh_occlusion2d_points / advh_occlusion2d_accumulate -- and the band x segment pooling of an attribution map, advh_tf_pool.
 //
-// The occlusion kernels are the 2-D form of csrc/attribution_ablation.hip and keep its contract: memory-bound grid-stride loops,
+// The occlusion kernels are the 2-D form of csrc/attribution_ablation.hip and keep its contract: the occluded rows are a rule of
+// the row-building skeleton (csrc/attribution_rows.h; scalar form only), the accumulation a memory-bound grid-stride loop, both
 // tiny next to the classifier forwards they serve; the sum of bin (b, f, t) adds diff[k][b] over the windows k = kf * Kt + kt that
 // cover it sequentially in increasing k from 0.f and divides by their count, as Captum's total_attrib += diff * mask;
 // weights += mask; total_attrib / weights does.  No prefix sums, no atomics.
@@ -9,32 +10,35 @@
 #include <math.h>
 
 #include "addvisor_hip.h"
+#include "attribution_rows.h"
 #include "common.h"
 
 namespace advh {
 
-struct Occ2dCtx {
-    const float* x;
-    const float* base;
-    int B, base_rows, Fm, Tm, wf, wt, sf, st, Kf, Kt;
-};
-
-// out[r][:] = occluded row g = row0 + r: base inside window k = g / B (kf = k / Kt, kt = k % Kt), x[g % B] elsewhere
-__global__ __launch_bounds__(256) void occlusion2d_points_kernel(Occ2dCtx c, long row0, int rows, float* __restrict__ out) {
-    const long n = (long)c.Fm * c.Tm, total = (long)rows * n, kb = (long)c.Kf * c.Kt * c.B;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long r = i / n, q = i - r * n, g = row0 + r;
-        const long b = g % c.B;
+// The occluded rows (csrc/attribution_rows.h): row g = k * B + b is x[b] with the baseline inside window k (kf = k / Kt,
+// kt = k % Kt); rows g >= Kf * Kt * B are padding.
+struct Occlusion2dRule {
+    advh_occlusion2d_desc c;
+    __host__ __device__ long n() const { return (long)c.Fm * c.Tm; }
+    struct Row {
+        bool pad;
+        long k;   // the window (meaningless for a padding row)
+        const float *xr, *br;
+    };
+    __device__ __forceinline__ Row row(long g) const {
+        const long k = g / c.B, b = g - k * c.B;
+        return {g >= (long)c.Kf * c.Kt * c.B, k, c.x + b * n(), c.base + (c.base_rows == 1 ? 0L : b * n())};
+    }
+    __device__ __forceinline__ float one(const Row& w, long q) const {
         const int f = (int)(q / c.Tm), t = (int)(q - (long)f * c.Tm);
         bool in = false;
-        if (g < kb) {
-            const long k = g / c.B;
-            const int f0 = (int)(k / c.Kt) * c.sf, t0 = (int)(k % c.Kt) * c.st;
-            in = f >= f0 && f < f0 + c.wf && t >= t0 && t < t0 + c.wt;
+        if (!w.pad) {
+            const int f0 = (int)(w.k / c.Kt) * c.sf, t0 = (int)(w.k % c.Kt) * c.st;
+            in = (f >= f0) & (f < f0 + c.wf) & (t >= t0) & (t < t0 + c.wt);   // no short circuit: one straight-line test
         }
-        out[i] = in ? c.base[(c.base_rows == 1 ? 0L : b * n) + q] : c.x[b * n + q];
+        return in ? w.br[q] : w.xr[q];
     }
-}
+};
 
 // the windows covering coordinate p of an axis: [lo, hi]
 __device__ __forceinline__ void covering(int p, int w, int s, int K, int& lo, int& hi) {
@@ -43,8 +47,8 @@ __device__ __forceinline__ void covering(int p, int w, int s, int K, int& lo, in
 }
 
 // attr[b][f][t] = (sum over kf = kf_lo..kf_hi, kt = kt_lo..kt_hi of f0[b] - fk[(kf * Kt + kt) * B + b], increasing k) / count
-__global__ __launch_bounds__(256) void occlusion2d_accumulate_kernel(Occ2dCtx c, const float* __restrict__ f0, const float* __restrict__ fk,
-                                                                     float* __restrict__ attr) {
+__global__ __launch_bounds__(256) void occlusion2d_accumulate_kernel(advh_occlusion2d_desc c, const float* __restrict__ f0,
+                                                                     const float* __restrict__ fk, float* __restrict__ attr) {
     const long n = (long)c.Fm * c.Tm, total = (long)c.B * n;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long b = i / n, q = i - b * n;
@@ -89,40 +93,28 @@ __global__ __launch_bounds__(256) void tf_pool_kernel(const float* __restrict__ 
 
 using namespace advh;
 
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 static bool axis_ok(int n, int w, int s, int K) {
     if (n < 1 || w < 1 || s < 1 || w > n || (s > w && w < n)) return false;
     return K == (n - w + s - 1) / s + 1;
 }
 
-static int occlusion2d_ctx(const advh_occlusion2d_desc* d, Occ2dCtx* c) {
-    if (!d || !d->x || !d->base || d->B <= 0) return ADVH_EINVAL;
-    if (d->base_rows != 1 && d->base_rows != d->B) return ADVH_EINVAL;
-    if (!axis_ok(d->Fm, d->wf, d->sf, d->Kf) || !axis_ok(d->Tm, d->wt, d->st, d->Kt)) return ADVH_EINVAL;
-    if ((long)d->Kf * d->Kt > 0x7fffffffL / d->B) return ADVH_EINVAL;
-    *c = Occ2dCtx{d->x, d->base, d->B, d->base_rows, d->Fm, d->Tm, d->wf, d->wt, d->sf, d->st, d->Kf, d->Kt};
-    return ADVH_OK;
+static bool occlusion2d_ok(const advh_occlusion2d_desc* d) {
+    if (!d || !d->x || !d->base || d->B <= 0) return false;
+    if (d->base_rows != 1 && d->base_rows != d->B) return false;
+    if (!axis_ok(d->Fm, d->wf, d->sf, d->Kf) || !axis_ok(d->Tm, d->wt, d->st, d->Kt)) return false;
+    return (long)d->Kf * d->Kt <= 0x7fffffffL / d->B;
 }
 
 extern "C" int advh_occlusion2d_points(const advh_occlusion2d_desc* d, int64_t row0, int rows, float* out, advh_stream_t stream) {
-    Occ2dCtx c;
-    if (occlusion2d_ctx(d, &c) != ADVH_OK || !out || row0 < 0 || rows < 0) return ADVH_EINVAL;
-    if (rows == 0) return ADVH_OK;
-    hipLaunchKernelGGL(occlusion2d_points_kernel, dim3(grid_for((long)rows * c.Fm * c.Tm)), dim3(256), 0, (hipStream_t)stream, c,
-                       (long)row0, rows, out);
-    return ADVH_LAUNCH_CHECK();
+    if (!occlusion2d_ok(d) || !out || row0 < 0 || rows < 0) return ADVH_EINVAL;
+    return build_rows<false>(Occlusion2dRule{*d}, false, (long)row0, rows, out, (hipStream_t)stream);
 }
 
 extern "C" int advh_occlusion2d_accumulate(const advh_occlusion2d_desc* d, const float* f0, const float* fk, float* attr,
                                            advh_stream_t stream) {
-    Occ2dCtx c;
-    if (occlusion2d_ctx(d, &c) != ADVH_OK || !f0 || !fk || !attr) return ADVH_EINVAL;
-    hipLaunchKernelGGL(occlusion2d_accumulate_kernel, dim3(grid_for((long)c.B * c.Fm * c.Tm)), dim3(256), 0, (hipStream_t)stream, c, f0,
-                       fk, attr);
+    if (!occlusion2d_ok(d) || !f0 || !fk || !attr) return ADVH_EINVAL;
+    hipLaunchKernelGGL(occlusion2d_accumulate_kernel, dim3(grid_for((long)d->B * d->Fm * d->Tm)), dim3(256), 0, (hipStream_t)stream, *d,
+                       f0, fk, attr);
     return ADVH_LAUNCH_CHECK();
 }
 

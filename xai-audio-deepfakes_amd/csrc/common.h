@@ -52,3 +52,12 @@ inline int advh_ensure_lds(const void* fn, int bytes = 160 * 1024) {
 }
 
 #define ADVH_LAUNCH_CHECK() (hipGetLastError() == hipSuccess ? ADVH_OK : ADVH_ELAUNCH)
+
+// The precondition of a float4 / int4 access through p.  nullptr (an optional pointer that is absent) passes.
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// Blocks of 256 threads for a grid-stride loop over `work` items: at least one, at most `cap`.
+inline unsigned grid_for(long work, long cap = 8192) {
+    const long blocks = (work + 255) / 256;
+    return (unsigned)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
+}

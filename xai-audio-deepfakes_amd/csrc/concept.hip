@@ -222,12 +222,7 @@ __global__ __launch_bounds__(256) void time_pool_kernel(const float* __restrict_
 
 using namespace advh;
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static inline unsigned grid_for(long work) {
-    long blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 1 ? 1 : blocks > 16384 ? 16384 : blocks);
-}
+constexpr long GRID_CAP = 16384;   // blocks of the grid-stride kernels (twice common.h's default)
 
 static bool gram_args_ok(int M, int N, int64_t F) { return M > 0 && N > 0 && F > 0 && M <= (1 << 20) && N <= (1 << 20) && F <= (1LL << 40); }
 
@@ -254,7 +249,7 @@ extern "C" int advh_concept_gram(const float* X, int64_t ldx, const float* Y, in
         hipLaunchKernelGGL(gram_partial_kernel<false>, grid, dim3(256), 0, s, X, (long)ldx, Y, (long)ldy, M, N, (long)F, p.slab, p.bn, symmetric,
                            workspace);
     if (ADVH_LAUNCH_CHECK() != ADVH_OK) return ADVH_ELAUNCH;
-    hipLaunchKernelGGL(gram_fold_kernel, dim3(grid_for((long)M * N)), dim3(256), 0, s, workspace, M, N, p.nslab, symmetric, G);
+    hipLaunchKernelGGL(gram_fold_kernel, dim3(grid_for((long)M * N, GRID_CAP)), dim3(256), 0, s, workspace, M, N, p.nslab, symmetric, G);
     return ADVH_LAUNCH_CHECK();
 }
 
@@ -267,9 +262,9 @@ extern "C" int advh_concept_combine(const float* A, const float* X, int64_t ldx,
     for (int c0 = 0; c0 < C; c0 += CB) {
         const int nc = C - c0 < CB ? C - c0 : CB;
         if (vec)
-            hipLaunchKernelGGL(combine_kernel<4>, dim3(grid_for((long)F / 4)), dim3(256), 0, s, A, X, (long)ldx, c0, nc, N, (long)F, W, (long)ldw);
+            hipLaunchKernelGGL(combine_kernel<4>, dim3(grid_for((long)F / 4, GRID_CAP)), dim3(256), 0, s, A, X, (long)ldx, c0, nc, N, (long)F, W, (long)ldw);
         else
-            hipLaunchKernelGGL(combine_kernel<1>, dim3(grid_for((long)F)), dim3(256), 0, s, A, X, (long)ldx, c0, nc, N, (long)F, W, (long)ldw);
+            hipLaunchKernelGGL(combine_kernel<1>, dim3(grid_for((long)F, GRID_CAP)), dim3(256), 0, s, A, X, (long)ldx, c0, nc, N, (long)F, W, (long)ldw);
         if (ADVH_LAUNCH_CHECK() != ADVH_OK) return ADVH_ELAUNCH;
     }
     return ADVH_OK;
@@ -278,6 +273,6 @@ extern "C" int advh_concept_combine(const float* A, const float* X, int64_t ldx,
 extern "C" int advh_concept_time_pool(const float* X, int64_t R, int T, int H, int mode, float* out, advh_stream_t stream) {
     if (!X || !out || R <= 0 || T <= 0 || H <= 0 || (mode != 0 && mode != 1) || R > (1LL << 40)) return ADVH_EINVAL;
     const float inv_t = (float)(1.0 / (double)T);
-    hipLaunchKernelGGL(time_pool_kernel, dim3(grid_for((long)R * H)), dim3(256), 0, (hipStream_t)stream, X, (long)R, T, H, mode, inv_t, out);
+    hipLaunchKernelGGL(time_pool_kernel, dim3(grid_for((long)R * H, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, X, (long)R, T, H, mode, inv_t, out);
     return ADVH_LAUNCH_CHECK();
 }
