@@ -243,3 +243,94 @@ def test_captum_front_end(gpu_device, tiny_runtime):
     assert torch.equal(ig, i2) and torch.equal(igd, id2)
     with pytest.raises(NotImplementedError):
         GradientShap(model).attribute(x, baselines=dist, target=0)
+
+
+def misaligned(t):
+    """A contiguous copy of ``t`` whose data pointer is 4 bytes past a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 != 0
+    return v
+
+
+U24 = 2.0 ** -24                                                          # unit roundoff of fp32
+
+
+@pytest.mark.parametrize("n,shift", [(1000, False), (1001, False), (1000, True)], ids=["float4", "scalar", "misaligned"])
+def test_path_accumulate_kernel_modes(gpu_device, n, shift):
+    """advh_attr_path_accumulate called directly, its five modes with ``row_sum`` where it is allowed, against an fp64 numpy
+    restatement: B = 3 clips, S = 4 rows per clip, two chunks [0, 5) and [5, 12) that cut a clip's (a step's) rows.
+
+    Bars, from the arithmetic: an element of ``total`` is a sum of at most R products of fp32 values (the fp32 difference
+    x~ - b counts as one such value) added in order, so it is within (R + 2) * 2^-24 * sum |terms| of the fp64 sum of the same
+    terms (one rounding of the factor, one of the product, at most R of the running sum); a row sum over n terms within
+    (n + 2) * 2^-24 * sum |terms|.  The running sums start from a non-zero ``total``, which counts as one of the R terms
+    (R = S + 1).  With sigma != 0 the restatement forms x~ = x + sigma * z unfused where the kernel may fuse
+    it: both lie within 2^-24 (|x~| + |sigma z|) of the exact value, which adds 2^-22 * sum (|x| + |sigma z|) |grad| (zero at
+    sigma = 0)."""
+    dev = gpu_device
+    B, S, rows = 3, 4, 12
+    place = (lambda t: misaligned(t.to(dev))) if shift else (lambda t: t.to(dev).contiguous())
+    gen = torch.Generator().manual_seed(n + 7 * shift)
+    x, base = torch.randn(B, n, generator=gen), torch.randn(5, n, generator=gen)
+    grad, w = torch.randn(rows, n, generator=gen), torch.rand(rows, generator=gen)
+    tot0 = torch.randn(B, n, generator=gen)
+    bidx = torch.tensor([4, 0, 2, 2, 1, 3, 0, 4, 1, 1, 3, 0], dtype=torch.int32)
+    xd, gd, wd, bid = place(x), place(grad), w.to(dev), bidx.to(dev)
+    x64, g64, w64 = x.double().numpy(), grad.double().numpy(), w.double().numpy()
+    chunks = ((0, 5), (5, 7))
+
+    def run(desc, mode, w_):
+        total = place(tot0)
+        sums = torch.full((rows,), 7.0, device=dev)
+        for r0, nr in chunks:
+            AT._accumulate(desc, gd[r0:r0 + nr], w_, mode, r0, nr, total, None if mode == AT.ACC_IG else sums)
+        return total.cpu().double().numpy(), sums.cpu().double().numpy()
+
+    def check(what, got, ref, mag, terms):
+        err, bar = np.abs(got - ref), (terms + 2) * U24 * mag
+        print(f"{what} n={n} shift={shift}: max err / bar {np.max(err / np.maximum(bar, 1e-300)):.3f}, max |ref| {np.abs(ref).max():.3e}")
+        assert np.all(err <= bar), (what, float(err.max()))
+
+    # ACC_IG: step-major rows g = s * B + b, total[b] += w[g] * grad[g]
+    bd = place(base[:B])
+    got, _ = run(AT._desc(xd, bd, None, S, 0), AT.ACC_IG, wd)
+    terms = (w64[:, None] * g64).reshape(S, B, n)
+    check("ACC_IG", got, tot0.double().numpy() + terms.sum(0), np.abs(tot0.double().numpy()) + np.abs(terms).sum(0), S + 1)
+
+    # ACC_SHAP / ACC_SHAP_GRAD: clip-major rows g = b * S + s, gathered baselines, x~ = x + sigma * N(seed, g, :)
+    b5 = place(base)
+    for sigma in (0.0, 0.25):
+        seed = 11
+        z = AT.philox_normal(seed, 0, rows, n, dev).cpu().numpy() if sigma else np.zeros((rows, n), np.float32)
+        xt = np.repeat(x.numpy(), S, axis=0) + (np.float32(sigma) * z).astype(np.float32)
+        d64 = (xt - base.numpy()[bidx.numpy()]).astype(np.float64)         # the fp32 difference, as the kernel forms it
+        extra = 4 * U24 * (np.abs(np.repeat(x64, S, axis=0)) + np.abs(sigma * z)) * np.abs(g64) * (sigma != 0)
+        desc = AT._desc(xd, b5, bid, S, 1, sigma, seed)
+        for mode, terms in ((AT.ACC_SHAP, d64 * g64), (AT.ACC_SHAP_GRAD, g64)):
+            got, sums = run(desc, mode, None)
+            ex = extra if mode == AT.ACC_SHAP else 0 * extra
+            t3, e3 = terms.reshape(B, S, n), ex.reshape(B, S, n)
+            ref, mag = tot0.double().numpy() + t3.sum(1), np.abs(tot0.double().numpy()) + np.abs(t3).sum(1)
+            err, bar = np.abs(got - ref), (S + 3) * U24 * mag + e3.sum(1)
+            print(f"mode {mode} sigma={sigma} n={n} shift={shift}: max err / bar {np.max(err / bar):.3f}")
+            assert np.all(err <= bar), (mode, sigma, float(err.max()))
+            rt = d64 * g64                                                # both modes report the row's (x~ - b) . grad
+            serr, sbar = np.abs(sums - rt.sum(1)), (n + 2) * U24 * np.abs(rt).sum(1) + extra.sum(1)
+            print(f"mode {mode} sigma={sigma} row sums: max err / bar {np.max(serr / sbar):.3f}")
+            assert np.all(serr <= sbar), (mode, sigma, float(serr.max()))
+
+    # FIN_IG: out = (x - b) * total, row sums of out;  FIN_MEAN: out = total / S
+    td = place(tot0)
+    for brows in (B, 1):
+        bd = place(base[:brows])
+        out, sums = place(torch.zeros(B, n)), torch.full((B,), 7.0, device=dev)
+        AT._accumulate(AT._desc(xd, bd, None, S, 0), td, None, AT.FIN_IG, 0, B, out, sums)
+        terms = (x.numpy() - base.numpy()[:brows]).astype(np.float64) * tot0.double().numpy()
+        check(f"FIN_IG base_rows={brows}", out.cpu().double().numpy(), terms, np.abs(terms), 1)
+        check(f"FIN_IG base_rows={brows} row sums", sums.cpu().double().numpy(), terms.sum(1), np.abs(terms).sum(1), n)
+    out = place(torch.zeros(B, n))
+    AT._accumulate(AT._desc(xd, bd, None, S, 0), td, None, AT.FIN_MEAN, 0, B, out)
+    terms = tot0.double().numpy() / S
+    check("FIN_MEAN", out.cpu().double().numpy(), terms, np.abs(terms), 1)

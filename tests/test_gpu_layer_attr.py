@@ -332,3 +332,92 @@ def test_captum_front_end(gpu_device, tiny_runtime):
         assert len(out) == 3
         for p in out:
             assert p.shape == (B, 1) and bool(((p >= 0) & (p <= 1)).all())
+
+
+def misaligned(t):
+    """A contiguous copy of ``t`` whose data pointer is 4 bytes past a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 != 0
+    return v
+
+
+KERNEL_SHAPES = [(7 * 8, False), (7 * 6, False), (7 * 8, True)]           # float4 form, scalar form (n % 4 != 0), misaligned base
+KERNEL_IDS = ["float4", "scalar", "misaligned"]
+
+
+@pytest.mark.parametrize("n,shift", KERNEL_SHAPES, ids=KERNEL_IDS)
+def test_layer_inject_kernel(gpu_device, n, shift):
+    """advh_layer_inject called directly: the residual copy and the fp16 / split operand are conversions of the input, so they
+    compare bit for bit with the input, ``.half()`` and the host packer ``split_planes``."""
+    from addvisor_hip.gemm import split_planes
+    _lib.init()
+    dev, rows = gpu_device, 3
+    src = torch.randn(rows, n, generator=torch.Generator().manual_seed(n))
+    src[0, :6] = torch.tensor([0.0, -0.0, 3e-5, -6.2e-5, 65504.0, -1234.567])      # below the hi plane's flush threshold, the edge
+    sd = misaligned(src.to(dev)) if shift else src.to(dev)
+    st = torch.cuda.current_stream().cuda_stream
+    for split in (None, 0, 1):
+        resid = torch.full((rows, n), 7.0, device=dev)
+        op = None if split is None else torch.full((2, rows, n), 7.0, dtype=torch.float16, device=dev)
+        _lib.check(_lib.lib().advh_layer_inject(sd.data_ptr(), rows, n, resid.data_ptr(), None if op is None else op.data_ptr(),
+                                                int(bool(split)), rows * n if split else 0, st), "advh_layer_inject")
+        assert torch.equal(resid.cpu().view(torch.int32), src.view(torch.int32)), split
+        if split == 0:
+            assert torch.equal(op[0].cpu().view(torch.int16), src.half().view(torch.int16))
+            assert bool((op[1] == 7.0).all())                             # the fp16 form writes no second plane
+        elif split == 1:
+            assert torch.equal(op.cpu().view(torch.int16), split_planes(src).view(torch.int16))
+
+
+def fma32(a, b, c):
+    """The correctly rounded float32 of ``a * b + c`` for float32 arrays: the product is exact in float64, TwoSum gives the
+    float64 sum and its exact error, the sum is moved to the odd neighbour when it is inexact (round to odd), and the final
+    rounding to float32 then equals a single rounding of the exact value (53 >= 24 + 2 bits)."""
+    import numpy as np
+    p, c64 = a.astype(np.float64) * b.astype(np.float64), c.astype(np.float64)
+    s = p + c64
+    t = s - p
+    e = (p - (s - t)) + (c64 - t)                                         # s + e == p + c exactly
+    bits = s.view(np.int64)
+    fix = (e != 0) & ((bits & 1) == 0)
+    bits = np.where(fix, np.where((e > 0) == (s > 0), bits + 1, bits - 1), bits)
+    return bits.view(np.float64).astype(np.float32)
+
+
+@pytest.mark.parametrize("n,shift", KERNEL_SHAPES, ids=KERNEL_IDS)
+def test_layer_conductance_kernel(gpu_device, n, shift):
+    """advh_layer_conductance_accumulate called directly: three steps in two chunks (2 + 1), the last chunk with
+    ngrad = steps - 1.  The kernel runs a fixed sequence of fp32 operations per element -- the rounded difference
+    ``act[k] - pa``, then one fused multiply-add into the total -- so it compares bit for bit with a float32 numpy replay of
+    that sequence.  (A replay that rounds the product before the add does not match, before or after the lane-pack rewrite:
+    the step has always compiled to a fused multiply-add, in both forms; the kernel now says so with ``fmaf``.)"""
+    import numpy as np
+    _lib.init()
+    dev, nb = gpu_device, 3
+    gen = torch.Generator().manual_seed(100 + n)
+    act, grad = torch.randn(3, nb, n, generator=gen), torch.randn(3, nb, n, generator=gen)
+    tot0 = torch.randn(nb, n, generator=gen)
+    place = (lambda t: misaligned(t.to(dev))) if shift else (lambda t: t.to(dev).contiguous())
+    total, pg, pa = place(tot0), place(torch.full((nb, n), 7.0)), place(torch.full((nb, n), 7.0))
+    st = torch.cuda.current_stream().cuda_stream
+    for k0, steps, ngrad, first in ((0, 2, 2, 1), (2, 1, 0, 0)):
+        a, g = place(act[k0:k0 + steps]), place(grad[k0:k0 + steps])
+        _lib.check(_lib.lib().advh_layer_conductance_accumulate(g.data_ptr() if ngrad else None, a.data_ptr(), nb, n, steps, ngrad, first,
+                                                                pg.data_ptr(), pa.data_ptr(), total.data_ptr(), st),
+                   "advh_layer_conductance_accumulate")
+    A, G = act.numpy(), grad.numpy()
+    acc = tot0.numpy().copy()
+    rpg, rpa = np.zeros_like(acc), np.zeros_like(acc)
+    for k in range(3):
+        if k > 0:
+            acc = fma32(rpg, A[k] - rpa, acc)                             # the float32 difference rounds on its own
+        rpa = A[k]
+        if k < 2:
+            rpg = G[k]
+    assert acc.dtype == np.float32
+    for what, got, ref in (("total", total, acc), ("prev_grad", pg, rpg), ("prev_act", pa, rpa)):
+        diff = int((got.cpu().numpy().view(np.uint32) != ref.view(np.uint32)).sum())
+        print(f"conductance {what} n={n} shift={shift}: {diff} of {ref.size} words differ")
+        assert diff == 0, what

@@ -146,17 +146,12 @@ extern "C" int advh_row_similarity(const float* rows_ptr, const float* x, int64_
     const double w = kernel_width, inv_2w2 = 1.0 / (2.0 * w * w);
     const bool vec = n % 4 == 0 && aligned16(rows_ptr) && aligned16(x);
     const hipStream_t s = (hipStream_t)stream;
-    if (mode == SIM_COSINE) {
-        if (vec)
-            hipLaunchKernelGGL((row_similarity_kernel<SIM_COSINE, true>), dim3(rows), dim3(256), 0, s, rows_ptr, x, (long)row0, B, (long)n, inv_2w2, sim);
-        else
-            hipLaunchKernelGGL((row_similarity_kernel<SIM_COSINE, false>), dim3(rows), dim3(256), 0, s, rows_ptr, x, (long)row0, B, (long)n, inv_2w2, sim);
-    } else {
-        if (vec)
-            hipLaunchKernelGGL((row_similarity_kernel<SIM_EUCLIDEAN, true>), dim3(rows), dim3(256), 0, s, rows_ptr, x, (long)row0, B, (long)n, inv_2w2, sim);
-        else
-            hipLaunchKernelGGL((row_similarity_kernel<SIM_EUCLIDEAN, false>), dim3(rows), dim3(256), 0, s, rows_ptr, x, (long)row0, B, (long)n, inv_2w2, sim);
-    }
+    if (mode == SIM_COSINE)
+        launch_vec(vec, row_similarity_kernel<SIM_COSINE, true>, row_similarity_kernel<SIM_COSINE, false>, dim3(rows), s, rows_ptr, x, row0, B, n,
+                   inv_2w2, sim);
+    else
+        launch_vec(vec, row_similarity_kernel<SIM_EUCLIDEAN, true>, row_similarity_kernel<SIM_EUCLIDEAN, false>, dim3(rows), s, rows_ptr, x, row0,
+                   B, n, inv_2w2, sim);
     return ADVH_LAUNCH_CHECK();
 }
 

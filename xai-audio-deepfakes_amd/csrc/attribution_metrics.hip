@@ -3,19 +3,19 @@
 // samples, the per-row dot products and norms, and the per-clip folds.
 //
 // These kernels move ~12 B per sample per row next to a forward (or a whole attribution) per row, so they stay simple:
-// grid-stride loops, one workgroup per row for the row reductions, float4 access when every row pointer is 16-byte aligned
-// (base pointers aligned and n % 4 == 0), a scalar path otherwise.
+// grid-stride loops, one workgroup per row for the row reductions, and the quad walkers of attribution_lanes.h, which states
+// the float4 / scalar rule (float4 when base pointers are aligned and n % 4 == 0; both forms visit the same elements in the same
+// order and give the same bits) and the row tree.
 //
 // Determinism contract: the noise of element (g, j) is a pure function of (seed, g, j) with the global (clip, sample) row
-// g = b * S + s0 + s' (the words of advh_philox_normal), so a row does not depend on the chunking.  Every row sum is a
-// fixed-shape tree in one workgroup: thread t adds the quads t, t + 256, ... in order, the four elements of a quad in order
-// (the scalar path visits the same elements in the same order, so both paths give the same bits), then a wave64 __shfl_xor
-// tree and the four waves as (w0 + w1) + (w2 + w3).  The per-clip folds run one thread per clip, samples in increasing order.
-// No atomics.
+// g = b * S + s0 + s' (the words of advh_philox_normal), so a row does not depend on the chunking.  Every row sum is the row tree
+// in one workgroup: thread t adds the quads t, t + 256, ... in order, the four elements of a quad in order, then the tree.  The
+// per-clip folds run one thread per clip, samples in increasing order.  No atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "addvisor_hip.h"
+#include "attribution_lanes.h"
 #include "common.h"
 #include "philox.h"
 
@@ -38,22 +38,6 @@ struct MetricCtx {
     int B, S, s0, p, base_rows, mode, mul;
     float scale;
 };
-
-__device__ __forceinline__ float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }
-
-// Fixed-shape workgroup reduction of one value per thread (256 threads): wave64 xor tree, then (w0 + w1) + (w2 + w3); the
-// maximum instead of the sum when take_max.  The result is valid in thread 0.
-__device__ __forceinline__ float block_reduce(float s, bool take_max) {
-    __shared__ float red[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float t = __shfl_xor(s, o, 64);
-        s = take_max ? nanmax(s, t) : s + t;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return take_max ? nanmax(nanmax(red[0], red[1]), nanmax(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // One element of a perturbed row: v = x + r * (2u - 1) (uniform; 2u - 1 is exact) or v = x - sigma * z (Gaussian), and in the
 // Gaussian mode its term of the dot product, pert * a, with pert = sigma * z or (multiply_by_inputs) the decorator's
@@ -93,32 +77,19 @@ __global__ __launch_bounds__(256) void metric_rows_kernel(MetricCtx c, long row0
         } else {
             z = philox_normal4(c.seed, g, q);
         }
-        const float zk[4] = {z.x, z.y, z.z, z.w};
-        if (VEC) {
-            const float4 xv = *(const float4*)(xr + q * 4);
-            const float4 av = ar ? *(const float4*)(ar + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 bv = br ? *(const float4*)(br + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float xk[4] = {xv.x, xv.y, xv.z, xv.w}, ak[4] = {av.x, av.y, av.z, av.w}, bk[4] = {bv.x, bv.y, bv.z, bv.w};
-            float o[4];
+        const lanes<4> zv = {{z.x, z.y, z.z, z.w}};
+        const lanes<4> xv = load_quad<VEC>(xr, q, c.n), av = load_quad_or<VEC>(ar, q, c.n), bv = load_quad_or<VEC>(br, q, c.n);
+        lanes<4> o;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float t = 0.f;
-                o[k] = metric_elem(c, xk[k], ak[k], bk[k], zk[k], &t);
-                if (c.mode == MR_GAUSS) s = s + t;
-            }
-            *(float4*)(orow + q * 4) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-            for (int k = 0; k < 4; ++k) {
-                const long j = q * 4 + k;
-                if (j >= c.n) break;
-                float t = 0.f;
-                orow[j] = metric_elem(c, xr[j], ar ? ar[j] : 0.f, br ? br[j] : 0.f, zk[k], &t);
-                if (c.mode == MR_GAUSS) s = s + t;
-            }
+        for (int k = 0; k < 4; ++k) {
+            float t = 0.f;
+            o[k] = metric_elem(c, xv[k], av[k], bv[k], zv[k], &t);
+            if (c.mode == MR_GAUSS && quad_lane<VEC>(q, k, c.n)) s = s + t;
         }
+        store_quad<VEC>(orow, q, c.n, o);
     }
     if (c.mode == MR_GAUSS) {
-        s = block_reduce(s, false);
+        s = block_sum(s);
         if (threadIdx.x == 0) dot[rr] = s;
     }
 }
@@ -133,21 +104,12 @@ __global__ __launch_bounds__(256) void row_dot_kernel(const float* __restrict__ 
     const long nq = (n + 3) / 4;
     float s = 0.f;
     for (long q = threadIdx.x; q < nq; q += 256) {
-        if (VEC) {
-            const float4 pv = *(const float4*)(pr + q * 4), av = *(const float4*)(ar + q * 4);
-            s = s + pv.x * av.x;
-            s = s + pv.y * av.y;
-            s = s + pv.z * av.z;
-            s = s + pv.w * av.w;
-        } else {
-            for (int k = 0; k < 4; ++k) {
-                const long j = q * 4 + k;
-                if (j >= n) break;
-                s = s + pr[j] * ar[j];
-            }
-        }
+        const lanes<4> pv = load_quad<VEC>(pr, q, n), av = load_quad<VEC>(ar, q, n);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (quad_lane<VEC>(q, k, n)) s = s + pv[k] * av[k];
     }
-    s = block_reduce(s, false);
+    s = block_sum(s);
     if (threadIdx.x == 0) dot[r] = s;
 }
 
@@ -166,20 +128,10 @@ __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__
     const long nq = (n + 3) / 4;
     float s = 0.f;
     for (long q = threadIdx.x; q < nq; q += 256) {
-        if (VEC) {
-            const float4 av = *(const float4*)(ar + q * 4);
-            const float4 bv = brow ? *(const float4*)(brow + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            s = norm_acc(s, brow ? av.x - bv.x : av.x, ord);
-            s = norm_acc(s, brow ? av.y - bv.y : av.y, ord);
-            s = norm_acc(s, brow ? av.z - bv.z : av.z, ord);
-            s = norm_acc(s, brow ? av.w - bv.w : av.w, ord);
-        } else {
-            for (int k = 0; k < 4; ++k) {
-                const long j = q * 4 + k;
-                if (j >= n) break;
-                s = norm_acc(s, brow ? ar[j] - brow[j] : ar[j], ord);
-            }
-        }
+        const lanes<4> av = load_quad<VEC>(ar, q, n), bv = load_quad_or<VEC>(brow, q, n);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (quad_lane<VEC>(q, k, n)) s = norm_acc(s, brow ? av[k] - bv[k] : av[k], ord);
     }
     s = block_reduce(s, ord == NORM_INF);
     if (threadIdx.x == 0) {
@@ -270,20 +222,14 @@ extern "C" int advh_metric_rows(const advh_metric_desc* d, int64_t row0, int row
     const MetricCtx c{d->x, d->mode == MR_GAUSS ? d->attr : nullptr, d->mode == MR_GAUSS && d->mul ? d->base : nullptr, (long)d->n,
                       d->seed, d->B, d->S, d->s0, d->p, d->base_rows, d->mode, d->mul, d->scale};
     const bool vec = c.n % 4 == 0 && aligned16(c.x) && aligned16(c.attr) && aligned16(c.base) && aligned16(out);
-    if (vec)
-        hipLaunchKernelGGL(metric_rows_kernel<true>, dim3(rows), dim3(256), 0, (hipStream_t)stream, c, (long)row0, out, dot);
-    else
-        hipLaunchKernelGGL(metric_rows_kernel<false>, dim3(rows), dim3(256), 0, (hipStream_t)stream, c, (long)row0, out, dot);
+    launch_vec(vec, metric_rows_kernel<true>, metric_rows_kernel<false>, dim3(rows), (hipStream_t)stream, c, row0, out, dot);
     return ADVH_LAUNCH_CHECK();
 }
 
 extern "C" int advh_metric_row_dot(const float* pert, const float* attr, int B, int p, int64_t n, float* dot, advh_stream_t stream) {
     if (!pert || !attr || !dot || !chunk_ok(B, p) || n <= 0) return ADVH_EINVAL;
     const bool vec = n % 4 == 0 && aligned16(pert) && aligned16(attr);
-    if (vec)
-        hipLaunchKernelGGL(row_dot_kernel<true>, dim3(B * p), dim3(256), 0, (hipStream_t)stream, pert, attr, p, (long)n, dot);
-    else
-        hipLaunchKernelGGL(row_dot_kernel<false>, dim3(B * p), dim3(256), 0, (hipStream_t)stream, pert, attr, p, (long)n, dot);
+    launch_vec(vec, row_dot_kernel<true>, row_dot_kernel<false>, dim3(B * p), (hipStream_t)stream, pert, attr, p, n, dot);
     return ADVH_LAUNCH_CHECK();
 }
 
@@ -303,12 +249,7 @@ extern "C" int advh_infidelity_finalize(const double* acc, int B, int S, int nor
 extern "C" int advh_row_norm(const float* v, int rows, int64_t n, int ord, float* out, advh_stream_t stream) {
     if (!v || !out || rows <= 0 || n <= 0 || ord < NORM_2 || ord > NORM_INF) return ADVH_EINVAL;
     const bool vec = n % 4 == 0 && aligned16(v);
-    if (vec)
-        hipLaunchKernelGGL(row_norm_kernel<true>, dim3(rows), dim3(256), 0, (hipStream_t)stream, v, (const float*)nullptr, 1, (long)n,
-                           ord, (const float*)nullptr, out);
-    else
-        hipLaunchKernelGGL(row_norm_kernel<false>, dim3(rows), dim3(256), 0, (hipStream_t)stream, v, (const float*)nullptr, 1, (long)n,
-                           ord, (const float*)nullptr, out);
+    launch_vec(vec, row_norm_kernel<true>, row_norm_kernel<false>, dim3(rows), (hipStream_t)stream, v, nullptr, 1, n, ord, nullptr, out);
     return ADVH_LAUNCH_CHECK();
 }
 
@@ -317,10 +258,7 @@ extern "C" int advh_sensitivity_fold(const float* e, const float* et, const floa
     if (!e || !et || !enorm || !ratio || !smax || !chunk_ok(B, p) || n <= 0 || ord < NORM_2 || ord > NORM_INF) return ADVH_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const bool vec = n % 4 == 0 && aligned16(e) && aligned16(et);
-    if (vec)
-        hipLaunchKernelGGL(row_norm_kernel<true>, dim3(B * p), dim3(256), 0, s, e, et, p, (long)n, ord, enorm, ratio);
-    else
-        hipLaunchKernelGGL(row_norm_kernel<false>, dim3(B * p), dim3(256), 0, s, e, et, p, (long)n, ord, enorm, ratio);
+    launch_vec(vec, row_norm_kernel<true>, row_norm_kernel<false>, dim3(B * p), s, e, et, p, n, ord, enorm, ratio);
     hipLaunchKernelGGL(max_fold_kernel, dim3(grid_for(B)), dim3(256), 0, s, (const float*)ratio, B, p, smax);
     return ADVH_LAUNCH_CHECK();
 }

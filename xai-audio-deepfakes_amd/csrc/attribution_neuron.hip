@@ -2,15 +2,16 @@
 // backward: include/addvisor_hip.h, advh_layer_seed / advh_neuron_values.  A neuron is a selection box over the [T][H] frame of
 // hidden_states[l]: (t0, t1, tstep, h0, h1, hstep), half-open, positive steps; its value is the sum of the selected elements.
 //
-// As attribution_layer.hip the kernels are elementwise over fp32 rows: grid-stride loops, float4 access when every row pointer is
-// 16-byte aligned (base pointers aligned and H % 4 == 0), a scalar path otherwise.
+// As attribution_layer.hip the kernels are elementwise over fp32 rows: grid-stride loops over the element walkers of
+// attribution_lanes.h, which states the float4 / scalar rule (float4 when base pointers are aligned and H % 4 == 0) and the row tree.
 //
-// Determinism contract: one thread per element; every product is rounded on its own (no FMA contraction); the box sum is a
-// fixed-shape tree in one workgroup per clip row.  No atomics.
+// Determinism contract: one thread per element; every product is rounded on its own (no FMA contraction); the box sum is the
+// row tree in one workgroup per clip row.  No atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "addvisor_hip.h"
+#include "attribution_lanes.h"
 #include "common.h"
 #include "device_math.h"
 
@@ -31,46 +32,33 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void layer_seed_kernel(const float* __restrict__ src, const float* __restrict__ row_scale, float scale,
                                                          int T, int H, sel_box box, float* __restrict__ resid, _Float16* __restrict__ op,
                                                          long lo, int split, long total) {
-    const long per = VEC ? total / 4 : total;
+    constexpr int W = VEC ? 4 : 1;
+    const long per = total / W;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long)gridDim.x * 256) {
-        const long e = VEC ? i * 4 : i;
+        const long e = i * W;
         const long row = e / H;
         const int h = (int)(e - row * H), t = (int)(row % T);
         float in = 0.f;
         if (!src) in = row_scale ? __fmul_rn(scale, row_scale[row / T]) : scale;
-        if (VEC) {
-            float v[4];
-            if (src) {
-                const float4 s = *(const float4*)(src + e);
-                v[0] = __fmul_rn(scale, s.x), v[1] = __fmul_rn(scale, s.y), v[2] = __fmul_rn(scale, s.z), v[3] = __fmul_rn(scale, s.w);
-            } else {
+        lanes<W> v;
+        if (src) {
+            const lanes<W> s = load_lanes<W>(src + e);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = in_box(box, t, h + j) ? in : 0.f;
-            }
-            *(float4*)(resid + e) = make_float4(v[0], v[1], v[2], v[3]);
-            if (op) store_h_rt<4>(op, e, split ? lo : 0L, v);
+            for (int j = 0; j < W; ++j) v[j] = __fmul_rn(scale, s[j]);
         } else {
-            const float v = src ? __fmul_rn(scale, src[e]) : (in_box(box, t, h) ? in : 0.f);
-            resid[e] = v;
-            if (op) {
-                if (split) {
-                    _Float16 hh, ll;
-                    split_f32(v, hh, ll);
-                    op[e] = hh;
-                    op[e + lo] = ll;
-                } else {
-                    op[e] = (_Float16)v;
-                }
-            }
+#pragma unroll
+            for (int j = 0; j < W; ++j) v[j] = in_box(box, t, h + j) ? in : 0.f;
         }
+        store_lanes<W>(resid + e, v);
+        if (op) store_h_item<W>(op, e, split ? lo : 0L, v.v);
     }
 }
 
-// One workgroup per clip row, fixed-shape tree: out[r] = sum over the box of v[r][t][h].  The float4 form walks the quads that
-// cover [h0, h1) of every selected frame and masks the components outside the box.
+// One workgroup per clip row, the row tree: out[r] = sum over the box of v[r][t][h].  The two forms walk different index sets, so
+// this kernel keeps two loops: the float4 form walks the quads that cover [h0, h1) of every selected frame and masks the
+// components outside the box, the scalar form walks the box's elements.
 template <bool VEC>
 __global__ __launch_bounds__(256) void neuron_values_kernel(const float* __restrict__ v, int T, int H, sel_box box, float* __restrict__ out) {
-    __shared__ float red[4];
     const long r = blockIdx.x;
     const float* vr = v + r * (long)T * H;
     const int nt = (box.t1 - box.t0 + box.ts - 1) / box.ts;
@@ -91,11 +79,8 @@ __global__ __launch_bounds__(256) void neuron_values_kernel(const float* __restr
             s += vr[(long)t * H + h];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[r] = (red[0] + red[1]) + (red[2] + red[3]);
+    s = block_sum(s);
+    if (threadIdx.x == 0) out[r] = s;
 }
 
 }  // namespace advh
@@ -119,21 +104,14 @@ extern "C" int advh_layer_seed(const float* src, const float* row_scale, float s
     if (!src) b = {box[0], box[1], box[2], box[3], box[4], box[5]};
     const bool vec = H % 4 == 0 && aligned16(src) && aligned16(resid) && (!op || (((uintptr_t)op & 7) == 0 && (!split || op_lo % 4 == 0)));
     const unsigned grid = grid_for(vec ? total / 4 : total);
-    if (vec)
-        hipLaunchKernelGGL(layer_seed_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, row_scale, scale, T, H, b, resid,
-                           (_Float16*)op, (long)op_lo, split, total);
-    else
-        hipLaunchKernelGGL(layer_seed_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, row_scale, scale, T, H, b, resid,
-                           (_Float16*)op, (long)op_lo, split, total);
+    launch_vec(vec, layer_seed_kernel<true>, layer_seed_kernel<false>, dim3(grid), (hipStream_t)stream, src, row_scale, scale, T, H, b, resid,
+               op, op_lo, split, total);
     return ADVH_LAUNCH_CHECK();
 }
 
 extern "C" int advh_neuron_values(const float* v, int R, int T, int H, const int* box, float* out, advh_stream_t stream) {
     if (!v || !out || R <= 0 || T <= 0 || H <= 0 || !box_ok(box, T, H)) return ADVH_EINVAL;
     const sel_box b = {box[0], box[1], box[2], box[3], box[4], box[5]};
-    if (H % 4 == 0 && aligned16(v))
-        hipLaunchKernelGGL(neuron_values_kernel<true>, dim3(R), dim3(256), 0, (hipStream_t)stream, v, T, H, b, out);
-    else
-        hipLaunchKernelGGL(neuron_values_kernel<false>, dim3(R), dim3(256), 0, (hipStream_t)stream, v, T, H, b, out);
+    launch_vec(H % 4 == 0 && aligned16(v), neuron_values_kernel<true>, neuron_values_kernel<false>, dim3(R), (hipStream_t)stream, v, T, H, b, out);
     return ADVH_LAUNCH_CHECK();
 }

@@ -3,18 +3,19 @@
 // moments of NoiseTunnel (advh_nt_fold / advh_nt_finalize), whose noisy rows are advh_attr_path_points' x~.
 //
 // Every kernel here is elementwise or a row reduction over fp32 rows (~40 MB per 160-row chunk at 4 s, next to hundreds of
-// milliseconds of GEMMs per chunk), so they stay simple: grid-stride loops, float4 access when every row pointer is 16-byte
-// aligned (base pointers aligned and n % 4 == 0), a scalar path otherwise.
+// milliseconds of GEMMs per chunk), so they stay simple: grid-stride loops over the element walkers of attribution_lanes.h, which
+// states the float4 / scalar rule (float4 when base pointers are aligned and n % 4 == 0) and the row tree.
 //
 // Determinism contract: the noise of element (g, j) is a pure function of (seed, g, j) -- Philox4x32-10 keyed by the seed,
 // counter (j / 4, g lo, g hi, 0), Box-Muller on the four words -- so a row's values depend on neither the grid nor the
-// chunking; each clip's rows of a chunk are added in global-row order by one thread per element, and every row sum is a
-// fixed-shape tree in one workgroup.  NoiseTunnel's fp64 moments add each element's samples in increasing sample order, one
+// chunking; each clip's rows of a chunk are added in global-row order by one thread per element, and every row sum is the
+// row tree (attribution_lanes.h) in one workgroup.  NoiseTunnel's fp64 moments add each element's samples in increasing sample order, one
 // thread per element.  No atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "addvisor_hip.h"
+#include "attribution_lanes.h"
 #include "common.h"
 #include "philox.h"
 
@@ -44,49 +45,39 @@ __device__ __forceinline__ const float* base_of(const PathCtx& c, long g, int cl
     return c.base + (c.base_rows == 1 ? 0L : (long)clip * c.n);
 }
 
-// x~ - b of the quad starting at column j (j % 4 == 0, row pointers 16-byte aligned)
-__device__ __forceinline__ float4 diff4(const PathCtx& c, long g, int clip, const float* b, long j, float4* bv) {
-    float4 xv = *(const float4*)(c.x + (long)clip * c.n + j);
-    *bv = *(const float4*)(b + j);
+// x~ - b of the W elements starting at column j of row g (W == 4: j % 4 == 0, row pointers 16-byte aligned); *bv = b there
+template <int W>
+__device__ __forceinline__ lanes<W> diff(const PathCtx& c, long g, int clip, const float* b, long j, lanes<W>* bv) {
+    lanes<W> xv = load_lanes<W>(c.x + (long)clip * c.n + j), d;
+    *bv = load_lanes<W>(b + j);
     if (c.sigma != 0.f) {
         const float4 z = philox_normal4(c.seed, g, j >> 2);
-        xv.x += c.sigma * z.x, xv.y += c.sigma * z.y, xv.z += c.sigma * z.z, xv.w += c.sigma * z.w;
+#pragma unroll
+        for (int k = 0; k < W; ++k) xv[k] += c.sigma * pick(z, W == 4 ? k : (int)(j & 3));
     }
-    return make_float4(xv.x - bv->x, xv.y - bv->y, xv.z - bv->z, xv.w - bv->w);
-}
-
-__device__ __forceinline__ float diff1(const PathCtx& c, long g, int clip, const float* b, long j, float* bv) {
-    float xv = c.x[(long)clip * c.n + j];
-    *bv = b[j];
-    if (c.sigma != 0.f) xv += c.sigma * pick(philox_normal4(c.seed, g, j >> 2), (int)(j & 3));
-    return xv - *bv;
+#pragma unroll
+    for (int k = 0; k < W; ++k) d[k] = xv[k] - (*bv)[k];
+    return d;
 }
 
 // out[r][:] = b + alpha[g] * (x~ - b),  g = row0 + r
 template <bool VEC>
 __global__ __launch_bounds__(256) void path_points_kernel(PathCtx c, const float* __restrict__ alpha, long row0, int rows,
                                                           float* __restrict__ out) {
-    const long per = VEC ? c.n / 4 : c.n, total = (long)rows * per;
+    constexpr int W = VEC ? 4 : 1;
+    const long per = c.n / W, total = (long)rows * per;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long r = i / per, q = i - r * per, g = row0 + r;
         const int clip = clip_of(c, g);
         const float* b = base_of(c, g, clip);
         const float a = alpha[g];
-        if (VEC) {
-            float4 o = make_float4(NAN, NAN, NAN, NAN), bv;
-            if (b) {
-                const float4 d = diff4(c, g, clip, b, q * 4, &bv);
-                o = make_float4(bv.x + a * d.x, bv.y + a * d.y, bv.z + a * d.z, bv.w + a * d.w);
-            }
-            *(float4*)(out + r * c.n + q * 4) = o;
-        } else {
-            float o = NAN, bv;
-            if (b) {
-                const float d = diff1(c, g, clip, b, q, &bv);
-                o = bv + a * d;
-            }
-            out[r * c.n + q] = o;
+        lanes<W> o = fill_lanes<W>(NAN), bv;
+        if (b) {
+            const lanes<W> d = diff<W>(c, g, clip, b, q * W, &bv);
+#pragma unroll
+            for (int k = 0; k < W; ++k) o[k] = bv[k] + a * d[k];
         }
+        store_lanes<W>(out + r * c.n + q * W, o);
     }
 }
 
@@ -95,13 +86,15 @@ enum { ACC_IG = 0, ACC_SHAP = 1, ACC_SHAP_GRAD = 2, FIN_IG = 3, FIN_MEAN = 4 };
 // Chunk accumulation: element (clip, j) of `total` adds the chunk's rows of that clip in global-row order,
 //   ACC_IG:        total += w[g] * grad[r]            (step-major rows, g % B = clip; product rounded before the add, as
 //                                                      advh_scale_rows does, so a zero baseline reproduces the zero-baseline IG)
-//   ACC_SHAP:      total += (x~ - b) * grad[r]        (clip-major rows, g / S = clip; x~ recomputed from the counter)
+//   ACC_SHAP:      total += (x~ - b) * grad[r]        (clip-major rows, g / S = clip; x~ recomputed from the counter; the product
+//                                                      rounded before the add as well, in both forms)
 //   ACC_SHAP_GRAD: total += grad[r]
 // clips [c0, c0 + nclip) are the ones the chunk touches.
 template <bool VEC>
 __global__ __launch_bounds__(256) void path_accumulate_kernel(PathCtx c, const float* __restrict__ grad, const float* __restrict__ w,
                                                               int mode, long row0, int rows, int c0, int nclip, float* __restrict__ tot) {
-    const long per = VEC ? c.n / 4 : c.n, total = (long)nclip * per, gend = row0 + rows;
+    constexpr int W = VEC ? 4 : 1;
+    const long per = c.n / W, total = (long)nclip * per, gend = row0 + rows;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long k = i / per, q = i - k * per;
         const int clip = c0 + (int)k;
@@ -115,74 +108,59 @@ __global__ __launch_bounds__(256) void path_accumulate_kernel(PathCtx c, const f
             last = gend;
             step = c.B;
         }
-        if (VEC) {
-            float4* tp = (float4*)(tot + (long)clip * c.n + q * 4);
-            float4 acc = *tp;
-            for (; g < last; g += step) {
-                const float4 gv = *(const float4*)(grad + (g - row0) * c.n + q * 4);
-                if (mode == ACC_IG) {
-                    const float wg = w[g];
-                    acc.x += __fmul_rn(wg, gv.x), acc.y += __fmul_rn(wg, gv.y), acc.z += __fmul_rn(wg, gv.z), acc.w += __fmul_rn(wg, gv.w);
-                } else if (mode == ACC_SHAP_GRAD) {
-                    acc.x += gv.x, acc.y += gv.y, acc.z += gv.z, acc.w += gv.w;
-                } else {
-                    const float* b = base_of(c, g, clip);
-                    float4 bv, d = make_float4(NAN, NAN, NAN, NAN);
-                    if (b) d = diff4(c, g, clip, b, q * 4, &bv);
-                    acc.x += d.x * gv.x, acc.y += d.y * gv.y, acc.z += d.z * gv.z, acc.w += d.w * gv.w;
-                }
+        float* tp = tot + (long)clip * c.n + q * W;
+        lanes<W> acc = load_lanes<W>(tp);
+        for (; g < last; g += step) {
+#pragma clang fp contract(off)                             // every term is rounded before it joins the sum (diff() keeps its own rule)
+            const lanes<W> gv = load_lanes<W>(grad + (g - row0) * c.n + q * W);
+            if (mode == ACC_IG) {
+                const float wg = w[g];
+#pragma unroll
+                for (int l = 0; l < W; ++l) acc[l] += wg * gv[l];
+            } else if (mode == ACC_SHAP_GRAD) {
+#pragma unroll
+                for (int l = 0; l < W; ++l) acc[l] += gv[l];
+            } else {
+                const float* b = base_of(c, g, clip);
+                lanes<W> bv, d = fill_lanes<W>(NAN);
+                if (b) d = diff<W>(c, g, clip, b, q * W, &bv);
+#pragma unroll
+                for (int l = 0; l < W; ++l) acc[l] += d[l] * gv[l];
             }
-            *tp = acc;
-        } else {
-            float* tp = tot + (long)clip * c.n + q;
-            float acc = *tp;
-            for (; g < last; g += step) {
-                const float gv = grad[(g - row0) * c.n + q];
-                if (mode == ACC_IG) {
-                    acc += __fmul_rn(w[g], gv);
-                } else if (mode == ACC_SHAP_GRAD) {
-                    acc += gv;
-                } else {
-                    const float* b = base_of(c, g, clip);
-                    float bv;
-                    acc += (b ? diff1(c, g, clip, b, q, &bv) : NAN) * gv;
-                }
-            }
-            *tp = acc;
         }
+        store_lanes<W>(tp, acc);
     }
 }
 
 // Finalize, row r = clip r:  FIN_IG: out = (x - b) * total;  FIN_MEAN: out = total / S
 template <bool VEC>
 __global__ __launch_bounds__(256) void path_finalize_kernel(PathCtx c, const float* __restrict__ tot, int mode, float* __restrict__ out) {
-    const long per = VEC ? c.n / 4 : c.n, total = (long)c.B * per;
+    constexpr int W = VEC ? 4 : 1;
+    const long per = c.n / W, total = (long)c.B * per;
     const float S = (float)c.S;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long r = i / per, q = i - r * per;
         const float* b = c.base + (c.base_rows == 1 ? 0L : r * c.n);
-        if (VEC) {
-            const float4 t = *(const float4*)(tot + r * c.n + q * 4);
-            float4 o;
-            if (mode == FIN_IG) {
-                const float4 xv = *(const float4*)(c.x + r * c.n + q * 4), bv = *(const float4*)(b + q * 4);
-                o = make_float4((xv.x - bv.x) * t.x, (xv.y - bv.y) * t.y, (xv.z - bv.z) * t.z, (xv.w - bv.w) * t.w);
-            } else {
-                o = make_float4(t.x / S, t.y / S, t.z / S, t.w / S);
-            }
-            *(float4*)(out + r * c.n + q * 4) = o;
+        const lanes<W> t = load_lanes<W>(tot + r * c.n + q * W);
+        lanes<W> o;
+        if (mode == FIN_IG) {
+            const lanes<W> xv = load_lanes<W>(c.x + r * c.n + q * W), bv = load_lanes<W>(b + q * W);
+#pragma unroll
+            for (int k = 0; k < W; ++k) o[k] = (xv[k] - bv[k]) * t[k];
         } else {
-            const float t = tot[r * c.n + q];
-            out[r * c.n + q] = mode == FIN_IG ? (c.x[r * c.n + q] - b[q]) * t : t / S;
+#pragma unroll
+            for (int k = 0; k < W; ++k) o[k] = t[k] / S;
         }
+        store_lanes<W>(out + r * c.n + q * W, o);
     }
 }
 
-// One workgroup per row, fixed-shape tree: sum[g] = sum_j (x~ - b)_j * v[r][j] (use_diff) or sum_j v[r][j]; g = row0 + r.
+// One workgroup per row, the row tree: sum[g] = sum_j (x~ - b)_j * v[r][j] (use_diff) or sum_j v[r][j]; g = row0 + r.  A thread
+// adds one term per element in the scalar form and one four-term sum per quad in the float4 form.
 template <bool VEC>
 __global__ __launch_bounds__(256) void path_row_sum_kernel(PathCtx c, const float* __restrict__ v, long row0, int use_diff,
                                                            float* __restrict__ sum) {
-    __shared__ float red[4];
+    constexpr int W = VEC ? 4 : 1;
     const long r = blockIdx.x, g = row0 + r;
     const int clip = use_diff ? clip_of(c, g) : 0;
     const float* b = use_diff ? base_of(c, g, clip) : nullptr;
@@ -190,34 +168,30 @@ __global__ __launch_bounds__(256) void path_row_sum_kernel(PathCtx c, const floa
     float s = 0.f;
     if (use_diff && !b) {
         s = NAN;
-    } else if (VEC) {
-        for (long q = threadIdx.x; q < c.n / 4; q += 256) {
-            const float4 t = *(const float4*)(vr + q * 4);
-            if (use_diff) {
-                float4 bv;
-                const float4 d = diff4(c, g, clip, b, q * 4, &bv);
-                s += d.x * t.x + d.y * t.y + d.z * t.z + d.w * t.w;
-            } else {
-                s += t.x + t.y + t.z + t.w;
-            }
-        }
     } else {
-        for (long j = threadIdx.x; j < c.n; j += 256) {
-            float bv;
-            s += use_diff ? diff1(c, g, clip, b, j, &bv) * vr[j] : vr[j];
+        for (long q = threadIdx.x; q < c.n / W; q += 256) {
+            lanes<W> t = load_lanes<W>(vr + q * W);
+            if (use_diff) {
+                lanes<W> bv;
+                const lanes<W> d = diff<W>(c, g, clip, b, q * W, &bv);
+#pragma unroll
+                for (int k = 0; k < W; ++k) t[k] = d[k] * t[k];
+            }
+            if constexpr (W == 4)
+                s += t[0] + t[1] + t[2] + t[3];
+            else
+                s += t[0];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) sum[g] = (red[0] + red[1]) + (red[2] + red[3]);
+    s = block_sum(s);
+    if (threadIdx.x == 0) sum[g] = s;
 }
 
 // out[r][j] = N(seed, row0 + r, j), or (raw) the Philox word j % 4 of counter (j / 4, row0 + r) as its bit pattern
 template <bool VEC>
 __global__ __launch_bounds__(256) void philox_normal_kernel(uint64_t seed, long row0, int rows, long n, int raw, float* __restrict__ out) {
-    const long per = VEC ? n / 4 : n, total = (long)rows * per;
+    constexpr int W = VEC ? 4 : 1;
+    const long per = n / W, total = (long)rows * per;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long r = i / per, q = i - r * per, g = row0 + r, quad = VEC ? q : q >> 2;
         float4 v;
@@ -228,10 +202,10 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(uint64_t seed, long 
         } else {
             v = philox_normal4(seed, g, quad);
         }
-        if (VEC)
-            *(float4*)(out + r * n + q * 4) = v;
-        else
-            out[r * n + q] = pick(v, (int)(q & 3));
+        lanes<W> o;
+#pragma unroll
+        for (int k = 0; k < W; ++k) o[k] = pick(v, VEC ? k : (int)(q & 3));
+        store_lanes<W>(out + r * n + q * W, o);
     }
 }
 
@@ -289,10 +263,7 @@ extern "C" int advh_attr_path_points(const advh_path_desc* d, const float* alpha
     if (path_ctx(d, &c) != ADVH_OK || !alpha || !out || !rows_ok(d, row0, rows)) return ADVH_EINVAL;
     const bool vec = c.n % 4 == 0 && aligned16(c.x) && aligned16(c.base) && aligned16(out);
     const unsigned grid = grid_for((long)rows * (vec ? c.n / 4 : c.n));
-    if (vec)
-        hipLaunchKernelGGL(path_points_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, alpha, (long)row0, rows, out);
-    else
-        hipLaunchKernelGGL(path_points_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c, alpha, (long)row0, rows, out);
+    launch_vec(vec, path_points_kernel<true>, path_points_kernel<false>, dim3(grid), (hipStream_t)stream, c, alpha, row0, rows, out);
     return ADVH_LAUNCH_CHECK();
 }
 
@@ -308,16 +279,9 @@ extern "C" int advh_attr_path_accumulate(const advh_path_desc* d, const float* g
     const bool vec = c.n % 4 == 0 && aligned16(c.x) && aligned16(c.base) && aligned16(grad) && aligned16(total);
     const long per = vec ? c.n / 4 : c.n;
     if (mode >= FIN_IG) {
-        if (vec)
-            hipLaunchKernelGGL(path_finalize_kernel<true>, dim3(grid_for(c.B * per)), dim3(256), 0, s, c, grad, mode, total);
-        else
-            hipLaunchKernelGGL(path_finalize_kernel<false>, dim3(grid_for(c.B * per)), dim3(256), 0, s, c, grad, mode, total);
-        if (row_sum) {                                     // per-clip sums of the attribution (IG's convergence delta)
-            if (vec)
-                hipLaunchKernelGGL(path_row_sum_kernel<true>, dim3(c.B), dim3(256), 0, s, c, (const float*)total, 0L, 0, row_sum);
-            else
-                hipLaunchKernelGGL(path_row_sum_kernel<false>, dim3(c.B), dim3(256), 0, s, c, (const float*)total, 0L, 0, row_sum);
-        }
+        launch_vec(vec, path_finalize_kernel<true>, path_finalize_kernel<false>, dim3(grid_for(c.B * per)), s, c, grad, mode, total);
+        if (row_sum)                                       // per-clip sums of the attribution (IG's convergence delta)
+            launch_vec(vec, path_row_sum_kernel<true>, path_row_sum_kernel<false>, dim3(c.B), s, c, total, 0L, 0, row_sum);
         return ADVH_LAUNCH_CHECK();
     }
     int c0, nclip;
@@ -328,18 +292,10 @@ extern "C" int advh_attr_path_accumulate(const advh_path_desc* d, const float* g
         c0 = 0;
         nclip = c.B;
     }
-    if (vec)
-        hipLaunchKernelGGL(path_accumulate_kernel<true>, dim3(grid_for(nclip * per)), dim3(256), 0, s, c, grad, w, mode, (long)row0, rows,
-                           c0, nclip, total);
-    else
-        hipLaunchKernelGGL(path_accumulate_kernel<false>, dim3(grid_for(nclip * per)), dim3(256), 0, s, c, grad, w, mode, (long)row0, rows,
-                           c0, nclip, total);
-    if (row_sum) {                                         // per-row (x~ - b) . grad (GradientShap's convergence delta)
-        if (vec)
-            hipLaunchKernelGGL(path_row_sum_kernel<true>, dim3(rows), dim3(256), 0, s, c, grad, (long)row0, 1, row_sum);
-        else
-            hipLaunchKernelGGL(path_row_sum_kernel<false>, dim3(rows), dim3(256), 0, s, c, grad, (long)row0, 1, row_sum);
-    }
+    launch_vec(vec, path_accumulate_kernel<true>, path_accumulate_kernel<false>, dim3(grid_for(nclip * per)), s, c, grad, w, mode, row0, rows,
+               c0, nclip, total);
+    if (row_sum)                                           // per-row (x~ - b) . grad (GradientShap's convergence delta)
+        launch_vec(vec, path_row_sum_kernel<true>, path_row_sum_kernel<false>, dim3(rows), s, c, grad, row0, 1, row_sum);
     return ADVH_LAUNCH_CHECK();
 }
 
@@ -347,10 +303,7 @@ extern "C" int advh_philox_normal(uint64_t seed, int64_t row0, int rows, int64_t
     if (!out || row0 < 0 || rows <= 0 || n <= 0 || (raw != 0 && raw != 1)) return ADVH_EINVAL;
     const bool vec = n % 4 == 0 && aligned16(out);
     const unsigned grid = grid_for((long)rows * (vec ? n / 4 : n));
-    if (vec)
-        hipLaunchKernelGGL(philox_normal_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, seed, (long)row0, rows, (long)n, raw, out);
-    else
-        hipLaunchKernelGGL(philox_normal_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, seed, (long)row0, rows, (long)n, raw, out);
+    launch_vec(vec, philox_normal_kernel<true>, philox_normal_kernel<false>, dim3(grid), (hipStream_t)stream, seed, row0, rows, n, raw, out);
     return ADVH_LAUNCH_CHECK();
 }
 

@@ -3,21 +3,23 @@
 // PGD's projection onto the Linf or L2 ball around the clean clip and the bound clamp in one pass -- PGD's random start, and
 // the fold of an epsilon ladder.
 //
-// These kernels move ~16 B per sample next to a forward + backward per row, so they stay simple, as attribution_metrics.hip:
-// float4 access when every row pointer is 16-byte aligned (base pointers aligned and n % 4 == 0), a scalar path otherwise that
-// visits the same elements in the same order.  Without a row reduction (no projection, Linf) a row is split over several
-// workgroups, grid-stride over its quads; the L2 projection and the L2 random start take one workgroup of 256 per row.
+// These kernels move ~16 B per sample next to a forward + backward per row, so they stay simple, as attribution_metrics.hip: the
+// quad walkers of attribution_lanes.h, which states the float4 / scalar rule (float4 when base pointers are aligned and
+// n % 4 == 0; both forms visit the same elements in the same order) and the row tree.  Without a row reduction (no projection,
+// Linf) a row is split over several workgroups, grid-stride over its quads; the L2 projection and the L2 random start take one
+// workgroup of 256 per row.
 //
 // Determinism contract: an output element is a pure function of its own inputs and, for L2, of its row's norm.  The row sum of
-// squares is the fixed-shape tree of attribution_metrics.hip: thread t adds the quads t, t + 256, ... in order, the four elements
-// of a quad in order, then a wave64 __shfl_xor tree and the four waves as (w0 + w1) + (w2 + w3); every thread reads the same
-// four partials, so the whole row is scaled by one value.  Pass 2 recomputes the step from its inputs; the row is not staged.
+// squares is the row tree: thread t adds the quads t, t + 256, ... in order, the four elements of a quad in order, then the tree;
+// every thread reads the same four partials, so the whole row is scaled by one value.  Pass 2 recomputes the step from its inputs;
+// the row is not staged.
 // The random start of clip b is a pure function of (seed, b, B).  The ladder fold runs one thread per clip, k in increasing
 // order.  No atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "addvisor_hip.h"
+#include "attribution_lanes.h"
 #include "common.h"
 #include "philox.h"
 
@@ -41,17 +43,6 @@ struct RobustCtx {
     float radius, lo, hi;
     float e[ROBUST_MAX_P];
 };
-
-// Fixed-shape workgroup sum of one value per thread (256 threads): wave64 xor tree, then (w0 + w1) + (w2 + w3); every thread
-// returns the same bits.
-__device__ __forceinline__ float block_sum(float s) {
-    __shared__ float red[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) {
     v = v < lo ? lo : v;                                     // NaN passes through, as torch.clamp
@@ -87,66 +78,43 @@ __global__ __launch_bounds__(256) void robust_step_kernel(RobustCtx c, long row0
     const float e = c.e[k];
     const long nq = (c.n + 3) / 4;
     const long q0 = (long)chunk * 256 + threadIdx.x, qs = (long)c.chunks * 256;
+    // the step of quad q, and its clean clip's elements (0 without a projection)
+    auto step = [&](long q, lanes<4>* cv) {
+        const lanes<4> xv = load_quad<VEC>(xr, q, c.n), gv = load_quad<VEC>(gr, q, c.n), mv = load_quad_or<VEC>(mr, q, c.n);
+        *cv = L2 ? load_quad<VEC>(x0r, q, c.n) : load_quad_or<VEC>(x0r, q, c.n);   // a projection always has its clean clip
+        lanes<4> v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = fgsm_elem(xv[i], gv[i], sd, has_seed, e, mv[i], has_mask);
+        return v;
+    };
     float scale = 1.f;
     if (L2) {
         float s = 0.f;
         for (long q = q0; q < nq; q += qs) {
-            if (VEC) {
-                const float4 xv = *(const float4*)(xr + q * 4), gv = *(const float4*)(gr + q * 4), cv = *(const float4*)(x0r + q * 4);
-                const float4 mv = has_mask ? *(const float4*)(mr + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float xk[4] = {xv.x, xv.y, xv.z, xv.w}, gk[4] = {gv.x, gv.y, gv.z, gv.w}, ck[4] = {cv.x, cv.y, cv.z, cv.w},
-                            mk[4] = {mv.x, mv.y, mv.z, mv.w};
+            lanes<4> cv;
+            const lanes<4> v = step(q, &cv);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float d = fgsm_elem(xk[i], gk[i], sd, has_seed, e, mk[i], has_mask) - ck[i];
-                    s = s + d * d;
-                }
-            } else {
-                for (int i = 0; i < 4; ++i) {
-                    const long j = q * 4 + i;
-                    if (j >= c.n) break;
-                    const float d = fgsm_elem(xr[j], gr[j], sd, has_seed, e, has_mask ? mr[j] : 0.f, has_mask) - x0r[j];
-                    s = s + d * d;
-                }
+            for (int i = 0; i < 4; ++i) {
+                const float d = v[i] - cv[i];
+                if (quad_lane<VEC>(q, i, c.n)) s = s + d * d;
             }
         }
         const float nrm = sqrtf(block_sum(s));               // the barrier inside: every read of pass 1 precedes pass 2's writes
         scale = nrm > c.radius ? c.radius / (nrm + 1e-7f) : 1.f;
     }
     for (long q = q0; q < nq; q += qs) {
-        if (VEC) {
-            const float4 xv = *(const float4*)(xr + q * 4), gv = *(const float4*)(gr + q * 4);
-            const float4 cv = x0r ? *(const float4*)(x0r + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 mv = has_mask ? *(const float4*)(mr + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float xk[4] = {xv.x, xv.y, xv.z, xv.w}, gk[4] = {gv.x, gv.y, gv.z, gv.w}, ck[4] = {cv.x, cv.y, cv.z, cv.w},
-                        mk[4] = {mv.x, mv.y, mv.z, mv.w};
-            float o[4];
+        lanes<4> cv;
+        lanes<4> v = step(q, &cv);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float v = fgsm_elem(xk[i], gk[i], sd, has_seed, e, mk[i], has_mask);
-                if (L2) {
-                    v = ck[i] + (v - ck[i]) * scale;
-                } else if (c.norm == RN_LINF) {
-                    v = ck[i] + clampf(v - ck[i], -c.radius, c.radius);
-                }
-                o[i] = clampf(v, c.lo, c.hi);
+        for (int i = 0; i < 4; ++i) {
+            if (L2) {
+                v[i] = cv[i] + (v[i] - cv[i]) * scale;
+            } else if (c.norm == RN_LINF) {
+                v[i] = cv[i] + clampf(v[i] - cv[i], -c.radius, c.radius);
             }
-            *(float4*)(orow + q * 4) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-            for (int i = 0; i < 4; ++i) {
-                const long j = q * 4 + i;
-                if (j >= c.n) break;
-                float v = fgsm_elem(xr[j], gr[j], sd, has_seed, e, has_mask ? mr[j] : 0.f, has_mask);
-                if (L2) {
-                    const float cv = x0r[j];
-                    v = cv + (v - cv) * scale;
-                } else if (c.norm == RN_LINF) {
-                    const float cv = x0r[j];
-                    v = cv + clampf(v - cv, -c.radius, c.radius);
-                }
-                orow[j] = clampf(v, c.lo, c.hi);
-            }
+            v[i] = clampf(v[i], c.lo, c.hi);
         }
+        store_quad<VEC>(orow, q, c.n, v);
     }
 }
 
@@ -189,20 +157,10 @@ __global__ __launch_bounds__(256) void robust_random_start_kernel(const float* x
                             2.f * philox_uniform(w.w) - 1.f);
         }
         const float zk[4] = {z.x, z.y, z.z, z.w};
-        if (VEC) {
-            const float4 xv = *(const float4*)(xr + q * 4);
-            const float xk[4] = {xv.x, xv.y, xv.z, xv.w};
-            float o[4];
+        lanes<4> o = load_quad<VEC>(xr, q, n);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = clampf(xk[i] + coef * zk[i], lo, hi);
-            *(float4*)(orow + q * 4) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-            for (int i = 0; i < 4; ++i) {
-                const long j = q * 4 + i;
-                if (j >= n) break;
-                orow[j] = clampf(xr[j] + coef * zk[i], lo, hi);
-            }
-        }
+        for (int i = 0; i < 4; ++i) o[i] = clampf(o[i] + coef * zk[i], lo, hi);
+        store_quad<VEC>(orow, q, n, o);
     }
 }
 
@@ -252,19 +210,12 @@ extern "C" int advh_robust_step(const advh_robust_desc* d, int64_t row0, int row
     if ((int64_t)rows * chunks > 0x7fffffff) chunks = 1;
     c.chunks = (int)chunks;
     const bool vec = c.n % 4 == 0 && aligned16(c.x0) && aligned16(c.x) && aligned16(c.grad) && aligned16(c.mask) && aligned16(out);
-    const dim3 grid((unsigned)(rows * chunks)), block(256);
+    const dim3 grid((unsigned)(rows * chunks));
     hipStream_t s = (hipStream_t)stream;
-    if (d->norm == RN_L2) {
-        if (vec)
-            hipLaunchKernelGGL((robust_step_kernel<true, true>), grid, block, 0, s, c, (long)row0, out);
-        else
-            hipLaunchKernelGGL((robust_step_kernel<false, true>), grid, block, 0, s, c, (long)row0, out);
-    } else {
-        if (vec)
-            hipLaunchKernelGGL((robust_step_kernel<true, false>), grid, block, 0, s, c, (long)row0, out);
-        else
-            hipLaunchKernelGGL((robust_step_kernel<false, false>), grid, block, 0, s, c, (long)row0, out);
-    }
+    if (d->norm == RN_L2)
+        launch_vec(vec, robust_step_kernel<true, true>, robust_step_kernel<false, true>, grid, s, c, row0, out);
+    else
+        launch_vec(vec, robust_step_kernel<true, false>, robust_step_kernel<false, false>, grid, s, c, row0, out);
     return ADVH_LAUNCH_CHECK();
 }
 
@@ -273,19 +224,13 @@ extern "C" int advh_robust_random_start(const float* x0, int B, int64_t n, uint6
     if (!x0 || !out || B <= 0 || n <= 0 || (norm != RN_LINF && norm != RN_L2)) return ADVH_EINVAL;
     if (!(radius >= 0.f) || isinf(radius) || !(lo <= hi)) return ADVH_EINVAL;
     const bool vec = n % 4 == 0 && aligned16(x0) && aligned16(out);
-    const dim3 grid(B), block(256);
+    const dim3 grid(B);
     hipStream_t s = (hipStream_t)stream;
-    if (norm == RN_L2) {
-        if (vec)
-            hipLaunchKernelGGL((robust_random_start_kernel<true, true>), grid, block, 0, s, x0, B, (long)n, seed, radius, lo, hi, out);
-        else
-            hipLaunchKernelGGL((robust_random_start_kernel<false, true>), grid, block, 0, s, x0, B, (long)n, seed, radius, lo, hi, out);
-    } else {
-        if (vec)
-            hipLaunchKernelGGL((robust_random_start_kernel<true, false>), grid, block, 0, s, x0, B, (long)n, seed, radius, lo, hi, out);
-        else
-            hipLaunchKernelGGL((robust_random_start_kernel<false, false>), grid, block, 0, s, x0, B, (long)n, seed, radius, lo, hi, out);
-    }
+    if (norm == RN_L2)
+        launch_vec(vec, robust_random_start_kernel<true, true>, robust_random_start_kernel<false, true>, grid, s, x0, B, n, seed, radius, lo, hi, out);
+    else
+        launch_vec(vec, robust_random_start_kernel<true, false>, robust_random_start_kernel<false, false>, grid, s, x0, B, n, seed, radius, lo, hi,
+                   out);
     return ADVH_LAUNCH_CHECK();
 }
 

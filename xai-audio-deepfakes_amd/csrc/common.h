@@ -61,3 +61,10 @@ inline unsigned grid_for(long work, long cap = 8192) {
     const long blocks = (work + 255) / 256;
     return (unsigned)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
 }
+
+// One launch of a kernel that exists in a float4 and a scalar form (`template <bool VEC>`): `vec`, the entry point's own
+// alignment predicate, picks the instantiation.  256 threads, no dynamic LDS; the arguments convert to the kernel's parameter types.
+template <class... P, class... A>
+inline void launch_vec(bool vec, void (*kvec)(P...), void (*kscalar)(P...), dim3 grid, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(vec ? kvec : kscalar, grid, dim3(256), 0, s, static_cast<P>(args)...);
+}

@@ -242,12 +242,7 @@ extern "C" int advh_concept_gram(const float* X, int64_t ldx, const float* Y, in
     const bool vec = aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0;
     const dim3 grid((unsigned)p.nblk, (unsigned)p.nslab);
     hipStream_t s = (hipStream_t)stream;
-    if (vec)
-        hipLaunchKernelGGL(gram_partial_kernel<true>, grid, dim3(256), 0, s, X, (long)ldx, Y, (long)ldy, M, N, (long)F, p.slab, p.bn, symmetric,
-                           workspace);
-    else
-        hipLaunchKernelGGL(gram_partial_kernel<false>, grid, dim3(256), 0, s, X, (long)ldx, Y, (long)ldy, M, N, (long)F, p.slab, p.bn, symmetric,
-                           workspace);
+    launch_vec(vec, gram_partial_kernel<true>, gram_partial_kernel<false>, grid, s, X, ldx, Y, ldy, M, N, F, p.slab, p.bn, symmetric, workspace);
     if (ADVH_LAUNCH_CHECK() != ADVH_OK) return ADVH_ELAUNCH;
     hipLaunchKernelGGL(gram_fold_kernel, dim3(grid_for((long)M * N, GRID_CAP)), dim3(256), 0, s, workspace, M, N, p.nslab, symmetric, G);
     return ADVH_LAUNCH_CHECK();
@@ -261,10 +256,7 @@ extern "C" int advh_concept_combine(const float* A, const float* X, int64_t ldx,
     hipStream_t s = (hipStream_t)stream;
     for (int c0 = 0; c0 < C; c0 += CB) {
         const int nc = C - c0 < CB ? C - c0 : CB;
-        if (vec)
-            hipLaunchKernelGGL(combine_kernel<4>, dim3(grid_for((long)F / 4, GRID_CAP)), dim3(256), 0, s, A, X, (long)ldx, c0, nc, N, (long)F, W, (long)ldw);
-        else
-            hipLaunchKernelGGL(combine_kernel<1>, dim3(grid_for((long)F, GRID_CAP)), dim3(256), 0, s, A, X, (long)ldx, c0, nc, N, (long)F, W, (long)ldw);
+        launch_vec(vec, combine_kernel<4>, combine_kernel<1>, dim3(grid_for(vec ? (long)F / 4 : (long)F, GRID_CAP)), s, A, X, ldx, c0, nc, N, F, W, ldw);
         if (ADVH_LAUNCH_CHECK() != ADVH_OK) return ADVH_ELAUNCH;
     }
     return ADVH_OK;

@@ -107,6 +107,25 @@ __device__ __forceinline__ void store_h_rt(_Float16* base, long o, long lo_off, 
         *(hvec*)(base + o) = hv;
     }
 }
+// one element, the scalar tail of a kernel whose vector form stores through store_h_rt: the checked conversion per value
+__device__ __forceinline__ void store_h1(_Float16* base, long o, long lo_off, float v) {
+    if (lo_off) {
+        _Float16 h, l;
+        split_f32(v, h, l);
+        base[o] = h;
+        base[o + lo_off] = l;
+    } else {
+        base[o] = (_Float16)v;
+    }
+}
+// the W values of one item of a float4 / scalar kernel pair (W = 4 or 1)
+template <int W>
+__device__ __forceinline__ void store_h_item(_Float16* base, long o, long lo_off, const float (&v)[W]) {
+    if constexpr (W == 1)
+        store_h1(base, o, lo_off, v[0]);
+    else
+        store_h_rt<W>(base, o, lo_off, v);
+}
 template <int VW>
 __device__ __forceinline__ void load_h_rt(const _Float16* base, long o, long lo_off, float (&v)[VW]) {
     typedef _Float16 hvec __attribute__((ext_vector_type(VW)));

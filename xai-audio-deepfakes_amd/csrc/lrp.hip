@@ -307,14 +307,7 @@ __global__ __launch_bounds__(256) void gelu_identity_bwd_kernel(const _Float16* 
         const float dv = d_lo ? join_f32(d[i], d[i + d_lo]) : (float)d[i];
         const float gv = g1_lo ? join_f32(g1[i], g1[i + g1_lo]) : (float)g1[i];
         const float o = dv * lrp_phi(gv);
-        if (out_lo) {
-            _Float16 h, l;
-            split_f32(o, h, l);
-            out[i] = h;
-            out[i + out_lo] = l;
-        } else {
-            out[i] = (_Float16)o;
-        }
+        store_h1(out, i, out_lo, o);
     }
 }
 
@@ -390,12 +383,7 @@ extern "C" int advh_gelu_identity_bwd(const void* d, int64_t d_lo, const void* g
     if (blocks > 8192) blocks = 8192;
     if (blocks < 1) blocks = 1;
     hipStream_t s = (hipStream_t)stream;
-    if (vec)
-        hipLaunchKernelGGL(gelu_identity_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, (const _Float16*)d, (long)d_lo,
-                           (const _Float16*)g1, (long)g1_lo, (_Float16*)out, (long)out_lo, (long)n);
-    else
-        hipLaunchKernelGGL(gelu_identity_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, (const _Float16*)d, (long)d_lo,
-                           (const _Float16*)g1, (long)g1_lo, (_Float16*)out, (long)out_lo, (long)n);
+    launch_vec(vec, gelu_identity_bwd_kernel<true>, gelu_identity_bwd_kernel<false>, dim3((unsigned)blocks), s, d, d_lo, g1, g1_lo, out, out_lo, n);
     return ADVH_LAUNCH_CHECK();
 }
 
