@@ -1057,7 +1057,9 @@ int advh_conv_taps_f16(const advh_taps_desc* d, int C, advh_stream_t stream);
 /* ---- training step of the U-Net mask decoder (addvisor.py:12-84 under train_addvisor.py:364-378)
  * Maps are zero-haloed channels-last fp16 [B][H+2PH][W+2PW][C]; only interiors are read for statistics / written.
  * BatchNorm2d in training mode (batch statistics over B*H*W, eps 1e-5) around LeakyReLU(slope):
- *   advh_bn_stats     sums[0..C) = sum z, sums[C..2C) = sum z^2 (deterministic two-stage; partial: advh_bn_partial_count()*2*C floats)
+ *   advh_bn_stats     sums[0..C) = sum z, sums[C..2C) = sum (z - mean)^2 >= 0, formed from fp64 sums of z and z^2 (an fp32 sum z^2
+ *                     loses mu^2/sigma^2 of its digits to sum z^2 / n - mean^2) and rounded once; deterministic two-stage;
+ *                     partial64: advh_bn_partial_count()*2*C DOUBLES -- twice the bytes of every other `partial` here
  *   advh_bn_apply     a = lrelu(coef[c]*z + coef[C+c])                        coef = [scale | shift | mean | invstd], 4*C floats
  *   advh_bn_bwd_sums  with dy^ = g_a * lrelu'(scale*z+shift), z^ = (z-mean)*invstd: sums = [sum dy^ | sum dy^ z^]
  *   advh_bn_bwd_apply dz = coef_b[c]*(dy^ - coef_b[C+c] - z^*coef_b[2C+c]) written at dz + d_c0 + b*d_sB + h*d_sH + w*d_sW
@@ -1073,7 +1075,7 @@ int advh_bn_coef(const float* sums, const float* gamma, const float* beta, int C
                  float* running_mean, float* running_var, int64_t* num_batches_tracked, float* coef, advh_stream_t stream);
 int advh_bn_bwd_coef(const float* sums, const float* coef, int C, float n, float inv_scale, float* coef_b, float* dgamma,
                      float* dbeta, advh_stream_t stream);
-int advh_bn_stats(const void* z, const advh_map_geom* g, float* partial, float* sums, advh_stream_t stream);
+int advh_bn_stats(const void* z, const advh_map_geom* g, double* partial64, float* sums, advh_stream_t stream);
 int advh_bn_apply(const void* z, const advh_map_geom* g, const float* coef, float slope, void* a, advh_stream_t stream);
 int advh_bn_bwd_sums(const void* z, const void* g_a, int g_f32, const advh_map_geom* g, const float* coef, float slope,
                      float* partial, float* sums, advh_stream_t stream);
@@ -1107,7 +1109,7 @@ int advh_unet_stem_wgrad(const void* dz, int Fq, int Tq, int B, int H, int W, co
  * elements between the planes), so LeakyReLU takes the branch the fp32 reference takes and the weight / activation
  * gradients keep ~22 bits.  The convolutions, dgrads and split-K wgrads are advh_gemm_f16 launches with desc.split = 1;
  * advh_transpose_gather is called once per plane.  g_a is a split map here.                                              */
-int advh_bn_stats_split(const void* z, int64_t z_lo, const advh_map_geom* g, float* partial, float* sums, advh_stream_t stream);
+int advh_bn_stats_split(const void* z, int64_t z_lo, const advh_map_geom* g, double* partial64, float* sums, advh_stream_t stream);
 int advh_bn_apply_split(const void* z, int64_t z_lo, const advh_map_geom* g, const float* coef, float slope, void* a, int64_t a_lo,
                         advh_stream_t stream);
 int advh_bn_bwd_sums_split(const void* z, int64_t z_lo, const void* g_a, int64_t g_lo, const advh_map_geom* g, const float* coef,

@@ -215,6 +215,7 @@ class HipUNetTrain:
                   mask=torch.empty(B, H, W, dtype=torch.float32, device=dev), logits=torch.empty(B, H, W, dtype=torch.float32, device=dev),
                   dlogit=torch.empty(B, H, W, dtype=torch.float32, device=dev),
                   partial=torch.empty(self.nparts * 2 * 512, dtype=torch.float32, device=dev),
+                  partial64=torch.empty(self.nparts * 2 * 512, dtype=torch.float64, device=dev),      # advh_bn_stats' fp64 partials
                   sums=torch.empty(2 * 512, dtype=torch.float32, device=dev))
         self._ws[key] = ws
         return ws
@@ -363,13 +364,13 @@ class HipUNetTrain:
             _lib.check(lib.advh_bn_apply(zmap.t.data_ptr(), C.byref(gm), L["coef"].data_ptr(), SLOPE, amap.t.data_ptr(), st), "advh_bn_apply")
 
     def _bn_stats(self, fmap: G.FMap, ws):
-        """per-channel (sum, sum of squares) of a map's interior -> ws["sums"]"""
+        """per-channel (sum, sum of squared deviations from the mean) of a map's interior -> ws["sums"]"""
         lib, st, gm = _lib.lib(), _st(), _geom(fmap)
         if self.split:
-            _lib.check(lib.advh_bn_stats_split(fmap.t.data_ptr(), fmap.t.stride(0), C.byref(gm), ws["partial"].data_ptr(),
+            _lib.check(lib.advh_bn_stats_split(fmap.t.data_ptr(), fmap.t.stride(0), C.byref(gm), ws["partial64"].data_ptr(),
                                                ws["sums"].data_ptr(), st), "advh_bn_stats_split")
         else:
-            _lib.check(lib.advh_bn_stats(fmap.t.data_ptr(), C.byref(gm), ws["partial"].data_ptr(), ws["sums"].data_ptr(), st), "advh_bn_stats")
+            _lib.check(lib.advh_bn_stats(fmap.t.data_ptr(), C.byref(gm), ws["partial64"].data_ptr(), ws["sums"].data_ptr(), st), "advh_bn_stats")
 
     def forward(self, mag: torch.Tensor, H: int = 512, W: Optional[int] = None) -> torch.Tensor:
         if mag.dim() != 3 or mag.dtype != torch.float32 or not mag.is_cuda:

@@ -28,9 +28,13 @@ __device__ __forceinline__ bool interior(const MapGeom& g, long row, int& b, int
     return h >= g.PH && h < g.PH + g.H && w >= g.PW && w < g.PW + g.W;
 }
 
-// MODE 0: (sum z, sum z^2).  MODE 1 (BatchNorm backward): with y = scale*z + shift, dy^ = g * lrelu'(y),
-// z^ = (z - mean) * invstd: (sum dy^, sum dy^ z^).  coef = [scale | shift | mean | invstd] (4 x C floats).
-// One thread owns 8 channels of every (NPART * lanes_per_chunk)-th row.
+// First stages of the two per-channel reductions; one thread owns 8 channels of every (NPART * lanes_per_chunk)-th row.
+// Forward (bn_stats_partial_kernel): (sum z, sum z^2), accumulated, combined and handed on in fp64.  The variance
+// sum z^2 / n - mean^2 cancels mu^2 / sigma^2 of the digits its sums carry: with fp32 sums an activation offset of 8 sigma
+// left 1e-5 and one of 64 sigma 1e-3 of invstd (two values 1e-3 apart, n = 2, lost everything); fp64 sums carry z^2 exactly
+// and leave 1e-16 mu^2 / sigma^2, without a second pass over z -- these kernels are HBM-bound.
+// Backward (bn_partial_kernel): with y = scale*z + shift, dy^ = g * lrelu'(y), z^ = (z - mean) * invstd: (sum dy^, sum dy^ z^),
+// fp32 partials (z^ is centred already).  coef = [scale | shift | mean | invstd] (4 x C floats).
 // fp32, fp16 (lo == 0) or a split-format plane pair (lo = distance to the lo plane; device_math.h)
 __device__ __forceinline__ void load_g8(const void* g, bool f32, long off, float (&o)[8], long lo = 0) {
     if (f32) {
@@ -43,7 +47,6 @@ __device__ __forceinline__ void load_g8(const void* g, bool f32, long off, float
 
 // The incoming gradient g may be fp32: BatchNorm's backward subtracts its per-channel mean, so an fp16 g would lose
 // exactly the part that survives (the dgrad GEMM accumulates in fp32 and can store fp32).
-template <int MODE>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const _Float16* __restrict__ z, const void* __restrict__ g, bool g_f32,
                                                          const float* __restrict__ coef, float slope, MapGeom gm,
                                                          float* __restrict__ partial /*[NPART][2][C]*/, long z_lo, long g_lo) {
@@ -55,10 +58,8 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const _Float16* __restr
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         s1[j] = s2[j] = 0.f;
-        if (MODE == 1) {
-            const int c = ch * 8 + j;
-            sc[j] = coef[c]; sh[j] = coef[gm.C + c]; mu[j] = coef[2 * gm.C + c]; is[j] = coef[3 * gm.C + c];
-        }
+        const int c = ch * 8 + j;
+        sc[j] = coef[c]; sh[j] = coef[gm.C + c]; mu[j] = coef[2 * gm.C + c]; is[j] = coef[3 * gm.C + c];
     }
     if (rl < RL) {
         for (long row = (long)blockIdx.x * RL + rl; row < rows; row += (long)gridDim.x * RL) {
@@ -66,19 +67,14 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const _Float16* __restr
             if (!interior(gm, row, b, h, w)) continue;
             float zv[8];
             load_h_rt<8>(z, row * gm.C + ch * 8, z_lo, zv);
-            if (MODE == 0) {
+            float gv[8];
+            load_g8(g, g_f32, row * gm.C + ch * 8, gv, g_lo);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { float v = zv[j]; s1[j] += v; s2[j] = fmaf(v, v, s2[j]); }
-            } else {
-                float gv[8];
-                load_g8(g, g_f32, row * gm.C + ch * 8, gv, g_lo);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    float zz = zv[j], y = fmaf(sc[j], zz, sh[j]);
-                    float d = gv[j] * (y > 0.f ? 1.f : slope);
-                    s1[j] += d;
-                    s2[j] = fmaf(d, (zz - mu[j]) * is[j], s2[j]);
-                }
+            for (int j = 0; j < 8; ++j) {
+                float zz = zv[j], y = fmaf(sc[j], zz, sh[j]);
+                float d = gv[j] * (y > 0.f ? 1.f : slope);
+                s1[j] += d;
+                s2[j] = fmaf(d, (zz - mu[j]) * is[j], s2[j]);
             }
         }
     }
@@ -105,6 +101,54 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
     if (lane == 0) sums[i] = (float)a;
 }
 
+// forward statistics, first stage: bn_partial_kernel's thread layout (one thread owns 8 channels of every (NPART * RL)-th row)
+// with fp64 accumulators and fp64 partials [NPART][2][C]
+__global__ __launch_bounds__(256) void bn_stats_partial_kernel(const _Float16* __restrict__ z, MapGeom gm, double* __restrict__ partial, long z_lo) {
+    __shared__ double red[256 * 16];
+    const int CH = gm.C / 8, tid = threadIdx.x;
+    const int ch = tid % CH, rl = tid / CH, RL = 256 / CH;
+    const long rows = (long)gm.B * gm.Hp * gm.Wp;
+    double s1[8], s2[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.0;
+    if (rl < RL) {
+        for (long row = (long)blockIdx.x * RL + rl; row < rows; row += (long)gridDim.x * RL) {
+            int b, h, w;
+            if (!interior(gm, row, b, h, w)) continue;
+            float zv[8];
+            load_h_rt<8>(z, row * gm.C + ch * 8, z_lo, zv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const double v = (double)zv[j]; s1[j] += v; s2[j] = fma(v, v, s2[j]); }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { red[tid * 16 + j] = s1[j]; red[tid * 16 + 8 + j] = s2[j]; }
+    __syncthreads();
+    for (int o = tid; o < 16 * CH; o += 256) {                  // one thread per output: fixed-order sum over the row lanes of its chunk
+        const int t = o >> 4, j = o & 15;
+        double a = 0.0;
+        for (int r = 0; r < RL; ++r) a += red[(r * CH + t) * 16 + j];
+        partial[((long)blockIdx.x * 2 + (j >> 3)) * gm.C + t * 8 + (j & 7)] = a;
+    }
+}
+
+// second stage of the forward statistics: one wavefront per channel adds both columns of partials in a fixed order and forms
+// sums[c] = sum z, sums[C + c] = sum (z - mean)^2 = sum z^2 - (sum z)^2 / n in fp64 (exactly 0 for a channel of ones); one fp32
+// rounding each
+__global__ __launch_bounds__(256) void bn_stats_reduce_kernel(const double* __restrict__ partial, int nparts, int C, double n,
+                                                              float* __restrict__ sums) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= C) return;
+    double a = 0.0, q = 0.0;
+    for (int p = lane; p < nparts; p += 64) { a += partial[(long)p * 2 * C + c]; q += partial[(long)p * 2 * C + C + c]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); q += __shfl_xor(q, o, 64); }
+    if (lane == 0) {
+        sums[c] = (float)a;
+        sums[C + c] = (float)fmax(q - a * a / n, 0.0);
+    }
+}
+
 // per-channel coefficients from the reduced sums (one thread per channel): replaces a dozen tiny tensor ops per layer.
 // forward: coef = [scale | shift | mean | invstd], running statistics updated as nn.BatchNorm2d does in train() mode
 // (momentum, unbiased variance).  backward: coef_b = [k1 | m1 | m2], dgamma = sum dy^ z^ / S, dbeta = sum dy^ / S.
@@ -115,7 +159,7 @@ __global__ void bn_coef_kernel(const float* __restrict__ sums, const float* __re
     if (c == 0 && nbt) *nbt += 1;
     if (c >= C) return;
     const float mean = sums[c] / n;
-    const float var = fmaxf(sums[C + c] / n - mean * mean, 0.f);
+    const float var = sums[C + c] / n;                       // sums[C + c] = sum (z - mean)^2 >= 0 (advh_bn_stats)
     const float invstd = rsqrtf(var + eps), scale = gamma[c] * invstd;
     coef[c] = scale; coef[C + c] = beta[c] - mean * scale; coef[2 * C + c] = mean; coef[3 * C + c] = invstd;
     if (rmean) {
@@ -434,20 +478,20 @@ static MapGeom mk(const advh_map_geom* g) { return MapGeom{g->B, g->H + 2 * g->P
 
 extern "C" int advh_bn_partial_count(void) { return NPART; }
 
-static int bn_stats_launch(const void* z, long z_lo, const advh_map_geom* g, float* partial, float* sums, advh_stream_t stream) {
-    if (!z || !partial || !sums || !geom_ok(g)) return ADVH_EINVAL;
+static int bn_stats_launch(const void* z, long z_lo, const advh_map_geom* g, double* partial, float* sums, advh_stream_t stream) {
+    if (!z || !partial || !sums || !geom_ok(g) || ((uintptr_t)partial & 7)) return ADVH_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(NPART), dim3(256), 0, s, (const _Float16*)z, (const void*)nullptr, false,
-                       (const float*)nullptr, 0.f, mk(g), partial, z_lo, 0L);
-    hipLaunchKernelGGL(bn_reduce_kernel, dim3((2 * g->C + 3) / 4), dim3(256), 0, s, partial, NPART, g->C, sums);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(NPART), dim3(256), 0, s, (const _Float16*)z, mk(g), partial, z_lo);
+    hipLaunchKernelGGL(bn_stats_reduce_kernel, dim3((g->C + 3) / 4), dim3(256), 0, s, partial, NPART, g->C,
+                       (double)g->B * g->H * g->W, sums);
     return ADVH_LAUNCH_CHECK();
 }
-extern "C" int advh_bn_stats(const void* z, const advh_map_geom* g, float* partial, float* sums, advh_stream_t stream) {
-    return bn_stats_launch(z, 0, g, partial, sums, stream);
+extern "C" int advh_bn_stats(const void* z, const advh_map_geom* g, double* partial64, float* sums, advh_stream_t stream) {
+    return bn_stats_launch(z, 0, g, partial64, sums, stream);
 }
-extern "C" int advh_bn_stats_split(const void* z, int64_t z_lo, const advh_map_geom* g, float* partial, float* sums, advh_stream_t stream) {
+extern "C" int advh_bn_stats_split(const void* z, int64_t z_lo, const advh_map_geom* g, double* partial64, float* sums, advh_stream_t stream) {
     if (z_lo <= 0 || z_lo % 8) return ADVH_EINVAL;
-    return bn_stats_launch(z, z_lo, g, partial, sums, stream);
+    return bn_stats_launch(z, z_lo, g, partial64, sums, stream);
 }
 
 extern "C" int advh_bn_coef(const float* sums, const float* gamma, const float* beta, int C, float n, float eps, float momentum,
@@ -489,7 +533,7 @@ static int bn_bwd_sums_launch(const void* z, long z_lo, const void* g_a, int g_f
                               float slope, float* partial, float* sums, advh_stream_t stream) {
     if (!z || !g_a || !coef || !partial || !sums || !geom_ok(g)) return ADVH_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(NPART), dim3(256), 0, s, (const _Float16*)z, g_a, g_f32 != 0, coef, slope,
+    hipLaunchKernelGGL(bn_partial_kernel, dim3(NPART), dim3(256), 0, s, (const _Float16*)z, g_a, g_f32 != 0, coef, slope,
                        mk(g), partial, z_lo, g_lo);
     hipLaunchKernelGGL(bn_reduce_kernel, dim3((2 * g->C + 3) / 4), dim3(256), 0, s, partial, NPART, g->C, sums);
     return ADVH_LAUNCH_CHECK();
