@@ -1199,6 +1199,66 @@ int advh_concept_gram(const float* X, int64_t ldx, const float* Y, int64_t ldy, 
 int advh_concept_combine(const float* A, const float* X, int64_t ldx, int C, int N, int64_t F, float* W, int64_t ldw, advh_stream_t stream);
 int advh_concept_time_pool(const float* X, int64_t R, int T, int H, int mode, float* out, advh_stream_t stream);
 
+/* Training-data influence (captum.influence: SimilarityInfluence, TracInCPFast; influence functions, Koh & Liang 2017) -- csrc/influence.hip.
+ * Rows are fp32, contiguous, with a row stride in floats; every result is bit-identical from run to run (no atomics, one fixed summation
+ * order); every argument check precedes the first HIP call.  16-byte loads are issued only where the base pointer and the stride are
+ * 16-byte aligned; anything else (4-byte aligned) is read with 4-byte loads.
+ *
+ * advh_influence_moment: Hm[f][g] = sum_i w[i] * X[i][f] * X[i][g] for X [N][F] (stride ldx >= F); w [N] or NULL (all ones); Hm double
+ * [F][F].  The N rows are cut into slabs of S rows, S = max(512, ceil(N / max(1, 1024 / (b (b + 1) / 2))) rounded up to a multiple of 32),
+ * b = ceil(F / 64): each slab's fp32 partial -- one i-ordered fmaf chain per entry on v_mfma_f32_16x16x4_f32, the product w[i] * X[i][g]
+ * rounded to fp32 first -- goes to `workspace` (advh_influence_moment_workspace(N, F) BYTES, = ceil(N / S) * F * F * 4) and a second
+ * launch adds the slabs in ascending order in fp64.  Only the 64 x 64 blocks on or above the diagonal are computed; Hm[f][g], f > g, is
+ * Hm[g][f] bit for bit.  ADVH_EINVAL: a null X / workspace / Hm, N outside [1, 2^24], F outside [1, 4096], ldx < F, X / w / workspace not
+ * 4-byte or Hm not 8-byte aligned.
+ *
+ * advh_influence_sqdist: D[i][j] = sum_f (X[i][f] - Y[j][f])^2 for X [M][F], Y [N][F]; D double [M][N].  Direct differences (no
+ * a + b - 2 G).  The tiling, the slab length S and the workspace size are advh_concept_gram's (non-symmetric form); within a slab an entry
+ * is one fp32 chain acc = fmaf(d, d, acc), d = x - y, f ascending; the slabs are added in ascending order in fp64.  With Y == X (same
+ * pointer and stride) the diagonal is exactly 0 and D is bitwise symmetric.  ADVH_EINVAL as advh_concept_gram.
+ *
+ * advh_influence_sumsq: out[i] = sum_f X[i][f]^2, double [M].  A row is cut into slabs of 16 floats; a slab is one fp32 chain
+ * acc = fmaf(x, x, acc), f ascending from 0.f; the slabs are added in ascending order in fp64.  ADVH_EINVAL: a null or misaligned
+ * pointer, M outside [1, 2^24], F outside [1, 2^40], ldx < F.
+ *
+ * advh_influence_residual: out[c][n] = sigma(Z[n][c]) - y[n]; Z double [N][C] (logits: advh_concept_gram of feature rows against
+ * checkpoint rows), y float [N] in {0, 1}, out float [C][N].  The sigmoid is fp64 (exp of a non-positive argument only; for y = 1 the
+ * difference is formed as -sigma(-z), which does not cancel), rounded once.  ADVH_EINVAL: a null or misaligned pointer, N outside [1, 2^24], C outside [1, 65536].
+ *
+ * advh_influence_cosine: out[m][n] = G[m][n] / (sqrt(a[m]) * sqrt(b[n])), 0 where a[m] or b[n] is 0 (Captum's cosine_similarity with
+ * replace_nan = 0); G double [M][N] contiguous, a double [M], b double [N], out float with row stride ldo >= N; fp64, rounded once.
+ * advh_influence_root: out[m][n] = sqrt(D[m][n]) (the euclidean distance from advh_influence_sqdist), fp64, rounded once.
+ * advh_influence_scale: out[m][n] = G[m][n] * sum_c (lr[c] * rt[c][m]) * rn[c][n]; c ascending from 0.0 in fp64, every product and sum
+ * rounded on its own (no fma), rounded once to fp32.  lr double [C], rt float [C][M], rn float [C][N].  C = 1 with lr = {1} is the
+ * influence-function form.  ADVH_EINVAL (all three): a null or misaligned pointer, M outside [1, 2^20], N outside [1, 2^24], ldo < N, C
+ * outside [1, 65536].
+ * advh_influence_self_scale: out[n] = ss[n] * sum_c (lr[c] * rn[c][n]) * rn[c][n] -- the scale kernel's product on the diagonal (TracIn's
+ * self-influence from ss = advh_influence_sumsq), same rounding; ss double [N], out float [N].  ADVH_EINVAL: a null or misaligned pointer,
+ * N outside [1, 2^24], C outside [1, 65536].
+ *
+ * advh_influence_topk: per row m of S float [M][N] (stride lds >= N) the k extreme entries in order -- value descending for largest = 1,
+ * ascending for largest = 0, ties to the lower index, -0.0 == +0.0: exactly np.argsort(-+S[m], kind="stable")[:k] on finite input (NaN
+ * is not ordered).  idx int32 [M][k], val float [M][k] (the entries of S themselves).  A row is sorted in chunks of 2048 entries that
+ * keep k each; the kept entries are sorted again in chunks of 2048 until one chunk is left.  `workspace` holds the kept 8-byte keys of
+ * the first two passes: advh_influence_topk_workspace(M, N, k) BYTES = max(16, 8 * M * k * (c1 + c2)), c1 = ceil(N / 2048) counted only
+ * if > 1, c2 = ceil(c1 * k / 2048) counted only if c1 > 1 and c2 > 1.  ADVH_EINVAL: a null or misaligned pointer (workspace: 8 bytes),
+ * M outside [1, 65535], N outside [1, 2^24], k outside [1, min(N, 256)], lds < N, largest not in {0, 1}.                             */
+int64_t advh_influence_moment_workspace(int64_t N, int F);
+int advh_influence_moment(const float* X, int64_t ldx, const float* w, int64_t N, int F, float* workspace, double* Hm, advh_stream_t stream);
+int64_t advh_influence_sqdist_workspace(int M, int N, int64_t F);
+int advh_influence_sqdist(const float* X, int64_t ldx, const float* Y, int64_t ldy, int M, int N, int64_t F, float* workspace, double* D,
+                          advh_stream_t stream);
+int advh_influence_sumsq(const float* X, int64_t ldx, int M, int64_t F, double* out, advh_stream_t stream);
+int advh_influence_residual(const double* Z, const float* y, int64_t N, int C, float* out, advh_stream_t stream);
+int advh_influence_cosine(const double* G, const double* a, const double* b, int M, int64_t N, float* out, int64_t ldo, advh_stream_t stream);
+int advh_influence_root(const double* D, int M, int64_t N, float* out, int64_t ldo, advh_stream_t stream);
+int advh_influence_scale(const double* G, const float* rt, const float* rn, const double* lr, int C, int M, int64_t N, float* out, int64_t ldo,
+                         advh_stream_t stream);
+int advh_influence_self_scale(const double* ss, const float* rn, const double* lr, int C, int64_t N, float* out, advh_stream_t stream);
+int64_t advh_influence_topk_workspace(int M, int64_t N, int k);
+int advh_influence_topk(const float* S, int64_t lds, int M, int64_t N, int k, int largest, void* workspace, int* idx, float* val,
+                        advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,18 @@ SIGNATURES = {
     "advh_concept_gram": (_i, [_p, _i64, _p, _i64, _i, _i, _i64, _i, _p, _p, _p]),
     "advh_concept_combine": (_i, [_p, _p, _i64, _i, _i, _i64, _p, _i64, _p]),
     "advh_concept_time_pool": (_i, [_p, _i64, _i, _i, _i, _p, _p]),
+    "advh_influence_moment_workspace": (_i64, [_i64, _i]),
+    "advh_influence_moment": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p]),
+    "advh_influence_sqdist_workspace": (_i64, [_i, _i, _i64]),
+    "advh_influence_sqdist": (_i, [_p, _i64, _p, _i64, _i, _i, _i64, _p, _p, _p]),
+    "advh_influence_sumsq": (_i, [_p, _i64, _i, _i64, _p, _p]),
+    "advh_influence_residual": (_i, [_p, _p, _i64, _i, _p, _p]),
+    "advh_influence_cosine": (_i, [_p, _p, _p, _i, _i64, _p, _i64, _p]),
+    "advh_influence_root": (_i, [_p, _i, _i64, _p, _i64, _p]),
+    "advh_influence_scale": (_i, [_p, _p, _p, _p, _i, _i, _i64, _p, _i64, _p]),
+    "advh_influence_self_scale": (_i, [_p, _p, _p, _i, _i64, _p, _p]),
+    "advh_influence_topk_workspace": (_i64, [_i, _i64, _i]),
+    "advh_influence_topk": (_i, [_p, _i64, _i, _i64, _i, _i, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -27,60 +27,9 @@
 
 #include "addvisor_hip.h"
 #include "common.h"
+#include "slab_tiles.h"   // the staging, the slab plan and the fold, shared with influence.hip
 
 namespace advh {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int GR_BLK = 64;            // output block edge
-constexpr int GR_KC = 64;             // floats of the contraction staged per step
-constexpr int GR_PITCH = GR_KC + 4;   // LDS row pitch (floats): 16-byte aligned rows, 4-bank skew per row
-constexpr int GR_SLAB_MIN = 512;      // shortest slab (floats)
-constexpr long GR_TARGET_WG = 1024;   // workgroups aimed at: four per CU
-
-struct GramPlan {
-    long slab;      // floats per slab, a multiple of GR_KC
-    int nslab;
-    int bm, bn;     // blocks along M, N
-    long nblk;      // blocks launched per slab
-};
-
-static GramPlan gram_plan(int M, int N, long F, int symmetric) {
-    GramPlan p;
-    p.bm = (M + GR_BLK - 1) / GR_BLK;
-    p.bn = (N + GR_BLK - 1) / GR_BLK;
-    p.nblk = symmetric ? (long)p.bm * (p.bm + 1) / 2 : (long)p.bm * p.bn;
-    const long full = (long)p.bm * p.bn;                                 // the plan does not depend on the mode: one workspace size
-    const long maxslabs = GR_TARGET_WG / full > 1 ? GR_TARGET_WG / full : 1;
-    long slab = (F + maxslabs - 1) / maxslabs;
-    slab = (slab + GR_KC - 1) / GR_KC * GR_KC;
-    p.slab = slab < GR_SLAB_MIN ? GR_SLAB_MIN : slab;
-    p.nslab = (int)((F + p.slab - 1) / p.slab);
-    return p;
-}
-
-// rows [r0, r0 + 64) x columns [k0, k0 + 64) of src (row stride ld) -> dst [64][GR_PITCH]; zero past `rows` and past `kend`
-template <bool VEC>
-__device__ __forceinline__ void gram_stage(float* dst, const float* __restrict__ src, long ld, int r0, int rows, long k0, long kend, int tid) {
-#pragma unroll
-    for (int q = 0; q < GR_BLK * GR_KC / 4 / 256; ++q) {
-        const int i = q * 256 + tid, r = i / (GR_KC / 4), c = (i % (GR_KC / 4)) * 4;
-        const long k = k0 + c;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r0 + r < rows && k < kend) {
-            const float* p = src + (long)(r0 + r) * ld + k;
-            if (VEC && k + 3 < kend) {
-                v = *(const float4*)p;
-            } else {
-                v.x = p[0];
-                if (k + 1 < kend) v.y = p[1];
-                if (k + 2 < kend) v.z = p[2];
-                if (k + 3 < kend) v.w = p[3];
-            }
-        }
-        *(float4*)(dst + r * GR_PITCH + c) = v;
-    }
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restrict__ X, long ldx, const float* __restrict__ Y, long ldy, int M,
@@ -90,15 +39,7 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int fr = lane & 15, g = lane >> 4;
     int bi, bj;
-    if (symmetric) {                                                     // blockIdx.x counts the blocks bj >= bi row by row
-        int rest = (int)blockIdx.x, row = 0;
-        while (rest >= bn - row) { rest -= bn - row; ++row; }
-        bi = row;
-        bj = row + rest;
-    } else {
-        bi = (int)blockIdx.x / bn;
-        bj = (int)blockIdx.x % bn;
-    }
+    block_of((int)blockIdx.x, bn, symmetric, bi, bj);
     const int i0 = bi * GR_BLK, j0 = bj * GR_BLK;
     const long kbeg = (long)blockIdx.y * slab, kend = kbeg + slab < F ? kbeg + slab : F;
     const int wi = (wv >> 1) * 32, wj = (wv & 1) * 32;                   // this wavefront's quarter of the block
@@ -145,21 +86,6 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
                 if (i < M && j < N) ps[(long)i * N + j] = acc[a][b][r];
             }
         }
-}
-
-// G[i][j] = sum over slabs, ascending, in fp64.  Symmetric: the blocks below the diagonal were not computed, and every entry
-// below the diagonal is read from its transpose.
-__global__ __launch_bounds__(256) void gram_fold_kernel(const float* __restrict__ part, int M, int N, int nslab, int symmetric,
-                                                        double* __restrict__ G) {
-    const long total = (long)M * N;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-        long i = e / N, j = e - i * N;
-        if (symmetric && i > j) { const long t = i; i = j; j = t; }
-        const float* p = part + i * N + j;
-        double s = 0.0;
-        for (int q = 0; q < nslab; ++q) s += (double)p[(long)q * total];
-        G[e] = s;
-    }
 }
 
 // W[c][f] = fmaf chain over i ascending, from 0.f; one thread owns VW consecutive f of up to CB rows c: X is read once per
@@ -244,7 +170,7 @@ extern "C" int advh_concept_gram(const float* X, int64_t ldx, const float* Y, in
     hipStream_t s = (hipStream_t)stream;
     launch_vec(vec, gram_partial_kernel<true>, gram_partial_kernel<false>, grid, s, X, ldx, Y, ldy, M, N, F, p.slab, p.bn, symmetric, workspace);
     if (ADVH_LAUNCH_CHECK() != ADVH_OK) return ADVH_ELAUNCH;
-    hipLaunchKernelGGL(gram_fold_kernel, dim3(grid_for((long)M * N, GRID_CAP)), dim3(256), 0, s, workspace, M, N, p.nslab, symmetric, G);
+    hipLaunchKernelGGL(gram_fold_kernel<double>, dim3(grid_for((long)M * N, GRID_CAP)), dim3(256), 0, s, workspace, M, N, p.nslab, symmetric, G);
     return ADVH_LAUNCH_CHECK();
 }
 
