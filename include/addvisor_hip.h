@@ -1259,6 +1259,60 @@ int64_t advh_influence_topk_workspace(int M, int64_t N, int k);
 int advh_influence_topk(const float* S, int64_t lds, int M, int64_t N, int k, int largest, void* workspace, int* idx, float* val,
                         advh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-clip optimised mask explanations (csrc/mask_opt.hip): Fong & Vedaldi's meaningful perturbation (2017) and extremal
+ * perturbations (2019) over the STFT mask, restated from the papers (no Captum class exists).  Per clip b the parameters
+ * theta[b] [Fc][Tc] live on a coarse grid, K = Fc * Tc; p = 1 / (1 + expf(-theta)); m = U p on [Fm][Tm], U torch's bilinear
+ * upsampling (align_corners = False): per axis, fine index d of N reads the coarse points i0, i1 of n with
+ *   src = max((d + 0.5) n / N - 0.5, 0), i0 = min(floor(src), n - 1), i1 = min(i0 + 1, n - 1), w1 = src - i0, w0 = 1 - w1
+ * (in integers: 2 N src = max((2 d + 1) n - N, 0), i0 its quotient by 2 N and w1 the remainder over 2 N, one correctly rounded
+ * fp32 division), and m[f][t] = (p[i0f][i0t] w0t + p[i0f][i1t] w1t) w0f +
+ * (p[i1f][i0t] w0t + p[i1f][i1t] w1t) w1f, every product rounded on its own.  All three entry points work on the clips
+ * b0 .. b0 + nb - 1 of theta / rank / sign / p / hist (each [B][...]) and on chunk-local rows 2j (mask-in), 2j + 1 (mask-out) of clip
+ * b0 + j -- the clip-major layout of advh_istft_masked_rows with S = 2, row0 = 2 b0.  Deterministic: no atomics, a fixed order.
+ *
+ * advh_mask_opt_rows : rows[2j] = m of clip b0 + j, rows[2j + 1] = 1.f - rows[2j], [2 nb][Fm * Tm].  float4 stores when
+ *                      Tm % 4 == 0 and rows is 16-byte aligned, scalar ones otherwise; the same bits either way.
+ * advh_mask_opt_terms: one workgroup per clip.  With r_k = 1 when rank[b][k] >= K - K1, else 0 (rank: advh_feature_rank of theta,
+ *                      descending = 0),
+ *                        A = (1 / K) sum_k (p_k - r_k)^2,  P = (1 / K) sum_k p_k,
+ *                        TV = (1 / K) sum_{i, j} (p[i + 1][j] - p[i][j])^2 + (p[i][j + 1] - p[i][j])^2   (pairs inside the grid),
+ *                      each sum: thread t adds the cells t, t + 256, ... in that order, then one 256-leaf tree.  From
+ *                      z_in = sign[b] logits[2j], z_out = sign[b] logits[2j + 1] and the reward phi (0: z; 1: sigmoid(z);
+ *                      2: log sigmoid(z)):
+ *                        seeds[2j] = -lam_in sign[b] phi'(z_in),  seeds[2j + 1] = lam_out sign[b] phi'(z_out)
+ *                      (dJ / d logit of the two rows: what EmbedderGrad.backward(seed=) takes), p[b][k] = p_k, and
+ *                        hist[b][0..5] = (z_in, z_out, A, P, TV, J),
+ *                        J = -lam_in phi(z_in) + lam_out phi(z_out) + lam_area A + lam_l1 P + lam_tv TV.
+ * advh_mask_opt_step : one wavefront per (clip, cell k).  With G [2 nb][Fm * Tm] the gradient of the rows under those seeds,
+ *                        g_k = p_k (1 - p_k) (sum_{(f, t)} U[(f, t), k] (G[2j][f][t] - G[2j + 1][f][t]) + lam_area (2 / K) (p_k - r_k)
+ *                              + lam_l1 / K + lam_tv dTV / dp_k),
+ *                      the sum over the cell's footprint box row-major, lane l the elements l, l + 64, ..., then a 64-leaf xor
+ *                      butterfly; p is read from the terms launch's output (never from a theta another wavefront updates).
+ *                      grad_theta[b][k] = g_k when grad_theta != NULL.  optimizer 0 (Adam, torch.optim.Adam's defaults' form):
+ *                        m1 = beta1 m1 + (1 - beta1) g, m2 = beta2 m2 + (1 - beta2) g^2,
+ *                        theta -= (lr / bias1) m1 / (sqrt(m2) / sqrt(bias2) + eps),  bias_i = 1 - beta_i^step from the host
+ *                      (fp32 state and arithmetic; 1 - beta_i, lr / bias1 and sqrt(bias2) are formed in double and rounded once);
+ *                      optimizer 1 (SGD): m1 = momentum m1 + g, theta -= lr m1 (m2 unused, may be NULL).  In place.
+ * ADVH_EINVAL before any HIP call: a NULL descriptor or pointer (grad_theta and, for SGD, m2 excepted), B, Fm, Tm, Fc, Tc or
+ * nb <= 0, B > 65535, Fc > Fm, Tc > Tm, Fm or Tm > 32768, B * K > 2^31 - 1, K1 outside [0, K], a reward outside [0, 2], an optimizer outside
+ * [0, 1], a non-finite lr, a clip range outside [0, B), and for Adam a bias correction that is not a positive finite number.   */
+typedef struct advh_mask_opt_desc {
+    int B;                   /* clips theta, rank, sign, p, the state and a history row hold      */
+    int Fm, Tm;              /* the mask                                                          */
+    int Fc, Tc;              /* the coarse grid, K = Fc * Tc                                      */
+    int K1;                  /* cells the ranked-area template sets to 1                          */
+    int reward;              /* 0: logit, 1: prob, 2: log_prob                                    */
+    int optimizer;           /* 0: Adam, 1: SGD with momentum                                     */
+    float lam_in, lam_out, lam_area, lam_l1, lam_tv;
+    double lr, beta1, beta2, eps, momentum; /* double: 1 - beta is formed before the rounding to fp32 */
+} advh_mask_opt_desc;
+int advh_mask_opt_rows(const advh_mask_opt_desc* d, const float* theta, int b0, int nb, float* rows, advh_stream_t stream);
+int advh_mask_opt_terms(const advh_mask_opt_desc* d, const float* theta, const int32_t* rank, const float* sign, const float* logits,
+                        int b0, int nb, float* p, float* seeds, float* hist, advh_stream_t stream);
+int advh_mask_opt_step(const advh_mask_opt_desc* d, float* theta, const float* p, const int32_t* rank, const float* G, int b0, int nb,
+                       double bias1, double bias2, float* m1, float* m2, float* grad_theta, advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,9 @@ SIGNATURES = {
     "advh_influence_self_scale": (_i, [_p, _p, _p, _i, _i64, _p, _p]),
     "advh_influence_topk_workspace": (_i64, [_i, _i64, _i]),
     "advh_influence_topk": (_i, [_p, _i64, _i, _i64, _i, _i, _p, _p, _p, _p]),
+    "advh_mask_opt_rows": (_i, [_p, _p, _i, _i, _p, _p]),
+    "advh_mask_opt_terms": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "advh_mask_opt_step": (_i, [_p, _p, _p, _p, _p, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -27,6 +27,9 @@ mask, or -- GradientShap -- a ``[N_b, Fm, Tm]`` distribution.  The same invarian
 curves over the features of ``tf_feature_mask`` (attribution.py; csrc/attribution_curve.hip).  There too a mask baseline, such as
 a constant 0.5, is the meaningful choice: the zero mask resynthesises silence.
 
+``optimize_mask`` solves for a mask instead of attributing one: the per-clip optimised mask of Fong & Vedaldi (2017, 2019), the
+objective the U-Net mask decoder amortises (mask_opt.py; csrc/mask_opt.hip).
+
 Not in this engine: KernelShap, Lime, FeaturePermutation, NoiseTunnel, the metrics and the attacks over masks
 (NotImplementedError)."""
 from __future__ import annotations
@@ -39,6 +42,7 @@ import torch
 
 from . import _lib, ops
 from . import attribution as A
+from . import mask_opt as MO
 from .attribution import HipAttribution
 
 DOMAINS = ("linear", "log1p")
@@ -190,6 +194,15 @@ class _MaskRows(HipAttribution):
         g = self.eg.backward(self.loss_scale)
         return ops.istft_masked_rows_bwd(g, o.spec, m, o.domain, row0, clip_major, S, o.hop, o.win).view(pts.shape)
 
+    def _row_gradient_seeded(self, pts, seeds_of, row0=0, clip_major=0, S=1):
+        """``_row_gradient`` under per-row seeds: ``seeds_of(logits [R]) -> seed [R]`` (device tensors; ``dJ / d logit`` of each
+        row) runs between the forward and the backward, and the result is the vector-Jacobian product ``[R, n]`` of the rows."""
+        o = self.owner
+        m, waves = self._waves(pts, row0, clip_major, S)
+        logit = self.eg.forward(waves)[0].view(-1).to(torch.float32)
+        g = self.eg.backward(self.loss_scale, seed=seeds_of(logit))
+        return ops.istft_masked_rows_bwd(g, o.spec, m, o.domain, row0, clip_major, S, o.hop, o.win).view(pts.shape)
+
     def _row_logit(self, pts, row0=0, clip_major=0, S=1):
         return self.eg.emb.forward(self._waves(pts, row0, clip_major, S)[1], want_hidden=False)[1].view(-1)
 
@@ -329,6 +342,37 @@ class HipSpectralAttribution:
         return self._rows.curve_summary(x, attr, feature_mask=fm, steps=steps, baselines=base, use_abs=use_abs, pool=pool,
                                         internal_batch_size=internal_batch_size)
 
+    def optimize_mask(self, area=0.1, steps: int = 100, cell=(16, 4), shape=None, lam_in: float = 1.0, lam_out: float = 1.0,
+                      lam_area: Optional[float] = None, lam_l1: float = 0.0, lam_tv: float = 0.0, reward: str = "log_prob", target=None,
+                      optimizer: str = "adam", lr: float = 0.05, momentum: float = 0.9, init=0.5,
+                      init_noise: float = MO.DEFAULT_INIT_NOISE, seed: Optional[int] = None, internal_batch_size: Optional[int] = None,
+                      trace: Optional[list] = None) -> "MO.MaskOptResult":
+        """The per-clip optimised mask (Fong & Vedaldi 2017; Fong, Patrick & Vedaldi 2019; mask_opt.py states the objective):
+        "the smallest ``area`` * 100 % of the spectrogram that keeps the decision", solved for each clip of the engine against the
+        classifier itself, ``steps`` updates of ``optimizer`` (``"adam"``: torch.optim.Adam's defaults at ``lr``; ``"sgd"``:
+        ``momentum``) on a coarse grid of ``cell = (bins, frames)`` cells under the mask ``shape = (Fm, Tm)`` (None: the full
+        ``(513, T)``).  ``reward``: ``"logit"``, ``"prob"`` or ``"log_prob"``; ``target``: None (each clip's predicted class, the
+        sign of ``F(ones)``) or ``[B]`` labels in {0, 1}; ``lam_area`` defaults to 10 with an area and to 0 without one.
+
+        Scale invariance: in the ``linear`` domain ``F(alpha m) = F(m)``, so a plain L1 penalty shrinks the mask towards the
+        silent clip, where the gradient grows as ``1 / alpha`` and the engine raises; the ranked-area constraint pins a share
+        ``area`` in (0, 1) of the cells at 1 instead.  ``area=None`` (the 2017 formulation with ``lam_l1`` / ``lam_tv``) is
+        accepted only with ``domain="log1p"``; otherwise ValueError, before any device work.
+
+        Ties: the rank breaks ties by index, so from a constant start the area term would push the high-index cells (high
+        frequency, late frames) to 1.  ``init`` is a number in (0, 1) or a ``[B, Fc, Tc]`` / ``[B, Fm, Tm]`` tensor of mask values
+        (a fine-grid one is box-averaged to the grid: the U-Net's mask, a normalised attribution); ``init_noise`` is the sigma of
+        a normal added to theta, drawn once on the host from a ``torch.Generator`` seeded with ``seed``, and defaults to a small
+        non-zero value.
+
+        Chunks hold whole clips (at most ``internal_batch_size`` rows, default 128, two rows per clip, at least one clip); the
+        clips are independent, so the result does not depend on the chunking.  ``trace``, a list, receives per step the clones
+        ``(theta_k, grad_theta_k, logits_k [2B], seeds_k [2B])`` the update read.  One finiteness check at the end:
+        FloatingPointError naming ``loss_scale`` instead of a poisoned mask.  Returns a ``MaskOptResult``."""
+        return MO.optimize(self, MO.check_mask_opt_args(self.B, self.T, self.domain, area, steps, cell, shape, lam_in, lam_out, lam_area,
+                                                        lam_l1, lam_tv, reward, target, optimizer, lr, momentum, init, init_noise, seed,
+                                                        internal_batch_size, trace))
+
     def pool(self, attr, band_bins: int = 64, seg_frames: Optional[int] = None) -> torch.Tensor:
         """``tf_pool``: the per-band (x per-segment) relevance of an attribution map."""
         return tf_pool(attr, band_bins, seg_frames)
@@ -338,7 +382,7 @@ def _not_here(name):
     def method(self, *args, **kwargs):
         raise NotImplementedError(f"HipSpectralAttribution does not implement {name} over STFT masks; it offers logits, saliency, "
                                   "input_x_gradient, integrated_gradients, gradient_shap, occlusion, feature_ablation, "
-                                  "shapley_value_sampling and pool")
+                                  "shapley_value_sampling, optimize_mask and pool")
     method.__name__ = name
     return method
 

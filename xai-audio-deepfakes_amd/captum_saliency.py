@@ -125,11 +125,11 @@ def tf_feature_mask(Fm, Tm, band_bins=64, seg_frames=None):
 
 
 SPECTRAL_METHODS = ("saliency", "input_x_gradient", "integrated_gradients", "occlusion", "feature_ablation",
-                    "shapley_value_sampling")
+                    "shapley_value_sampling", "optimized_mask")
 
 
 def explain_spectrogram(model, waves, method="input_x_gradient", mask=None, baselines=None, n_steps=50, window=(64, 8),
-                        stride=(64, 4), band_bins=64, seg_frames=16, n_samples=25, domain="linear"):
+                        stride=(64, 4), band_bins=64, seg_frames=16, n_samples=25, domain="linear", mask_opt=None):
     """``explain_waves`` in the time-frequency domain for a batch ``[B, L]``: ``method`` (one of ``SPECTRAL_METHODS``) attributes
     the classifier to the STFT mask ``mask`` (default ``ones(B, 513, T)``: the clip itself) through ``F`` of
     ``MaskedSpectrogramLogReg(model, waves, domain)``; the explanation mask is ``|attr| / (max|attr| + 1e-8)`` per clip, and the
@@ -138,16 +138,23 @@ def explain_spectrogram(model, waves, method="input_x_gradient", mask=None, base
     features of ``tf_feature_mask(Fm, Tm, band_bins, seg_frames)``; ``baselines`` as the engine's methods take them (for
     ``"integrated_gradients"`` pass a mask baseline, not the zero mask: HipSpectralAttribution).  Three classifier passes in one
     forward; returns ``(predictions, theta_out, masked_predictions)``, each ``[B, 1]``, ready for ``compute_faithfulness``,
-    ``compute_fidelity`` and ``lmac_metrics``."""
-    from addvisor_hip import ops as _ops
+    ``compute_fidelity`` and ``lmac_metrics``.
+    ``"optimized_mask"`` attributes nothing: the explanation mask is the per-clip optimised mask itself
+    (``HipSpectralAttribution.optimize_mask(shape=(Fm, Tm), **mask_opt)``, ``mask_opt`` a dict of its keywords or None), not
+    ``|attr| / max``; the three outputs come out as for every other method."""
     if method not in SPECTRAL_METHODS:
         raise ValueError(f"method must be one of {SPECTRAL_METHODS}, not {method!r}")
     if not torch.is_tensor(waves) or waves.dim() != 2:
         raise ValueError("waves must be a [B, L] tensor")
+    if mask_opt is not None and (method != "optimized_mask" or not isinstance(mask_opt, dict) or "shape" in mask_opt):
+        raise ValueError("mask_opt is the dict of optimize_mask's keywords for method='optimized_mask' (the shape is the mask's)")
     eng = MaskedSpectrogramLogReg(model, waves, domain).hip_mask_attribution()
     B, T = eng.B, eng.T
     m = torch.ones((B, 513, T), dtype=torch.float32, device=eng.waves.device) if mask is None else mask.to(eng.waves.device, torch.float32)
     Fm, Tm = m.shape[1], m.shape[2]
+    if method == "optimized_mask":
+        rel = eng.optimize_mask(shape=(Fm, Tm), **(mask_opt or {})).mask
+        return _mask_outputs(model, eng, rel)
     if method == "saliency":
         attr = eng.saliency(m)
     elif method == "input_x_gradient":
@@ -160,10 +167,16 @@ def explain_spectrogram(model, waves, method="input_x_gradient", mask=None, base
         ids = tf_feature_mask(Fm, Tm, band_bins, seg_frames)
         attr = (eng.feature_ablation(m, baselines=baselines, feature_mask=ids) if method == "feature_ablation" else
                 eng.shapley_value_sampling(m, baselines=baselines, feature_mask=ids, n_samples=n_samples))
-    att = model.hip_attribution()
-    rel = att.time_mask(attr.reshape(B, Fm * Tm)).view(B, Fm, Tm)
+    return _mask_outputs(model, eng, model.hip_attribution().time_mask(attr.reshape(B, Fm * Tm)).view(B, Fm, Tm))
+
+
+def _mask_outputs(model, eng, rel):
+    """The three ``[B, 1]`` outputs of an explanation mask ``rel [B, Fm, Tm]``: the clip, its mask-in and its mask-out ``log1p``
+    resynthesis in one forward."""
+    from addvisor_hip import ops as _ops
+    B = eng.B
     w_rel, w_irr = _ops.istft_masked_c64(eng.spec, rel, eng.L, "log1p", hop=eng.hop, win=eng.win)
-    _, _, p = att.emb.forward(torch.cat([eng.waves, w_rel, w_irr], 0), want_hidden=False)
+    _, _, p = model.hip_attribution().emb.forward(torch.cat([eng.waves, w_rel, w_irr], 0), want_hidden=False)
     return p[:B], p[B:2 * B], p[2 * B:]
 
 
