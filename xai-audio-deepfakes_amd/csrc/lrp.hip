@@ -24,40 +24,11 @@
 #include "addvisor_hip.h"
 #include "common.h"
 #include "device_math.h"
+#include "attention_f32_tiles.h"
 
 namespace advh {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-constexpr float LRP_LOG2E = 1.4426950408889634f;
-
-#define MFMA4(acc, a4, b4)                                                        \
-    do {                                                                          \
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32((a4).x, (b4).x, acc, 0, 0, 0); \
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32((a4).y, (b4).y, acc, 0, 0, 0); \
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32((a4).z, (b4).z, acc, 0, 0, 0); \
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32((a4).w, (b4).w, acc, 0, 0, 0); \
-    } while (0)
-
-// four consecutive channels d .. d+3 of one row of a split-format / fp16 matrix (zeros past the real head dim)
-__device__ __forceinline__ float4 grow4(const _Float16* base, long lo, long row_off, int d, int dm) {
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (d < dm) load_h_rt<4>(base, row_off + d, lo, v);
-    return make_float4(v[0], v[1], v[2], v[3]);
-}
-
-// rows [0, T) x channels [0, dm) of a split-format / fp16 matrix (row stride ld) -> fp32 LDS tile [NKEY][D + 4], zero elsewhere
-template <int NKEY, int D, int NTH>
-__device__ __forceinline__ void stage_f32(float* dst, const _Float16* src, long lo, long ld, int T, int dm, int tid) {
-    constexpr int PITCH = D + 4, CH = D / 8;
-    for (int i = tid; i < NKEY * CH; i += NTH) {
-        const int row = i / CH, c = i % CH;
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (row < T && c * 8 < dm) load_h_rt<8>(src, (long)row * ld + c * 8, lo, v);
-        *(float4*)(dst + row * PITCH + c * 8) = make_float4(v[0], v[1], v[2], v[3]);
-        *(float4*)(dst + row * PITCH + c * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    }
-}
 
 template <int NT, int D>
 struct AttValue {
@@ -87,7 +58,7 @@ __global__ __launch_bounds__(256) void attention_bwd_value_kernel(const _Float16
     const _Float16* base = qkv + (long)b * T * ld + head * dm;           // q at +0, k at +H, v at +2H
     const _Float16* dob = dctx + (long)b * T * H + head * dm;
     _Float16* dbase = dqkv + (long)b * T * ld + head * dm;
-    const float c2 = scale * LRP_LOG2E;
+    const float c2 = scale * LOG2E;
 
     // dQ = dK = 0: this head's columns of the Q and K thirds, every row of the clip, both planes
     {
