@@ -38,6 +38,46 @@ class PosconvDesc(ctypes.Structure):
                 ("G", ctypes.c_int), ("K", ctypes.c_int)]
 
 
+def plan_posconv(B: int, T: int, H: int, Gp: int, K: int, weight, bias: Optional[torch.Tensor] = None, *, flip: bool = False,
+                 device=None, cache: Optional[tuple] = None, split: bool = False) -> G.GemmPlan:
+    """The positional convolution as one implicit GEMM batched over the ``Gp`` groups, on the operand ``advh_posconv_gather``
+    lays out (``[Gp][B][T + K][Cg]``): row (b, t) reads the K gathered rows from t on and writes columns ``g * Cg ..`` of row
+    (b, t) of a ``[B * T, H]`` buffer.  ``weight``: the folded ``Conv1d`` weight ``[H, Cg, K]`` or a zero-argument callable
+    returning it (only called when the packed weight is not in ``cache``).  Forward: ``[g][co][(k, ci)]``, bias, GELU.
+    ``flip``: the gradient w.r.t. the input, ``[g][ci][(k', co)]`` with the taps reversed, no bias, no activation (the operand
+    is then gathered at ``pad_left = K / 2 - 1``)."""
+    Cg = H // Gp
+    cc = Cg // 8
+    assert not flip or bias is None
+
+    def w2():
+        w = (weight() if callable(weight) else weight).reshape(Gp, Cg, Cg, K)
+        if flip:
+            return w.flip(3).permute(0, 2, 3, 1).reshape(Gp, Cg, K * Cg)
+        return w.permute(0, 1, 3, 2).reshape(Gp, Cg, K * Cg)
+    return G.GemmPlan(M=B * T, N=Cg, w2=w2, ktab=np.arange(K * cc, dtype=np.int64),
+                      sources=[G.Source((T + K) * cc, 0, cc, 0, sZ=B * (T + K) * cc)], Hg=1, Wg=T,
+                      window=(0, 1, 0, T), halo_zero=False, out=(T * H, 0, H, 0), n_div=G.round_up(Cg, 4),
+                      o_sZ=Cg, nz=Gp, bias=bias, bias_sZ=0 if bias is None else Cg, act="none" if flip else "gelu",
+                      device=device, cache=cache, split=split)
+
+
+def pack_posconv_tile(weight: torch.Tensor, Gp: int) -> torch.Tensor:
+    """The folded ``Conv1d`` weight ``[H, Cg, K]`` as the line tile streams it (csrc/posconv_tile.hip): fp16
+    ``[g][k-step][n][32]``, K order (tap, channel), 32 K values per step."""
+    H, Cg, K = weight.shape
+    assert H == Gp * Cg
+    return weight.reshape(Gp, Cg, Cg, K).permute(0, 1, 3, 2).reshape(Gp, Cg, K * Cg // 32, 32) \
+        .permute(0, 2, 1, 3).contiguous().to(torch.float16)
+
+
+def posconv_tile_selected(Cg: int, T: int, B: int, K: int, split: bool) -> bool:
+    """Does the forward run the line tile (csrc/posconv_tile.hip) for this shape?  fp16 mode only, 48 or 64 channels per group,
+    T <= 256, K = 128; 64-channel groups leave room for one workgroup per CU only (measured 308 vs 369 us at 64 clips but
+    925 vs 876 us at 192 -- tools/bench_posconv.py), so large models switch back to the GEMM for big batches."""
+    return bool(POSCONV_TILE and not split and _lib.lib().advh_posconv_tile_lds_bytes(Cg, T) > 0 and K == 128 and (Cg <= 48 or B <= 96))
+
+
 def _f32(t, dev):
     return t.detach().to(torch.float32).contiguous().to(dev)
 
@@ -187,23 +227,16 @@ class HipEmbedder:
         # positional conv: weight_norm folded (modeling_wav2vec2.py:326-357), one GEMM batched over groups
         g0 = sd["encoder.pos_conv_embed.conv.parametrizations.weight.original0"]
         v0 = sd["encoder.pos_conv_embed.conv.parametrizations.weight.original1"]
-        w2 = lambda: (g0 * v0 / v0.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()).view(Gp, Cg, Cg, K) \
-            .permute(0, 1, 3, 2).reshape(Gp, Cg, K * Cg)                            # [g][n][(k, ci)]
-        cc = Cg // 8
-        ws["pos"] = G.GemmPlan(M=M, N=Cg, w2=w2, ktab=np.arange(K * cc, dtype=np.int64),
-                               sources=[G.Source((T + K) * cc, 0, cc, 0, sZ=B * (T + K) * cc)], Hg=1, Wg=T,
-                               window=(0, 1, 0, T), halo_zero=False, out=(T * H, 0, H, 0), n_div=G.round_up(Cg, 4),
-                               o_sZ=Cg, nz=Gp, bias=sd["encoder.pos_conv_embed.conv.bias"], bias_sZ=Cg, act="gelu",
-                               device=dev, cache=(self._wcache, "pos"), split=sp)
+        wconv = lambda: g0 * v0 / v0.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()          # [H][Cg][K]
+        ws["pos"] = plan_posconv(B, T, H, Gp, K, wconv, sd["encoder.pos_conv_embed.conv.bias"], device=dev,
+                                 cache=(self._wcache, "pos"), split=sp)
         # line-tile launch for the same layer (csrc/posconv_tile.hip): the clip's gathered rows staged in LDS once, the
         # group's weights streamed; the implicit GEMM above stays as the fallback for other geometries
         ws["pos_tile"] = None
-        # (64-channel groups leave room for one workgroup per CU only: measured 308 vs 369 us at 64 clips but 925 vs 876 us
-        # at 192 -- tools/bench_posconv.py -- so large models switch back to the GEMM for big batches)
-        if POSCONV_TILE and not sp and _lib.lib().advh_posconv_tile_lds_bytes(Cg, T) > 0 and K == 128 and (Cg <= 48 or B <= 96):
+        if posconv_tile_selected(Cg, T, B, K, sp):
             if "pos_tile" not in self._wcache:
-                wt = w2().view(Gp, Cg, K * Cg // 32, 32).permute(0, 2, 1, 3).contiguous().to(torch.float16)   # [g][k-step][n][32]
-                self._wcache["pos_tile"] = (wt.to(dev), sd["encoder.pos_conv_embed.conv.bias"].float().contiguous().to(dev))
+                self._wcache["pos_tile"] = (pack_posconv_tile(wconv(), Gp).to(dev),
+                                            sd["encoder.pos_conv_embed.conv.bias"].float().contiguous().to(dev))
             d = PosconvDesc()
             d.B, d.T, d.H, d.G, d.K = B, T, H, Gp, K
             d.W, d.bias = self._wcache["pos_tile"][0].data_ptr(), self._wcache["pos_tile"][1].data_ptr()

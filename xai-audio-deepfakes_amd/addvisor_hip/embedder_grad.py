@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib, gemm as G
-from .embedder import FE_SLACK_ROWS, HipEmbedder
+from .embedder import FE_SLACK_ROWS, HipEmbedder, plan_posconv
 
 
 def plan_conv1d_dgrad(B: int, P_out: int, weight: torch.Tensor, stride: int, device=None, cache=None, split: bool = False) -> G.GemmPlan:
@@ -190,15 +190,10 @@ class EmbedderGrad:
         w["layers"] = layers
         w["proj"] = lin(sd["feature_projection.projection.weight"].t(), "proj")
         K, Gp = cfg.num_conv_pos_embeddings, cfg.num_conv_pos_embedding_groups
-        Cg, cc = H // Gp, H // Gp // 8
         g0 = sd["encoder.pos_conv_embed.conv.parametrizations.weight.original0"]
         v0 = sd["encoder.pos_conv_embed.conv.parametrizations.weight.original1"]
-        w2b = lambda: (g0 * v0 / v0.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()).view(Gp, Cg, Cg, K) \
-            .flip(3).permute(0, 2, 3, 1).reshape(Gp, Cg, K * Cg)                   # [g][ci][(k', co)], taps flipped
-        w["pos"] = G.GemmPlan(M=M, N=Cg, w2=w2b, ktab=np.arange(K * cc, dtype=np.int64),
-                              sources=[G.Source((T + K) * cc, 0, cc, 0, sZ=B * (T + K) * cc)], Hg=1, Wg=T,
-                              window=(0, 1, 0, T), halo_zero=False, out=(T * H, 0, H, 0), n_div=G.round_up(Cg, 4),
-                              o_sZ=Cg, nz=Gp, device=dev, cache=(wc, "pos"), split=sp)
+        wconv = lambda: g0 * v0 / v0.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
+        w["pos"] = plan_posconv(B, T, H, Gp, K, wconv, flip=True, device=dev, cache=(wc, "pos"), split=sp)   # [g][ci][(k', co)], taps flipped
         fe = []
         for i in range(1, nfe):
             plan, nt = plan_conv1d_dgrad(B, P[i], sd[f"feature_extractor.conv_layers.{i}.conv.weight"], cfg.conv_stride[i], dev,
