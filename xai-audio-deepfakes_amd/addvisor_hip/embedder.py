@@ -168,12 +168,22 @@ class HipEmbedder:
             out.append(n)
         return out
 
+    def min_length(self) -> int:
+        """The shortest clip with one frame: the receptive field of the feature encoder (400 samples for wav2vec2)."""
+        n = 1
+        for k, s in zip(reversed(self.cfg.conv_kernel), reversed(self.cfg.conv_stride)):
+            n = (n - 1) * s + k
+        return n
+
     def _workspace(self, B: int, L: int, slot: int = 0) -> dict:
         key = (B, L, slot)
         if key in self._ws:
             return self._ws[key]
         cfg, dev, sd = self.cfg, self.dev, self.sd
         Ls = self._lengths(L)
+        if min(Ls) < 1:                              # no frame: refused before any allocation, plan or launch
+            raise ValueError(f"a clip of {L} samples is shorter than the feature encoder's receptive field: the shortest "
+                             f"supported length is {self.min_length()} samples")
         nfe = len(Ls)
         strides = cfg.conv_stride
         # padded row counts: P[i] = P[i+1] * stride[i+1], every P[i] >= L[i]
