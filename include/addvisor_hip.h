@@ -1313,6 +1313,50 @@ int advh_mask_opt_terms(const advh_mask_opt_desc* d, const float* theta, const i
 int advh_mask_opt_step(const advh_mask_opt_desc* d, float* theta, const float* p, const int32_t* rank, const float* G, int b0, int nb,
                        double bias1, double bias2, float* m1, float* m2, float* grad_theta, advh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ragged batches: per-clip lengths in the embedder forward.  A batch wave [B][L] carries lens[b] valid samples in clip b; the
+ * result for clip b is what the model gives for wave[b, :lens[b]] run ALONE, unpadded.  This is the attention_mask semantics
+ * of HF Wav2Vec2Model for layer-norm feature encoders (transformers/models/wav2vec2/modeling_wav2vec2.py): the valid frame
+ * count per clip is _get_feat_extract_output_lengths / _get_feature_vector_attention_mask; Wav2Vec2Encoder(.StableLayerNorm)
+ * .forward sets hidden_states[~expand_attention_mask] = 0 after the projection and adds -inf to the scores of padded keys
+ * (the additive attention_mask [B, 1, T, T]).  For group-norm feature encoders HF lets the padding into GroupNorm's
+ * statistics; here the statistics run over the clip's own frames in both modes (the per-clip-alone definition).
+ *
+ * All lengths are int32 [B] DEVICE arrays: `lens` in samples, `frames` in encoder frames (the feature encoder's output-length
+ * formula applied to lens[b]).  Every kernel clamps what it reads from them into the batch's own range, so no array content
+ * can move an access out of bounds; the host is expected to pass lens[b] in [receptive field, L] and frames[b] in [1, T].
+ * The feature-encoder convolutions need no change: they have no padding, so valid frame t of a layer reads valid rows only.
+ * Every entry point returns ADVH_EINVAL before any HIP call for a NULL pointer (optional pointers of the sibling excepted),
+ * NULL lens / frames, B, T or H <= 0, H % heads != 0 or a bad plane distance, and ADVH_EUNSUPPORTED where its sibling does.
+ *
+ * advh_w2v2_frontend_ragged / _split_ragged: advh_w2v2_frontend / _split (same arguments, same checks) plus lens.  Per clip the
+ *   mean and 1 / (std + 1e-7) run over lens[b] samples (clamped to [10, L]); samples >= lens[b] are never read for their value
+ *   (a NaN there does not matter); mode 0: the GroupNorm statistics run over T0_b = (lens[b] - 10) / 5 + 1 frames; rows
+ *   t >= T0_b of out are written as zeros, as rows [T0, P0) are in the batch form.  stats_ws / norm_ws / mr_ws hold the
+ *   per-clip figures.  lens[b] = L for every b gives the batch form's output bit for bit (n_in >= L).
+ * advh_attention_f16_ragged / advh_attention_split_ragged: advh_attention_f16 / _split (same layouts, limits, kernel classes by
+ *   the row stride T, error codes) with the keys, queries and tile loops of clip b bounded by Tv = clamp(frames[b], 1, T): rows
+ *   t < Tv of ctx are the sibling's result for the clip's first Tv rows alone, rows Tv <= t < T are written as zeros (both
+ *   planes); rows >= Tv of qkv are never read for their value.  frames[b] = T gives the sibling's output bit for bit.
+ * advh_zero_tail_rows: x [B][T][H] fp32, x[b, frames[b]:, :] = 0 (frames[b] clamped to [0, T]); 16-byte stores where x is
+ *   16-byte aligned and H % 4 == 0.  B <= 65535 (ADVH_EUNSUPPORTED above).
+ * advh_pool_logreg_ragged: advh_pool_logreg over frames t < frames[b] (clamped to [1, T]), added in the sibling's order and
+ *   divided by that count; clips stay T rows apart.                                                                      */
+int advh_w2v2_frontend_ragged(const float* wave, int64_t wave_stride, int n_in, int B, int L, const float* w0,
+                              const float* bias0, const float* gamma, const float* beta, int mode, int normalize, float* stats_ws,
+                              float* norm_ws, float* mr_ws, void* out, int T0, int P0, int C0, const int32_t* lens,
+                              advh_stream_t stream);
+int advh_w2v2_frontend_split_ragged(const float* wave, int64_t wave_stride, int n_in, int B, int L, const float* w0,
+                                    const float* bias0, const float* gamma, const float* beta, int mode, int normalize,
+                                    float* stats_ws, float* norm_ws, float* mr_ws, void* out, int64_t out_lo, int T0, int P0, int C0,
+                                    const int32_t* lens, advh_stream_t stream);
+int advh_attention_f16_ragged(const void* qkv, void* ctx, const int32_t* frames, int B, int T, int H, int heads, advh_stream_t stream);
+int advh_attention_split_ragged(const void* qkv, int64_t qkv_lo, void* ctx, int64_t ctx_lo, const int32_t* frames, int B, int T, int H,
+                                int heads, advh_stream_t stream);
+int advh_zero_tail_rows(float* x, const int32_t* frames, int B, int T, int H, advh_stream_t stream);
+int advh_pool_logreg_ragged(const float* h, const float* coef, float intercept, float* logit, float* prob, float* pooled,
+                            const int32_t* frames, int B, int T, int H, advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

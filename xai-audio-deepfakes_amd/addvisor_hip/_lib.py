@@ -195,6 +195,12 @@ SIGNATURES = {
     "advh_mask_opt_rows": (_i, [_p, _p, _i, _i, _p, _p]),
     "advh_mask_opt_terms": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "advh_mask_opt_step": (_i, [_p, _p, _p, _p, _p, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p]),
+    "advh_w2v2_frontend_ragged": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "advh_w2v2_frontend_split_ragged": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i64, _i, _i, _i, _p, _p]),
+    "advh_attention_f16_ragged": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "advh_attention_split_ragged": (_i, [_p, _i64, _p, _i64, _p, _i, _i, _i, _i, _p]),
+    "advh_zero_tail_rows": (_i, [_p, _p, _i, _i, _i, _p]),
+    "advh_pool_logreg_ragged": (_i, [_p, _p, _f, _p, _p, _p, _p, _i, _i, _i, _p]),
 }
 
 _lib = None

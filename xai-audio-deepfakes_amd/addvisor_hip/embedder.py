@@ -175,6 +175,42 @@ class HipEmbedder:
             n = (n - 1) * s + k
         return n
 
+    def frame_lengths(self, lengths) -> List[int]:
+        """Valid encoder frames of clips with ``lengths`` samples (HF ``_get_feat_extract_output_lengths``)."""
+        return [self._lengths(int(n))[-1] for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+
+    def _check_lengths(self, lengths, B: int, L: int) -> List[int]:
+        """``lengths`` of a ragged batch ``[B, L]`` as a list of ints; ``ValueError`` for anything else.  Host only: called
+        before any allocation, plan or launch."""
+        if torch.is_tensor(lengths):
+            if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+                raise ValueError("lengths must be a sequence or a 1-D integer tensor with one entry per clip")
+            lengths = lengths.tolist()
+        elif isinstance(lengths, np.ndarray):
+            if lengths.ndim != 1 or not np.issubdtype(lengths.dtype, np.integer):
+                raise ValueError("lengths must be a sequence or a 1-D integer tensor with one entry per clip")
+            lengths = lengths.tolist()
+        else:
+            try:
+                lengths = list(lengths)
+            except TypeError:
+                raise ValueError("lengths must be a sequence or a 1-D integer tensor with one entry per clip") from None
+        if len(lengths) != B:
+            raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} clips")
+        lo = self.min_length()
+        out = []
+        for b, n in enumerate(lengths):
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+                raise ValueError(f"lengths[{b}] = {n!r} is not an integer sample count")
+            n = int(n)
+            if n > L:
+                raise ValueError(f"lengths[{b}] = {n} exceeds the batch's {L} samples")
+            if n < lo:
+                raise ValueError(f"clip {b} has {n} samples, shorter than the feature encoder's receptive field: the shortest "
+                                 f"supported length is {lo} samples")
+            out.append(n)
+        return out
+
     def _workspace(self, B: int, L: int, slot: int = 0) -> dict:
         key = (B, L, slot)
         if key in self._ws:
@@ -289,12 +325,24 @@ class HipEmbedder:
 
     # ------------------------------------------------------------------ forward
     def forward(self, wave: torch.Tensor, length: Optional[int] = None, want_hidden: bool = True,
-                normalize: bool = True, slot: int = 0):
-        """Returns ``(hidden [B,T,H] fp32 or None, logits [B,1], probs [B,1])`` -- fresh tensors."""
+                normalize: bool = True, slot: int = 0, lengths=None):
+        """Returns ``(hidden [B,T,H] fp32 or None, logits [B,1], probs [B,1])`` -- fresh tensors.
+
+        ``lengths`` (a sequence or 1-D integer tensor of ``B`` sample counts): a ragged batch.  Clip ``b`` is
+        ``wave[b, :lengths[b]]``; what lies behind is padding of any content.  Its result is what the model gives for that clip
+        run alone, unpadded: ``hidden[b, :T_b]`` with ``T_b = frame_lengths(lengths)[b]``, ``hidden[b, T_b:] = 0``, and
+        logits / probs pooled over the ``T_b`` valid frames (HF's ``attention_mask`` semantics for layer-norm feature encoders;
+        for group-norm ones the GroupNorm statistics run over the clip's own frames, which HF does not do).  Workspace and plans
+        are those of the padded ``(B, L)`` call."""
         if wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
             raise ValueError("wave must be a CUDA fp32 tensor [B, n]")
-        wave = wave.contiguous()
         B, n_in = wave.shape
+        rag = None
+        if lengths is not None:
+            if length is not None:
+                raise ValueError("give length= (one length for the batch) or lengths= (one per clip), not both")
+            lens = self._check_lengths(lengths, B, n_in)
+        wave = wave.contiguous()
         L = n_in if length is None else int(length)
         cfg, lib = self.cfg, _lib.lib()
         ws = self._workspace(B, L, slot)           # `slot` gives concurrent streams their own buffers
@@ -306,7 +354,23 @@ class HipEmbedder:
         mode = 1 if self.layer_mode else 0
         ln0 = self.fe_ln[0]
         sp = self.split
-        if sp:
+        if lengths is not None:
+            # sample and frame counts in one small copy: rag[0] = lens, rag[1] = frames
+            rag = torch.tensor([lens, self.frame_lengths(lens)], dtype=torch.int32).to(self.dev, non_blocking=False)
+            lens_p, frames_p = rag[0].data_ptr(), rag[1].data_ptr()
+            if sp:
+                _lib.check(lib.advh_w2v2_frontend_split_ragged(
+                    wave.data_ptr(), wave.stride(0), n_in, B, L, self.w0.data_ptr(),
+                    None if self.b0 is None else self.b0.data_ptr(), ln0.g.data_ptr(), ln0.b.data_ptr(), mode, int(normalize),
+                    ws["stats"].data_ptr(), ws["norm"].data_ptr(), ws["mr"].data_ptr(), a.data_ptr(), a.stride(0), Ls[0], P[0], C[0],
+                    lens_p, st), "advh_w2v2_frontend_split_ragged")
+            else:
+                _lib.check(lib.advh_w2v2_frontend_ragged(
+                    wave.data_ptr(), wave.stride(0), n_in, B, L, self.w0.data_ptr(),
+                    None if self.b0 is None else self.b0.data_ptr(), ln0.g.data_ptr(), ln0.b.data_ptr(), mode, int(normalize),
+                    ws["stats"].data_ptr(), ws["norm"].data_ptr(), ws["mr"].data_ptr(), a.data_ptr(), Ls[0], P[0], C[0], lens_p, st),
+                    "advh_w2v2_frontend_ragged")
+        elif sp:
             _lib.check(lib.advh_w2v2_frontend_split(
                 wave.data_ptr(), wave.stride(0), n_in, B, L, self.w0.data_ptr(),
                 None if self.b0 is None else self.b0.data_ptr(), ln0.g.data_ptr(), ln0.b.data_ptr(), mode, int(normalize),
@@ -332,6 +396,8 @@ class HipEmbedder:
         h, h16 = ws["h"], ws["h16"]
         self.fp_ln(ws["feat"], M, eps, out_h=ws["featn"], split=sp)
         ws["proj"].run(ws["featn"], out_f=h)
+        if rag is not None:                                           # hidden_states[~mask] = 0: the positional conv's zero padding
+            _lib.check(lib.advh_zero_tail_rows(h.data_ptr(), frames_p, B, T, H, st), "advh_zero_tail_rows")
         K, Gp = cfg.num_conv_pos_embeddings, cfg.num_conv_pos_embedding_groups
         if sp:
             _lib.check(lib.advh_posconv_gather_split(h.data_ptr(), ws["xg"].data_ptr(), ws["xg"].stride(0), B, T, H, Gp, K, K // 2, st),
@@ -352,7 +418,14 @@ class HipEmbedder:
             if stable:
                 self.ln1[l](h, M, eps, out_h=h16, split=sp)
             lay["qkv"].run(h16, out_h=ws["qkv"])
-            if sp:
+            if rag is not None and sp:
+                _lib.check(lib.advh_attention_split_ragged(ws["qkv"].data_ptr(), ws["qkv"].stride(0), ws["ctx"].data_ptr(),
+                                                           ws["ctx"].stride(0), frames_p, B, T, H, cfg.num_attention_heads, st),
+                           "advh_attention_split_ragged")
+            elif rag is not None:
+                _lib.check(lib.advh_attention_f16_ragged(ws["qkv"].data_ptr(), ws["ctx"].data_ptr(), frames_p, B, T, H,
+                                                         cfg.num_attention_heads, st), "advh_attention_f16_ragged")
+            elif sp:
                 _lib.check(lib.advh_attention_split(ws["qkv"].data_ptr(), ws["qkv"].stride(0), ws["ctx"].data_ptr(), ws["ctx"].stride(0),
                                                     B, T, H, cfg.num_attention_heads, st), "advh_attention_split")
             else:
@@ -378,6 +451,13 @@ class HipEmbedder:
                 self.ln2[l](h, M, eps, out_f=h, out_h=h16, split=sp)
         if stable and self.nl == cfg.num_hidden_layers:
             self.enc_ln(h, M, eps, out_f=h)
+        if rag is not None:
+            _lib.check(lib.advh_pool_logreg_ragged(h.data_ptr(), self.coef.data_ptr(), self.intercept, ws["logit"].data_ptr(),
+                                                   ws["prob"].data_ptr(), None, frames_p, B, T, H, st), "advh_pool_logreg_ragged")
+            hid = h.view(B, T, H).clone() if want_hidden else None
+            if hid is not None:
+                _lib.check(lib.advh_zero_tail_rows(hid.data_ptr(), frames_p, B, T, H, st), "advh_zero_tail_rows")
+            return hid, ws["logit"].clone().view(B, 1), ws["prob"].clone().view(B, 1)
         _lib.check(lib.advh_pool_logreg(h.data_ptr(), self.coef.data_ptr(), self.intercept, ws["logit"].data_ptr(),
                                         ws["prob"].data_ptr(), None, B, T, H, st), "advh_pool_logreg")
         hid = h.view(B, T, H).clone() if want_hidden else None

@@ -28,6 +28,19 @@ def _read_wav(path):
     return read_wav(path)
 
 
+def pad_clips(clips):
+    """Clips of different lengths (1-D tensors) as one ragged batch: ``(waves [B, Lmax] zero-padded on the right, lengths)``
+    for ``AudioProcessor.extract_features(waves, lengths)`` / ``classify(waves, lengths)``."""
+    clips = list(clips)
+    if not clips or any(c.dim() != 1 or c.numel() == 0 for c in clips):
+        raise ValueError("pad_clips takes a non-empty list of non-empty 1-D tensors")
+    lengths = [int(c.numel()) for c in clips]
+    waves = torch.zeros(len(clips), max(lengths), dtype=torch.float32, device=clips[0].device)
+    for b, c in enumerate(clips):
+        waves[b, :lengths[b]] = c.to(waves.device, torch.float32)
+    return waves, lengths
+
+
 class AudioProcessor:
     def __init__(self, sampling_rate=16000, n_fft=1024, hop_length=322, win_length=644, n_mels=80, audio_length=5):
         if n_fft != 1024:
@@ -57,18 +70,21 @@ class AudioProcessor:
         return audio, target_sr
 
     # audioprocessor.py:69-77
-    def extract_features(self, waveforms):
+    def extract_features(self, waveforms, lengths=None):
+        """``lengths``: per-clip sample counts of a ragged batch (``pad_clips``); clip ``b``'s rows are those of the clip run
+        alone, rows past its ``HipEmbedder.frame_lengths`` frames are zero."""
         if waveforms.dim() == 1:
             waveforms = waveforms[None]
         x = waveforms.to(device, torch.float32)
-        hid, _, _ = _rt.hip_embedder().forward(x)          # normaliser + wav2vec2 -> hidden_states[9]
+        hid, _, _ = _rt.hip_embedder().forward(x, lengths=lengths)          # normaliser + wav2vec2 -> hidden_states[9]
         return hid.squeeze(0)
 
-    def classify(self, waveforms):
-        """Pool + logreg head fused behind the embedder (LMAC_metrics.py:130): ``(logits, probs) [B,1]``."""
+    def classify(self, waveforms, lengths=None):
+        """Pool + logreg head fused behind the embedder (LMAC_metrics.py:130): ``(logits, probs) [B,1]``.  ``lengths``:
+        per-clip sample counts of a ragged batch; each clip pools over its own valid frames."""
         if waveforms.dim() == 1:
             waveforms = waveforms[None]
-        _, logits, probs = _rt.hip_embedder().forward(waveforms.to(device, torch.float32), want_hidden=False)
+        _, logits, probs = _rt.hip_embedder().forward(waveforms.to(device, torch.float32), want_hidden=False, lengths=lengths)
         return logits, probs
 
     # audioprocessor.py:82-112

@@ -47,8 +47,9 @@ class Wav2vec2LogReg(nn.Module):
         self._att = None
         self._rob = None
 
-    def forward(self, waveform):
-        logits, _ = self.ap.classify(waveform)
+    def forward(self, waveform, lengths=None):
+        """``lengths``: per-clip sample counts of a ragged batch (forward only: the attribution methods take none)."""
+        logits, _ = self.ap.classify(waveform) if lengths is None else self.ap.classify(waveform, lengths=lengths)
         return logits
 
     def num_layers(self):

@@ -23,32 +23,57 @@ processor = None                            # the HF feature extractor is never 
 class _HiddenStates:
     """``output.hidden_states``: index k runs the first k encoder layers on the GPU."""
 
-    def __init__(self, x):
+    def __init__(self, x, lengths=None):
         self._x = x
+        self._lengths = lengths
 
     def __getitem__(self, k):
         emb = _rt.hip_embedder()
         if k != emb.cfg.layer_index:
             raise IndexError(f"this embedder is built for hidden_states[{emb.cfg.layer_index}] "
                              "(set ADDVISOR_LAYER_INDEX to change it)")
-        hid, _, _ = emb.forward(self._x, normalize=False)
+        hid, _, _ = emb.forward(self._x, normalize=False, lengths=self._lengths)
         return hid
 
 
 class _Output:
-    def __init__(self, x):
-        self.hidden_states = _HiddenStates(x)
+    def __init__(self, x, lengths=None):
+        self.hidden_states = _HiddenStates(x, lengths)
+
+
+def mask_lengths(attention_mask, shape):
+    """Per-clip lengths of a 0/1 right-padded ``attention_mask`` of ``shape`` ``[B, L]``; a mask of another shape, with other
+    values or with holes (a 1 behind a 0) raises ``ValueError``."""
+    m = torch.as_tensor(attention_mask)
+    if m.dim() == 1:
+        m = m[None]
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError(f"attention_mask has shape {tuple(m.shape)}, input_values {tuple(shape)}")
+    m = m.cpu()
+    if not bool(((m == 0) | (m == 1)).all()):
+        raise ValueError("attention_mask must hold 0 and 1 only")
+    m = m.to(torch.int64)
+    lengths = m.sum(-1)
+    if not torch.equal(m, (torch.arange(m.shape[1])[None] < lengths[:, None]).to(torch.int64)):
+        raise ValueError("attention_mask must be right-padded: ones up to each clip's length, zeros behind (a mask with holes "
+                         "is not supported)")
+    return lengths.tolist()
 
 
 class _Wav2Vec2:
     """``wav2vec2(input_values, output_hidden_states=True).hidden_states[9]`` (audioprocessor.py:76-77).
-    ``input_values`` is the already normalised waveform, as in the reference."""
+    ``input_values`` is the already normalised waveform, as in the reference.  ``attention_mask`` (HF's argument: 0/1,
+    right-padded) makes the batch ragged: clip ``b`` is its first ``mask[b].sum()`` samples, expected normalised over that valid
+    part as HF's feature extractor delivers it; samples behind read as 0 and rows past the clip's frames come back as zeros.
+    For group-norm feature encoders the result is that of the clip run alone, which HF's masked call is not (HF lets the padding
+    into GroupNorm's statistics)."""
 
-    def __call__(self, input_values, output_hidden_states=True):
+    def __call__(self, input_values, attention_mask=None, output_hidden_states=True):
         x = input_values
         if x.dim() == 1:
             x = x[None]
-        return _Output(x.to(_rt.device(), torch.float32).contiguous())
+        lengths = None if attention_mask is None else mask_lengths(attention_mask, x.shape)
+        return _Output(x.to(_rt.device(), torch.float32).contiguous(), lengths)
 
     def to(self, *a, **k):
         return self

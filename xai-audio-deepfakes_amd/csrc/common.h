@@ -6,8 +6,10 @@
 // Per-module one-time initialisation (dynamic-LDS attributes); defined in gemm.hip.
 int advh_init_rest();
 int advh_init_attention();   // attention.hip
+int advh_init_attention_ragged();   // attention_ragged.hip
 // per-translation-unit setters of the split-format range flag pointer (csrc/device_math.h: ADVH_SPLIT_FLAG_SETTER)
 int advh_split_flag_attention(int* flag);
+int advh_split_flag_attention_ragged(int* flag);
 int advh_split_flag_attention_bwd_f32(int* flag);
 int advh_split_flag_attribution_layer(int* flag);
 int advh_split_flag_attribution_neuron(int* flag);
@@ -15,6 +17,7 @@ int advh_split_flag_attention_bwd_x3(int* flag);
 int advh_split_flag_backward(int* flag);
 int advh_split_flag_conv_taps(int* flag);
 int advh_split_flag_frontend(int* flag);
+int advh_split_flag_frontend_ragged(int* flag);
 int advh_split_flag_frontend_bwd(int* flag);
 int advh_split_flag_gemm(int* flag);
 int advh_split_flag_hifigan(int* flag);
