@@ -1357,6 +1357,49 @@ int advh_zero_tail_rows(float* x, const int32_t* frames, int B, int T, int H, ad
 int advh_pool_logreg_ragged(const float* h, const float* coef, float intercept, float* logit, float* prob, float* pooled,
                             const int32_t* frames, int B, int T, int H, advh_stream_t stream);
 
+/* ---- ragged batches: the gradient chain (csrc/attention_bwd_ragged.hip, backward_ragged.hip) -----------------------------
+ * The backward of the ragged forward above, same definition: what the chain returns for clip b is what the batch form returns
+ * for wave[b, :lens[b]] run alone.  `lens` / `frames` are the int32 [B] device arrays of the forward, clamped in every kernel.
+ * The row-wise launches of the chain (dgrad GEMMs without bias, LayerNorm backward, the feature encoder's dgrad) need no ragged
+ * form: a padded row whose incoming gradient is exactly 0, with finite saves, stays exactly 0.  Every entry point returns
+ * ADVH_EINVAL before any HIP call for a NULL pointer (optional pointers of the sibling excepted), NULL lens / frames, a
+ * non-positive or inconsistent size or a bad plane distance, and ADVH_EUNSUPPORTED where its sibling does.
+ *
+ * advh_attention_bwd_f16_ragged / advh_attention_bwd_split_ragged: advh_attention_bwd_f16 / _split (same layouts, limits, kernel
+ *   instance by the row stride T, refusals, and the split entry honours the attention_bwd_mfma_f32 option) with every bound of
+ *   clip b taken from Tv = clamp(frames[b], 1, T): rows t < Tv of dqkv are the sibling's result for the clip's first Tv rows of
+ *   qkv / dctx alone, rows Tv <= t < T are written as zeros (every plane), rows >= Tv of qkv / dctx are never read for their
+ *   value.  frames[b] = T gives the sibling's output bit for bit.
+ * advh_pool_logreg_bwd_ragged / _split_ragged: advh_pool_logreg_bwd / _split with dh[b, t, :] = coef * (dlogit[b] / Tv) for
+ *   t < Tv and zeros for Tv <= t < T, in dh and in dh16 (both planes).
+ * advh_zero_tail_rows_h: advh_zero_tail_rows for fp16 rows x [B][T][H] (lo = 0) or a plane pair (lo > 0: the lo plane lies lo
+ *   elements behind); 16-byte stores where x is 16-byte aligned, H % 8 == 0 and lo % 8 == 0.  B <= 65535.
+ * advh_w2v2_frontend_bwd_group_ragged / _split_ragged: advh_w2v2_frontend_bwd_group / _split plus lens: the sums, their divisor
+ *   and the bound above which dz0 is written as zero (up to P0) are the clip's own T0_b = (lens[b] - 10) / 5 + 1; samples
+ *   >= lens[b] and rows >= T0_b of dy0 are never read for their value.  Same 64-frame tiles and partial order.
+ * advh_wave_bwd_ragged: advh_wave_bwd plus lens: the gather, S1 / L_b, (L_b - 1) sigma and T0_b per clip with L_b = lens[b]
+ *   (clamped to [10, L]); dx[b, u] = 0 for L_b <= u < n_in.  T0 must be (L - 10) / 5 + 1.  Same 2048-sample tiles.           */
+int advh_attention_bwd_f16_ragged(const void* qkv, const void* dctx, void* dqkv, const int32_t* frames, int B, int T, int H, int heads,
+                                  advh_stream_t stream);
+int advh_attention_bwd_split_ragged(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, void* dqkv, int64_t dqkv_lo,
+                                    const int32_t* frames, int B, int T, int H, int heads, advh_stream_t stream);
+int advh_pool_logreg_bwd_ragged(const float* coef, const float* dlogit, float* dh, void* dh16, const int32_t* frames, int B, int T,
+                                int H, advh_stream_t stream);
+int advh_pool_logreg_bwd_split_ragged(const float* coef, const float* dlogit, float* dh, void* dh16, int64_t dh16_lo,
+                                      const int32_t* frames, int B, int T, int H, advh_stream_t stream);
+int advh_zero_tail_rows_h(void* x, int64_t lo, const int32_t* frames, int B, int T, int H, advh_stream_t stream);
+int advh_w2v2_frontend_bwd_group_ragged(const float* wave, int64_t wave_stride, int n_in, int B, int L, const float* w0,
+                                        const float* gamma, const float* stats_ws, const float* norm_ws, const float* mr_ws,
+                                        const void* dy0, float* part_ws, float* sums_ws, void* dz0, int T0, int P0, int C0,
+                                        const int32_t* lens, advh_stream_t stream);
+int advh_w2v2_frontend_bwd_group_split_ragged(const float* wave, int64_t wave_stride, int n_in, int B, int L, const float* w0,
+                                              const float* gamma, const float* stats_ws, const float* norm_ws, const float* mr_ws,
+                                              const void* dy0, int64_t dy_lo, float* part_ws, float* sums_ws, void* dz0, int64_t dz_lo,
+                                              int T0, int P0, int C0, const int32_t* lens, advh_stream_t stream);
+int advh_wave_bwd_ragged(const float* g, const float* wave, int64_t wave_stride, int n_in, int B, int L, const float* stats_ws,
+                         float* dxhat_ws, float* part_ws, int normalize, float out_scale, float* dx, int64_t dx_stride, int T0, int P0,
+                         const int32_t* lens, advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

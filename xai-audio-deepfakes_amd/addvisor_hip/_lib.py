@@ -201,6 +201,14 @@ SIGNATURES = {
     "advh_attention_split_ragged": (_i, [_p, _i64, _p, _i64, _p, _i, _i, _i, _i, _p]),
     "advh_zero_tail_rows": (_i, [_p, _p, _i, _i, _i, _p]),
     "advh_pool_logreg_ragged": (_i, [_p, _p, _f, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "advh_attention_bwd_f16_ragged": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "advh_attention_bwd_split_ragged": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _i, _i, _i, _i, _p]),
+    "advh_pool_logreg_bwd_ragged": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "advh_pool_logreg_bwd_split_ragged": (_i, [_p, _p, _p, _p, _i64, _p, _i, _i, _i, _p]),
+    "advh_zero_tail_rows_h": (_i, [_p, _i64, _p, _i, _i, _i, _p]),
+    "advh_w2v2_frontend_bwd_group_ragged": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "advh_w2v2_frontend_bwd_group_split_ragged": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p, _p]),
+    "advh_wave_bwd_ragged": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p, _i, _f, _p, _i64, _i, _i, _p, _p]),
 }
 
 _lib = None

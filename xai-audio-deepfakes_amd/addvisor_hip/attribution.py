@@ -1133,6 +1133,8 @@ NEURON_LOSS_SCALE = 128.0
 
 
 class HipAttribution:
+    _lens = None          # the per-clip lengths of the ragged call in flight (``lengths=``), None outside one
+
     def __init__(self, emb: HipEmbedder, loss_scale: float = 4096.0, precision: Optional[str] = None,
                  neuron_loss_scale: float = NEURON_LOSS_SCALE):
         """``precision``: None = the embedder's (an fp32-class embedder gives the fp32-class gradient chain, the reference's
@@ -1155,18 +1157,48 @@ class HipAttribution:
     # ``s * B + b``, ``k * B + b``, ``(p * K + j) * B + b``) or ``(row0 + r) // S`` (``clip_major=1``: rows ``b * S + s``).  A
     # waveform row is the classifier's input itself, so the layout is not used here; the mask-domain engine
     # (spectral_attribution.py) overrides the pair and resynthesises each row from its clip's spectrogram first.
+    # A ragged call (``lengths=``, ``_ragged``): row ``row0 + r`` carries the length of its clip ``(row0 + r) % B`` -- the methods
+    # that take lengths build clip-minor rows only -- so a path point of clip b has ``lengths[b]`` samples whatever the chunking.
     def _row_gradient(self, pts: torch.Tensor, row0: int = 0, clip_major: int = 0, S: int = 1) -> torch.Tensor:
         """d logit / d row over ``pts [R, n]``, ``[R, n]`` fp32."""
-        self.eg.forward(pts)
+        self.eg.forward(pts, lengths=self._row_lengths(pts.shape[0], row0))
         return self.eg.backward(self.loss_scale)
 
     def _row_logit(self, pts: torch.Tensor, row0: int = 0, clip_major: int = 0, S: int = 1) -> torch.Tensor:
         """``[R]`` fp32 logits of the rows ``pts [R, n]``."""
-        return self.eg.emb.forward(pts, want_hidden=False)[1].view(-1)
+        return self.eg.emb.forward(pts, want_hidden=False, lengths=self._row_lengths(pts.shape[0], row0))[1].view(-1)
 
-    def input_gradient(self, waves: torch.Tensor) -> torch.Tensor:
-        """d logit / d wave, ``[B, L]`` fp32."""
-        return self._row_gradient(self._prep(waves))
+    def _row_lengths(self, R: int, row0: int):
+        lens = self._lens
+        return None if lens is None else [lens[(row0 + r) % len(lens)] for r in range(R)]
+
+    def _ragged(self, waves, lengths):
+        """The clips of a ragged call, ``(x [B, L] on the device, lens)``: ``lengths`` checked on the host before anything is
+        allocated (``HipEmbedder._check_lengths``), and the samples past each length replaced by zeros, so that ``x * g`` and
+        ``x - baseline`` are exactly 0 there whatever the padding holds (the chain itself never reads it)."""
+        B, L = _dims(waves)
+        lens = self.emb._check_lengths(lengths, B, L)
+        return self._mask_tail(self._prep(waves), lens), lens
+
+    @staticmethod
+    def _mask_tail(x: torch.Tensor, lens) -> torch.Tensor:
+        keep = torch.arange(x.shape[1], device=x.device)[None] < torch.tensor(lens, device=x.device)[:, None]
+        return torch.where(keep, x, torch.zeros((), dtype=x.dtype, device=x.device))
+
+    def input_gradient(self, waves: torch.Tensor, lengths=None) -> torch.Tensor:
+        """d logit / d wave, ``[B, L]`` fp32.  ``lengths`` (one sample count per clip, ``EmbedderGrad.forward``): clip b is
+        ``waves[b, :lengths[b]]`` and its gradient the one of that clip run alone, exactly 0 past its length."""
+        if lengths is None:
+            return self._row_gradient(self._prep(waves))
+        return self._ragged_rows(self._row_gradient, *self._ragged(waves, lengths))
+
+    def _ragged_rows(self, fn, x, lens):
+        """``fn(x)`` (``_row_gradient`` / ``_row_logit``) with the rows of ``x`` carrying ``lens``."""
+        self._lens = lens
+        try:
+            return fn(x)
+        finally:
+            self._lens = None
 
     def _finalize(self, g, x, mode):
         out = torch.empty_like(g)
@@ -1184,37 +1216,59 @@ class HipAttribution:
                                                                       "(lower HipAttribution.loss_scale by a power of two)"))
         return out
 
-    def saliency(self, waves):
-        x = self._prep(waves)
-        return self._finalize(self.input_gradient(x), x, 0)
+    def saliency(self, waves, lengths=None):
+        """``|d logit / d wave|``.  ``lengths``: as ``input_gradient``; values past a length are exactly 0."""
+        if lengths is None:
+            x = self._prep(waves)
+            return self._finalize(self.input_gradient(x), x, 0)
+        x, lens = self._ragged(waves, lengths)
+        return self._finalize(self._ragged_rows(self._row_gradient, x, lens), x, 0)
 
-    def input_x_gradient(self, waves):
-        x = self._prep(waves)
-        return self._finalize(self.input_gradient(x), x, 1)
+    def input_x_gradient(self, waves, lengths=None):
+        """``wave * d logit / d wave``.  ``lengths``: as ``input_gradient``; values past a length are exactly 0."""
+        if lengths is None:
+            x = self._prep(waves)
+            return self._finalize(self.input_gradient(x), x, 1)
+        x, lens = self._ragged(waves, lengths)
+        return self._finalize(self._ragged_rows(self._row_gradient, x, lens), x, 1)
 
-    def logits(self, waves) -> torch.Tensor:
-        """``[B]`` fp32 logits of the gradient chain's own forward (the F of the convergence deltas)."""
-        return self._row_logit(self._prep(waves))
+    def logits(self, waves, lengths=None) -> torch.Tensor:
+        """``[B]`` fp32 logits of the gradient chain's own forward (the F of the convergence deltas).  ``lengths``: the ragged
+        forward, clip b pooled over its own frames."""
+        if lengths is None:
+            return self._row_logit(self._prep(waves))
+        return self._ragged_rows(self._row_logit, *self._ragged(waves, lengths))
 
     def integrated_gradients(self, waves, n_steps: int = 50, internal_batch_size: Optional[int] = None, baselines=None,
-                             method: str = "gausslegendre", multiply_by_inputs: bool = True, return_convergence_delta: bool = False):
+                             method: str = "gausslegendre", multiply_by_inputs: bool = True, return_convergence_delta: bool = False,
+                             lengths=None):
         """Captum's IntegratedGradients.  ``baselines``: None (zero), a number, ``[1, L]`` or ``[B, L]``; ``method``: one of
         ``METHODS``.  With ``return_convergence_delta`` returns ``(attr, delta)``, ``delta[b] = sum_j attr[b, j] -
         (F(x_b) - F(base_b))`` ``[B]`` (F from one extra forward over x and the baselines).  A constant clip (the alpha = 0
         point of a number baseline under ``riemann_left`` / ``riemann_trapezoid``) is where the classifier's per-clip
-        normalisation has no scale: its gradient can leave the chain's range, and the call then raises FloatingPointError."""
+        normalisation has no scale: its gradient can leave the chain's range, and the call then raises FloatingPointError.
+        ``lengths`` (one sample count per clip): a ragged batch.  Every path point of clip b carries ``lengths[b]`` whatever the
+        chunking, the input and the baseline count as zero past it, so the attribution is exactly 0 there, and the delta's F is
+        the ragged forward (a shared ``[1, L]`` baseline is scored once per clip, under that clip's length)."""
         B, L = _dims(waves)
+        lens = None if lengths is None else self.emb._check_lengths(lengths, B, L)
         base = check_ig_baselines(baselines, B, L)
         alphas, steps = approximation(method, n_steps)
         _check_delta(return_convergence_delta, multiply_by_inputs)
         x = self._prep(waves)
         base = _device_base(base, x)
-        out, sums = self._integrate_path(x, base, alphas, steps, internal_batch_size, self._row_gradient,
-                                         FIN_IG if multiply_by_inputs else FIN_MEAN, return_convergence_delta)
-        out = self._checked(out)
-        if not return_convergence_delta:
-            return out
-        f = self.logits(torch.cat([x, base])).double()
+        if lens is not None:
+            x, base = self._mask_tail(x, lens), self._mask_tail(base.expand(B, L), lens)
+        self._lens = lens
+        try:
+            out, sums = self._integrate_path(x, base, alphas, steps, internal_batch_size, self._row_gradient,
+                                             FIN_IG if multiply_by_inputs else FIN_MEAN, return_convergence_delta)
+            out = self._checked(out)
+            if not return_convergence_delta:
+                return out
+            f = self._row_logit(torch.cat([x, base])).double()
+        finally:
+            self._lens = None
         fb = f[B:].expand(B) if base.shape[0] == 1 else f[B:]
         return out, (sums.double() - (f[:B] - fb)).float()
 

@@ -116,6 +116,7 @@ class EmbedderGrad:
         self._ws: Dict[Tuple[int, int], dict] = {}
         self._wcache: dict = {}
         self._stop: Optional[int] = None                       # forward(to_layer=l): the layer the last pass stopped at
+        self._rag: Optional[torch.Tensor] = None               # forward(lengths=...): int32 [2, B] on the device, samples | frames
 
     # ------------------------------------------------------------------ buffers and plans
     def _workspace(self, B: int, L: int) -> dict:
@@ -207,18 +208,33 @@ class EmbedderGrad:
         return w
 
     # ------------------------------------------------------------------ forward with saves
-    def forward(self, wave: torch.Tensor, length: Optional[int] = None, to_layer: Optional[int] = None):
+    def forward(self, wave: torch.Tensor, length: Optional[int] = None, to_layer: Optional[int] = None, lengths=None):
         """The classifier with the backward's saves: ``(logits [B,1], probs [B,1])``.  ``to_layer=l`` (the neuron methods,
         ``captum.attr.Neuron*``): the pass stops at ``hidden_states[l]`` -- the front end and layers ``0 .. l-1`` run with their
         saves, and for ``l == nl`` of a full-depth pre-LN model the final LayerNorm, whose output ``hidden_states[nl]`` is; no
         layer ``>= l``, no pooling and no logreg is launched -- and returns it, ``[B, T, H]`` fp32.  After such a pass only
-        ``hidden(l' <= l)`` and ``backward(from_layer <= l, ...)`` are defined."""
+        ``hidden(l' <= l)`` and ``backward(from_layer <= l, ...)`` are defined.
+        ``lengths`` (a sequence or 1-D integer tensor of ``B`` sample counts; ``HipEmbedder.forward``): a ragged batch.  Clip
+        ``b`` is ``wave[b, :lengths[b]]``, what lies behind is padding of any content, and everything this pass and the
+        ``backward`` after it return for the clip is what they return for that clip run alone, unpadded: logits pooled over its
+        own ``T_b = frame_lengths(lengths)[b]`` frames, ``to_layer`` hidden states with rows ``t >= T_b`` zero, ``dx[b, lengths[b]:]``
+        and layer gradients on rows ``t >= T_b`` exactly 0.  Workspace and plans are those of the padded ``(B, L)`` call."""
+        lens = None
+        if lengths is not None:                            # host checks, before any allocation, plan or launch
+            if length is not None:
+                raise ValueError("give length= (one length for the batch) or lengths= (one per clip), not both")
+            if wave.dim() != 2:
+                raise ValueError("wave must be a tensor [B, n]")
+            lens = self.emb._check_lengths(lengths, wave.shape[0], wave.shape[1])
         stop = None if to_layer is None else check_layer(to_layer, self.emb.nl)
         emb, cfg, lib, sp = self.emb, self.cfg, _lib.lib(), self.split
         wave = wave.contiguous()
         B, n_in = wave.shape
         L = n_in if length is None else int(length)
         w = self._workspace(B, L)
+        rag = None
+        if lens is not None:                               # sample and frame counts in one small copy: rag[0] = lens, rag[1] = frames
+            rag = torch.tensor([lens, emb.frame_lengths(lens)], dtype=torch.int32).to(self.dev, non_blocking=False)
         f = w["f"]
         st = torch.cuda.current_stream().cuda_stream
         Ls, P, T, M, H = f["Ls"], f["P"], f["T"], f["M"], cfg.hidden_size
@@ -229,7 +245,17 @@ class EmbedderGrad:
         y = [body(t, i) for i, t in enumerate(w["y"])]
         zb = [None if t is None else (body(t, i) if i < nfe - 1 else t) for i, t in enumerate(w["z"])]
         out0 = zb[0] if lm else y[0]
-        if sp:
+        if rag is not None and sp:
+            _lib.check(lib.advh_w2v2_frontend_split_ragged(
+                wave.data_ptr(), wave.stride(0), n_in, B, L, emb.w0.data_ptr(), None if emb.b0 is None else emb.b0.data_ptr(),
+                ln0.g.data_ptr(), ln0.b.data_ptr(), 1 if lm else 0, 1, f["stats"].data_ptr(), f["norm"].data_ptr(), f["mr"].data_ptr(),
+                out0.data_ptr(), out0.stride(0), Ls[0], P[0], C[0], rag[0].data_ptr(), st), "advh_w2v2_frontend_split_ragged")
+        elif rag is not None:
+            _lib.check(lib.advh_w2v2_frontend_ragged(
+                wave.data_ptr(), wave.stride(0), n_in, B, L, emb.w0.data_ptr(), None if emb.b0 is None else emb.b0.data_ptr(),
+                ln0.g.data_ptr(), ln0.b.data_ptr(), 1 if lm else 0, 1, f["stats"].data_ptr(), f["norm"].data_ptr(), f["mr"].data_ptr(),
+                out0.data_ptr(), Ls[0], P[0], C[0], rag[0].data_ptr(), st), "advh_w2v2_frontend_ragged")
+        elif sp:
             _lib.check(lib.advh_w2v2_frontend_split(
                 wave.data_ptr(), wave.stride(0), n_in, B, L, emb.w0.data_ptr(), None if emb.b0 is None else emb.b0.data_ptr(),
                 ln0.g.data_ptr(), ln0.b.data_ptr(), 1 if lm else 0, 1, f["stats"].data_ptr(), f["norm"].data_ptr(), f["mr"].data_ptr(),
@@ -252,6 +278,8 @@ class EmbedderGrad:
         emb.fp_ln(w["feat"], M, eps, out_h=f["featn"], split=sp)
         h = f["h"]
         f["proj"].run(f["featn"], out_f=h)
+        if rag is not None:                                # hidden_states[~mask] = 0: the positional conv's zero padding
+            _lib.check(lib.advh_zero_tail_rows(h.data_ptr(), rag[1].data_ptr(), B, T, H, st), "advh_zero_tail_rows")
         K, Gp = cfg.num_conv_pos_embeddings, cfg.num_conv_pos_embedding_groups
         if sp:
             _lib.check(lib.advh_posconv_gather_split(h.data_ptr(), f["xg"].data_ptr(), f["xg"].stride(0), B, T, H, Gp, K, K // 2, st),
@@ -266,10 +294,14 @@ class EmbedderGrad:
             emb.enc_ln(w["h1"], M, eps, out_f=w["x"][0], out_h=h16, split=sp)
         self._start = None
         self._stop = stop
+        self._rag = rag
         self._encoder_tail(w, 0, B, stop)
         self._last = (wave, B, n_in, L)
         if stop is not None:
-            return self._hidden_buf(w, stop).view(B, T, H).clone()
+            hid = self._hidden_buf(w, stop).view(B, T, H).clone()
+            if rag is not None:
+                _lib.check(lib.advh_zero_tail_rows(hid.data_ptr(), rag[1].data_ptr(), B, T, H, st), "advh_zero_tail_rows")
+            return hid
         return f["logit"].clone().view(B, 1), f["prob"].clone().view(B, 1)
 
     def _encoder_tail(self, w: dict, start: int, B: int, stop: Optional[int] = None) -> None:
@@ -282,12 +314,20 @@ class EmbedderGrad:
         T, M, H = f["T"], f["M"], cfg.hidden_size
         eps, nl = cfg.layer_norm_eps, emb.nl
         h16 = f["h16"]
+        rag = self._rag                                    # the [2, B] lengths of a ragged pass (forward(lengths=...)), else None
         for l in range(start, nl if stop is None else stop):
             lay = f["layers"][l]
             if self.stable:
                 emb.ln1[l](w["x"][l], M, eps, out_h=h16, split=sp)
             lay["qkv"].run(h16, out_h=w["qkv"][l])
-            if sp:
+            if rag is not None and sp:
+                _lib.check(lib.advh_attention_split_ragged(w["qkv"][l].data_ptr(), w["qkv"][l].stride(0), f["ctx"].data_ptr(),
+                                                           f["ctx"].stride(0), rag[1].data_ptr(), B, T, H, cfg.num_attention_heads, st),
+                           "advh_attention_split_ragged")
+            elif rag is not None:
+                _lib.check(lib.advh_attention_f16_ragged(w["qkv"][l].data_ptr(), f["ctx"].data_ptr(), rag[1].data_ptr(), B, T, H,
+                                                         cfg.num_attention_heads, st), "advh_attention_f16_ragged")
+            elif sp:
                 _lib.check(lib.advh_attention_split(w["qkv"][l].data_ptr(), w["qkv"][l].stride(0), f["ctx"].data_ptr(), f["ctx"].stride(0),
                                                     B, T, H, cfg.num_attention_heads, st), "advh_attention_split")
             else:
@@ -313,6 +353,10 @@ class EmbedderGrad:
             final = w["xf"]
         if stop is not None:
             return
+        if rag is not None:
+            _lib.check(lib.advh_pool_logreg_ragged(final.data_ptr(), emb.coef.data_ptr(), emb.intercept, f["logit"].data_ptr(),
+                                                   f["prob"].data_ptr(), None, rag[1].data_ptr(), B, T, H, st), "advh_pool_logreg_ragged")
+            return
         _lib.check(lib.advh_pool_logreg(final.data_ptr(), emb.coef.data_ptr(), emb.intercept, f["logit"].data_ptr(),
                                         f["prob"].data_ptr(), None, B, T, H, st), "advh_pool_logreg")
 
@@ -332,7 +376,11 @@ class EmbedderGrad:
             raise ValueError(f"the last pass stopped at layer {self._stop}: hidden_states[{l}] was not computed")
         _, B, _, L = self._last
         w = self._workspace(B, L)
-        return self._hidden_buf(w, l).view(B, w["f"]["T"], self.cfg.hidden_size).clone()
+        hid = self._hidden_buf(w, l).view(B, w["f"]["T"], self.cfg.hidden_size).clone()
+        if self._rag is not None:                          # a ragged pass: rows past a clip's frames are zero
+            _lib.check(_lib.lib().advh_zero_tail_rows(hid.data_ptr(), self._rag[1].data_ptr(), B, w["f"]["T"], self.cfg.hidden_size,
+                                                      torch.cuda.current_stream().cuda_stream), "advh_zero_tail_rows")
+        return hid
 
     def forward_from(self, layer: int, hidden: torch.Tensor):
         """The classifier from ``hidden_states[layer]`` on: ``hidden [R, T, H]`` fp32 rows take the place of the layer's input,
@@ -343,6 +391,8 @@ class EmbedderGrad:
         l = check_layer(layer, self.emb.nl)
         if getattr(self, "_last", None) is None:
             raise RuntimeError("forward_from() needs one forward pass first (it fixes the clip length of the workspace)")
+        if self._rag is not None:
+            raise RuntimeError("the last pass was ragged (forward(lengths=...)): forward_from takes no per-clip lengths")
         L = self._last[3]
         H, nl = self.cfg.hidden_size, self.emb.nl
         if not torch.is_tensor(hidden) or hidden.dim() != 3 or hidden.dtype != torch.float32 or not hidden.is_cuda:
@@ -410,6 +460,27 @@ class EmbedderGrad:
             _lib.check(lib.advh_attention_bwd_f16(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), B, T, H, heads, st),
                        "advh_attention_bwd_f16")
 
+    def _att_bwd_ragged(self, qkv, dctx, dqkv, frames, B, T, H, heads, st):
+        """``_att_bwd`` of a ragged pass (advh_attention_bwd_*_ragged): same refusals, ``frames`` int32 [B] on the device."""
+        lib = _lib.lib()
+        if self.split:
+            _lib.check(lib.advh_attention_bwd_split_ragged(qkv.data_ptr(), qkv.stride(0), dctx.data_ptr(), dctx.stride(0), dqkv.data_ptr(),
+                                                           dqkv.stride(0), frames.data_ptr(), B, T, H, heads, st),
+                       "advh_attention_bwd_split_ragged")
+        else:
+            if H // heads > 64 and T > F16_WIDE_HEAD_MAX_T:
+                raise _lib.AdvhError(f"advh_attention_bwd_f16_ragged: ADVH_EUNSUPPORTED: head dim {H // heads} > 64 is held for T <= {F16_WIDE_HEAD_MAX_T} "
+                                     f"frames only (T = {T}: its whole-clip tiles exceed the 160 KiB of LDS); shorten the clip or use precision='f32'")
+            _lib.check(lib.advh_attention_bwd_f16_ragged(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), frames.data_ptr(), B, T, H,
+                                                         heads, st), "advh_attention_bwd_f16_ragged")
+
+    def _zero_tail(self, g32, g16, rag, B, T, H, st):
+        """Rows ``t >= T_b`` of a residual-stream gradient = 0: the fp32 buffer and its fp16 / plane-pair copy."""
+        lib = _lib.lib()
+        _lib.check(lib.advh_zero_tail_rows(g32.data_ptr(), rag[1].data_ptr(), B, T, H, st), "advh_zero_tail_rows")
+        _lib.check(lib.advh_zero_tail_rows_h(g16.data_ptr(), g16.stride(0) if self.split else 0, rag[1].data_ptr(), B, T, H, st),
+                   "advh_zero_tail_rows_h")
+
     def _ln_bwd_frozen(self, ln, x, dy, M, out_f=None, out_h=None, add=None):
         """advh_layernorm_bwd_frozen(_split): ``_ln_bwd`` with ``1/sigma`` a constant (the LN-rule)."""
         st = torch.cuda.current_stream().cuda_stream
@@ -453,6 +524,8 @@ class EmbedderGrad:
             raise ValueError("fuse must be 0 (none), 1 (mean), 2 (max) or 3 (min)")
         if getattr(self, "_last", None) is None:
             raise RuntimeError("attention_probs() needs a forward pass first")
+        if self._rag is not None:
+            raise ValueError("the last pass was ragged (forward(lengths=...)): attention maps take no per-clip lengths")
         if self._start is not None and l < self._start:
             raise ValueError(f"the last pass started at layer {self._start}: layer {l}'s attention did not run")
         if self._stop is not None and l >= self._stop:
@@ -538,6 +611,10 @@ class EmbedderGrad:
             check_layer(to_layer, self.emb.nl)
         if getattr(self, "_last", None) is None:
             raise RuntimeError("backward() needs a forward pass first")
+        rag = self._rag
+        if rag is not None and (attention_maps is not None or rules is not None):
+            raise ValueError("the last pass was ragged (forward(lengths=...)): backward takes neither attention_maps nor rules "
+                             "after it (they have no per-clip lengths)")
         _w = self._workspace(self._last[1], self._last[3])["f"]
         top, box = self._seed_args(self._last[1], _w["T"], self.cfg.hidden_size, seed, to_layer, from_layer, neuron, layer_seed, row_scale)
         if from_layer is None and self._stop is not None:
@@ -575,13 +652,22 @@ class EmbedderGrad:
                 p(src), p(rs), loss_scale, B, T, H,
                 None if box is None else (ctypes.c_int * 6)(*box), da.data_ptr(), d16.data_ptr(), int(sp), d16.stride(0) if sp else 0, st),
                 "advh_layer_seed")
+            if rag is not None:                            # a seed or box reaching past a clip's frames is ignored
+                self._zero_tail(da, d16, rag, B, T, H, st)
         else:
             top = nl
             if seed is None:
                 w["dlogit"].fill_(loss_scale)
             else:
                 w["dlogit"].copy_(seed.reshape(-1).to(w["dlogit"].dtype) * loss_scale)
-            if sp:
+            if rag is not None and sp:
+                _lib.check(lib.advh_pool_logreg_bwd_split_ragged(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(),
+                                                                 d16.stride(0), rag[1].data_ptr(), B, T, H, st),
+                           "advh_pool_logreg_bwd_split_ragged")
+            elif rag is not None:
+                _lib.check(lib.advh_pool_logreg_bwd_ragged(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(),
+                                                           rag[1].data_ptr(), B, T, H, st), "advh_pool_logreg_bwd_ragged")
+            elif sp:
                 _lib.check(lib.advh_pool_logreg_bwd_split(emb.coef.data_ptr(), w["dlogit"].data_ptr(), da.data_ptr(), d16.data_ptr(),
                                                           d16.stride(0), B, T, H, st), "advh_pool_logreg_bwd_split")
             else:
@@ -590,6 +676,8 @@ class EmbedderGrad:
         # the rules swap a launch for its conservative form (csrc/lrp.hip); rules=None is the plain chain, launch for launch
         ln_bwd = self._ln_bwd_frozen if (rules is not None and rules.ln) else self._ln_bwd
         att_bwd = self._att_bwd_value if (rules is not None and rules.attention) else self._att_bwd
+        if rag is not None:                                # rows past a clip's frames: never read, written as zeros
+            att_bwd = lambda qkv, dctx, dqkv, B_, T_, H_, heads_, st_: self._att_bwd_ragged(qkv, dctx, dqkv, rag[1], B_, T_, H_, heads_, st_)
         gelu_id = rules is not None and rules.gelu == "identity"
 
         def ff2_bwd(bl, l):                                                                   # d16 -> w["dI"] = d(pre-GELU)
@@ -636,6 +724,8 @@ class EmbedderGrad:
             _lib.check(lib.advh_posconv_gather(da.data_ptr(), f["xg"].data_ptr(), B, T, H, Gp, K, K // 2 - 1, w["pc"].data_ptr(), st),
                        "advh_posconv_gather")
         w["pos"].run(f["xg"], out_f=db, out_h=d16, resid=da)                                  # d h0
+        if rag is not None:        # the backward of the forward's zeroing of h: the convolution spread the last frames' gradient into padded rows
+            self._zero_tail(db, d16, rag, B, T, H, st)
         w["proj"].run(d16, out_h=w["dfeatn"])
         dz = w["dz"]
         last = nfe - 1
@@ -657,7 +747,18 @@ class EmbedderGrad:
                 plan.run(a0, out_h=body(i - 1), dact_src=zb(i - 1) if i > 1 else None)
         if not self.layer_mode:
             ln0 = emb.fe_ln[0]
-            if sp:
+            if rag is not None and sp:
+                _lib.check(lib.advh_w2v2_frontend_bwd_group_split_ragged(
+                    wave.data_ptr(), wave.stride(0), n_in, B, L, emb.w0.data_ptr(), ln0.g.data_ptr(), f["stats"].data_ptr(),
+                    f["norm"].data_ptr(), f["mr"].data_ptr(), body(0).data_ptr(), dz[0].stride(0), w["part"].data_ptr(),
+                    w["sums"].data_ptr(), body(0).data_ptr(), dz[0].stride(0), Ls[0], P[0], C[0], rag[0].data_ptr(), st),
+                    "advh_w2v2_frontend_bwd_group_split_ragged")
+            elif rag is not None:
+                _lib.check(lib.advh_w2v2_frontend_bwd_group_ragged(
+                    wave.data_ptr(), wave.stride(0), n_in, B, L, emb.w0.data_ptr(), ln0.g.data_ptr(), f["stats"].data_ptr(),
+                    f["norm"].data_ptr(), f["mr"].data_ptr(), body(0).data_ptr(), w["part"].data_ptr(), w["sums"].data_ptr(),
+                    body(0).data_ptr(), Ls[0], P[0], C[0], rag[0].data_ptr(), st), "advh_w2v2_frontend_bwd_group_ragged")
+            elif sp:
                 _lib.check(lib.advh_w2v2_frontend_bwd_group_split(
                     wave.data_ptr(), wave.stride(0), n_in, B, L, emb.w0.data_ptr(), ln0.g.data_ptr(), f["stats"].data_ptr(),
                     f["norm"].data_ptr(), f["mr"].data_ptr(), body(0).data_ptr(), dz[0].stride(0), w["part"].data_ptr(),
@@ -669,6 +770,11 @@ class EmbedderGrad:
                     body(0).data_ptr(), Ls[0], P[0], C[0], st), "advh_w2v2_frontend_bwd_group")
         w["g_plan"].run(body(0), out_f=w["g"])
         dx = torch.empty((B, n_in), dtype=torch.float32, device=wave.device)
+        if rag is not None:
+            _lib.check(lib.advh_wave_bwd_ragged(w["g"].data_ptr(), wave.data_ptr(), wave.stride(0), n_in, B, L, f["stats"].data_ptr(),
+                                                w["dxh"].data_ptr(), w["wpart"].data_ptr(), 1, 1.0 / loss_scale, dx.data_ptr(), n_in,
+                                                Ls[0], P[0], rag[0].data_ptr(), st), "advh_wave_bwd_ragged")
+            return dx
         _lib.check(lib.advh_wave_bwd(w["g"].data_ptr(), wave.data_ptr(), wave.stride(0), n_in, B, L, f["stats"].data_ptr(),
                                      w["dxh"].data_ptr(), w["wpart"].data_ptr(), 1, 1.0 / loss_scale, dx.data_ptr(), n_in,
                                      Ls[0], P[0], st), "advh_wave_bwd")

@@ -11,10 +11,12 @@ int advh_init_attention_ragged();   // attention_ragged.hip
 int advh_split_flag_attention(int* flag);
 int advh_split_flag_attention_ragged(int* flag);
 int advh_split_flag_attention_bwd_f32(int* flag);
+int advh_split_flag_attention_bwd_ragged(int* flag);
 int advh_split_flag_attribution_layer(int* flag);
 int advh_split_flag_attribution_neuron(int* flag);
 int advh_split_flag_attention_bwd_x3(int* flag);
 int advh_split_flag_backward(int* flag);
+int advh_split_flag_backward_ragged(int* flag);
 int advh_split_flag_conv_taps(int* flag);
 int advh_split_flag_frontend(int* flag);
 int advh_split_flag_frontend_ragged(int* flag);
