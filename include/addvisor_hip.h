@@ -1400,6 +1400,19 @@ int advh_wave_bwd_ragged(const float* g, const float* wave, int64_t wave_stride,
                          float* dxhat_ws, float* part_ws, int normalize, float out_scale, float* dx, int64_t dx_stride, int T0, int P0,
                          const int32_t* lens, advh_stream_t stream);
 
+/* ---- attention for clips of any length (csrc/attention_long.hip) ----------------------------------------------------------
+ * advh_attention_long_f16 / advh_attention_long_split: the layouts of advh_attention_f16 / _split (qkv [B*T][3H], ctx [B*T][H],
+ *   fp16 or split plane pairs qkv_lo / ctx_lo elements apart) for ANY T >= 1: the keys stream through LDS in blocks of 256 (112
+ *   in the split format at head dims above 64) with an online softmax; grid (heads, B, ceil(T / 128)), one block of 128 queries
+ *   per workgroup.  `frames` is an int32 [B] device array or NULL: with it, every bound of clip b is Tv = clamp(frames[b], 1, T)
+ *   as in the ragged entry points above (rows t < Tv of ctx: the result for the clip's first Tv rows alone; rows Tv <= t < T:
+ *   zeros in every plane; rows >= Tv of qkv are never read for their value); NULL: Tv = T.  ADVH_EINVAL for what the whole-clip
+ *   pair reports (frames may be NULL); ADVH_EUNSUPPORTED for dm % 8, dm > 128, B > 65535 or more than 65535 query blocks; both
+ *   before any launch.  The whole-clip entry points keep their T <= 256 limit.                                               */
+int advh_attention_long_f16(const void* qkv, void* ctx, const int32_t* frames, int B, int T, int H, int heads, advh_stream_t stream);
+int advh_attention_long_split(const void* qkv, int64_t qkv_lo, void* ctx, int64_t ctx_lo, const int32_t* frames, int B, int T, int H,
+                              int heads, advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

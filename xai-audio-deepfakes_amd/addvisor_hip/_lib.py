@@ -208,6 +208,8 @@ SIGNATURES = {
     "advh_zero_tail_rows_h": (_i, [_p, _i64, _p, _i, _i, _i, _p]),
     "advh_w2v2_frontend_bwd_group_ragged": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "advh_w2v2_frontend_bwd_group_split_ragged": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p, _p]),
+    "advh_attention_long_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "advh_attention_long_split": (_i, [_p, _i64, _p, _i64, _p, _i, _i, _i, _i, _p]),
     "advh_wave_bwd_ragged": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p, _i, _f, _p, _i64, _i, _i, _p, _p]),
 }
 

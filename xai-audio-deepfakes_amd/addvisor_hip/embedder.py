@@ -118,6 +118,8 @@ class _LN:
 class HipEmbedder:
     """``forward(wave[B, n]) -> hidden_states[layer_index] [B,T,H] fp32, logits [B,1], probs [B,1]``."""
 
+    WHOLE_CLIP_MAX_FRAMES = 256        # up to here K and V of a (clip, head) stay in LDS (csrc/attention.hip); above, the keys stream
+
     def __init__(self, cfg: EmbedderConfig, sd: Dict[str, torch.Tensor], coef, intercept, device, precision: Optional[str] = None):
         _lib.init()
         self.cfg, self.dev = cfg, device
@@ -174,6 +176,13 @@ class HipEmbedder:
         for k, s in zip(reversed(self.cfg.conv_kernel), reversed(self.cfg.conv_stride)):
             n = (n - 1) * s + k
         return n
+
+    def whole_clip_max_samples(self) -> int:
+        """The longest clip with ``WHOLE_CLIP_MAX_FRAMES`` frames (82 319 samples, 5.1 s, for wav2vec2)."""
+        n = self.WHOLE_CLIP_MAX_FRAMES + 1
+        for k, s in zip(reversed(self.cfg.conv_kernel), reversed(self.cfg.conv_stride)):
+            n = (n - 1) * s + k
+        return n - 1
 
     def frame_lengths(self, lengths) -> List[int]:
         """Valid encoder frames of clips with ``lengths`` samples (HF ``_get_feat_extract_output_lengths``)."""
@@ -418,7 +427,14 @@ class HipEmbedder:
             if stable:
                 self.ln1[l](h, M, eps, out_h=h16, split=sp)
             lay["qkv"].run(h16, out_h=ws["qkv"])
-            if rag is not None and sp:
+            if T > self.WHOLE_CLIP_MAX_FRAMES and sp:                 # streamed keys (csrc/attention_long.hip); frames may be absent
+                _lib.check(lib.advh_attention_long_split(ws["qkv"].data_ptr(), ws["qkv"].stride(0), ws["ctx"].data_ptr(),
+                                                         ws["ctx"].stride(0), None if rag is None else frames_p, B, T, H,
+                                                         cfg.num_attention_heads, st), "advh_attention_long_split")
+            elif T > self.WHOLE_CLIP_MAX_FRAMES:
+                _lib.check(lib.advh_attention_long_f16(ws["qkv"].data_ptr(), ws["ctx"].data_ptr(), None if rag is None else frames_p,
+                                                       B, T, H, cfg.num_attention_heads, st), "advh_attention_long_f16")
+            elif rag is not None and sp:
                 _lib.check(lib.advh_attention_split_ragged(ws["qkv"].data_ptr(), ws["qkv"].stride(0), ws["ctx"].data_ptr(),
                                                            ws["ctx"].stride(0), frames_p, B, T, H, cfg.num_attention_heads, st),
                            "advh_attention_split_ragged")

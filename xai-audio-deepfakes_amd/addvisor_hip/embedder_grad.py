@@ -97,6 +97,16 @@ class LrpRules:
             raise ValueError(f"the gelu rule must be one of {GELU_RULES}, not {self.gelu!r}")
 
 
+def check_chain_frames(emb: HipEmbedder, L: int) -> None:
+    """The gradient chain keeps the whole-clip attention kernels, forward and backward: ``AdvhError`` for a batch of ``L``
+    samples with more frames than they hold.  Host only."""
+    T = emb._lengths(int(L))[-1]
+    if T > emb.WHOLE_CLIP_MAX_FRAMES:
+        raise _lib.AdvhError(f"EmbedderGrad.forward: ADVH_EUNSUPPORTED: the gradient chain is held for T <= {emb.WHOLE_CLIP_MAX_FRAMES} frames "
+                             f"({emb.whole_clip_max_samples()} samples) and this clip has T = {T} ({int(L)} samples); the forward-only "
+                             "methods (HipEmbedder.forward, classify, explain, the perturbation attributions) take longer clips")
+
+
 class EmbedderGrad:
     def __init__(self, emb: HipEmbedder, precision: Optional[str] = None):
         """``precision``: None = the embedder's own ("f32": split-format chain; "f16": fp16 chain), or "f16" to run the fp16
@@ -227,6 +237,7 @@ class EmbedderGrad:
                 raise ValueError("wave must be a tensor [B, n]")
             lens = self.emb._check_lengths(lengths, wave.shape[0], wave.shape[1])
         stop = None if to_layer is None else check_layer(to_layer, self.emb.nl)
+        check_chain_frames(self.emb, wave.shape[-1] if length is None else int(length))     # before any allocation, plan or launch
         emb, cfg, lib, sp = self.emb, self.cfg, _lib.lib(), self.split
         wave = wave.contiguous()
         B, n_in = wave.shape

@@ -7,9 +7,11 @@
 int advh_init_rest();
 int advh_init_attention();   // attention.hip
 int advh_init_attention_ragged();   // attention_ragged.hip
+int advh_init_attention_long();   // attention_long.hip
 // per-translation-unit setters of the split-format range flag pointer (csrc/device_math.h: ADVH_SPLIT_FLAG_SETTER)
 int advh_split_flag_attention(int* flag);
 int advh_split_flag_attention_ragged(int* flag);
+int advh_split_flag_attention_long(int* flag);
 int advh_split_flag_attention_bwd_f32(int* flag);
 int advh_split_flag_attention_bwd_ragged(int* flag);
 int advh_split_flag_attribution_layer(int* flag);
