@@ -1413,6 +1413,31 @@ int advh_attention_long_f16(const void* qkv, void* ctx, const int32_t* frames, i
 int advh_attention_long_split(const void* qkv, int64_t qkv_lo, void* ctx, int64_t ctx_lo, const int32_t* frames, int B, int T, int H,
                               int heads, advh_stream_t stream);
 
+/* ---- attention backward for clips of any length (csrc/attention_bwd_long.hip) ---------------------------------------------
+ * advh_attention_bwd_long_f16 / advh_attention_bwd_long_split: the layouts of advh_attention_bwd_f16 / _split (qkv and dqkv
+ *   [B*T][3H], dctx [B*T][H], fp16 or split plane pairs qkv_lo / dctx_lo / dqkv_lo elements apart) for ANY T >= 1 and head dims
+ *   dm = H / heads that are multiples of 8 up to 128, in both formats.  Two kernels on `stream`, no atomics, every product on the
+ *   fp32-input matrix instruction: the query kernel (grid (heads, B, ceil(T / 128)); keys streamed in blocks of 128, two sweeps)
+ *   writes the softmax statistics (m in the log2 domain, 1 / l, delta) of every query to `stats_ws` and the Q third of dqkv; the
+ *   key kernel (grid (heads, B, ceil(T / 128)); queries streamed in blocks of 128 in index order) reads them and writes the K and
+ *   V thirds.  stats_ws: fp32 [3][B * heads * T], at least advh_attention_bwd_long_ws_bytes(B, T, heads) bytes, content on entry
+ *   irrelevant, 4-byte aligned; it may be shared by consecutive calls on one stream.  Every element of dqkv in rows < T and the
+ *   columns of the launch's heads is written.  Split outputs pass the checked conversion (|x| > 65504 saturates and raises the
+ *   sticky range flag, advh_split_overflow); fp16 outputs are rounded once.
+ *   `frames` is an int32 [B] device array or NULL, with the semantics of advh_attention_long_*: every bound of clip b is
+ *   Tv = clamp(frames[b], 1, T) and T stays the row stride; rows t < Tv of dqkv are the result for the clip's first Tv rows alone
+ *   (they depend on Tv only, not on T or B), rows Tv <= t < T are zeros in every plane and all three thirds, rows >= Tv of qkv /
+ *   dctx / stats_ws are never read.  NULL: Tv = T.
+ *   ADVH_EINVAL for a NULL pointer (frames excepted), a non-positive size, H % heads != 0 or, in the split entry, a plane
+ *   distance that is not a positive multiple of 8; ADVH_EUNSUPPORTED for dm % 8, dm > 128, B > 65535 or more than 65535 blocks of
+ *   128 rows, with dqkv untouched; both before any HIP call.  The whole-clip entry points keep their T <= 256 limit.
+ * advh_attention_bwd_long_ws_bytes: 3 * B * heads * T * 4 rounded up to a multiple of 256; 0 for a non-positive argument.  */
+size_t advh_attention_bwd_long_ws_bytes(int B, int T, int heads);
+int advh_attention_bwd_long_f16(const void* qkv, const void* dctx, void* dqkv, float* stats_ws, const int32_t* frames, int B, int T, int H,
+                                int heads, advh_stream_t stream);
+int advh_attention_bwd_long_split(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, void* dqkv, int64_t dqkv_lo,
+                                  float* stats_ws, const int32_t* frames, int B, int T, int H, int heads, advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

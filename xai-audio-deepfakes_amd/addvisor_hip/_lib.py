@@ -210,6 +210,9 @@ SIGNATURES = {
     "advh_w2v2_frontend_bwd_group_split_ragged": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p, _p]),
     "advh_attention_long_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "advh_attention_long_split": (_i, [_p, _i64, _p, _i64, _p, _i, _i, _i, _i, _p]),
+    "advh_attention_bwd_long_ws_bytes": (C.c_size_t, [_i, _i, _i]),
+    "advh_attention_bwd_long_f16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "advh_attention_bwd_long_split": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, _p]),
     "advh_wave_bwd_ragged": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p, _i, _f, _p, _i64, _i, _i, _p, _p]),
 }
 

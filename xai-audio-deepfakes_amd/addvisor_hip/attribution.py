@@ -1136,14 +1136,15 @@ class HipAttribution:
     _lens = None          # the per-clip lengths of the ragged call in flight (``lengths=``), None outside one
 
     def __init__(self, emb: HipEmbedder, loss_scale: float = 4096.0, precision: Optional[str] = None,
-                 neuron_loss_scale: float = NEURON_LOSS_SCALE):
+                 neuron_loss_scale: float = NEURON_LOSS_SCALE, long_clips: bool = False):
         """``precision``: None = the embedder's (an fp32-class embedder gives the fp32-class gradient chain, the reference's
         fp32 autograd class); "f16" = the fp16-operand chain.  ``neuron_loss_scale``: the power of two the neuron methods seed
-        ``hidden_states[l]`` with (a unit seed there is far larger than the logit's ``coef / T``; DESIGN)."""
+        ``hidden_states[l]`` with (a unit seed there is far larger than the logit's ``coef / T``; DESIGN).  ``long_clips``: passed
+        to the ``EmbedderGrad`` -- True lets every method built on the gradient chain take clips above 256 frames."""
         v = neuron_loss_scale
         if not (isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0 and math.isfinite(v) and math.frexp(v)[0] == 0.5):
             raise ValueError(f"neuron_loss_scale must be a positive power of two, not {v!r}")
-        self.emb, self.eg, self.loss_scale = emb, EmbedderGrad(emb, precision), loss_scale
+        self.emb, self.eg, self.loss_scale = emb, EmbedderGrad(emb, precision, long_clips=long_clips), loss_scale
         self.neuron_loss_scale = float(neuron_loss_scale)
         self.precision = self.eg.precision
 

@@ -97,22 +97,35 @@ class LrpRules:
             raise ValueError(f"the gelu rule must be one of {GELU_RULES}, not {self.gelu!r}")
 
 
-def check_chain_frames(emb: HipEmbedder, L: int) -> None:
-    """The gradient chain keeps the whole-clip attention kernels, forward and backward: ``AdvhError`` for a batch of ``L``
-    samples with more frames than they hold.  Host only."""
+def check_chain_frames(emb: HipEmbedder, L: int, long_clips: bool = False) -> None:
+    """The default gradient chain keeps the whole-clip attention kernels, forward and backward: ``AdvhError`` for a batch of ``L``
+    samples with more frames than they hold, unless the chain was built with ``long_clips=True`` (the streamed kernels of
+    csrc/attention_long.hip and csrc/attention_bwd_long.hip above that length).  Host only."""
     T = emb._lengths(int(L))[-1]
-    if T > emb.WHOLE_CLIP_MAX_FRAMES:
+    if T > emb.WHOLE_CLIP_MAX_FRAMES and not long_clips:
         raise _lib.AdvhError(f"EmbedderGrad.forward: ADVH_EUNSUPPORTED: the gradient chain is held for T <= {emb.WHOLE_CLIP_MAX_FRAMES} frames "
                              f"({emb.whole_clip_max_samples()} samples) and this clip has T = {T} ({int(L)} samples); the forward-only "
-                             "methods (HipEmbedder.forward, classify, explain, the perturbation attributions) take longer clips")
+                             "methods (HipEmbedder.forward, classify, explain, the perturbation attributions) take longer clips, and so "
+                             "does a chain built with long_clips=True (EmbedderGrad, HipAttribution; ADDVISOR_LONG_CLIPS=1 for the "
+                             "runtime singleton)")
 
 
 class EmbedderGrad:
-    def __init__(self, emb: HipEmbedder, precision: Optional[str] = None):
+    long_clips = False          # the default chain refuses clips above 256 frames (check_chain_frames)
+
+    def __init__(self, emb: HipEmbedder, precision: Optional[str] = None, long_clips: bool = False):
         """``precision``: None = the embedder's own ("f32": split-format chain; "f16": fp16 chain), or "f16" to run the fp16
-        chain next to an fp32-class embedder (``HipEmbedder.f16_twin``)."""
+        chain next to an fp32-class embedder (``HipEmbedder.f16_twin``).
+        ``long_clips=True``: clips above 256 frames (82 319 samples) are taken -- there the attention runs on the streamed kernels,
+        forward (advh_attention_long_*) and backward (advh_attention_bwd_long_*, both precisions on the fp32-input matrix
+        instruction); ``seed``, ``to_layer``, ``from_layer``, ``forward_from`` and ``lengths=`` work as below that length, while
+        ``attention_maps=``, ``attention_probs`` and ``rules=`` keep the 256-frame limit of their ``T x T`` kernels.  At 256 frames
+        and below every launch is the default chain's."""
         if precision not in (None, "f16", "f32"):
             raise ValueError("precision must be None, 'f16' or 'f32'")
+        if not isinstance(long_clips, bool):
+            raise ValueError(f"long_clips must be a bool, not {long_clips!r}")
+        self.long_clips = long_clips
         if precision == "f16":
             emb = emb.f16_twin()
         elif precision == "f32" and not emb.split:
@@ -185,6 +198,9 @@ class EmbedderGrad:
         w["sums"] = z(B, C[0], 2, dt=f32)
         w["dxh"] = z(B, L, dt=f32)
         w["wpart"] = z(B, -(-L // 2048), 2, dt=f32)
+        if T > emb.WHOLE_CLIP_MAX_FRAMES:             # long_clips: the streamed attention backward's (m, 1/l, delta), shared by the layers
+            nb = _lib.lib().advh_attention_bwd_long_ws_bytes(B, T, cfg.num_attention_heads)
+            w["att_stats"] = torch.empty(nb // 4, dtype=f32, device=dev)
         # backward plans -----------------------------------------------------------------
         wc = self._wcache
         lin = lambda wt, key: G.plan_linear(M, wt, None, device=dev, cache=(wc, key), split=sp)
@@ -237,7 +253,7 @@ class EmbedderGrad:
                 raise ValueError("wave must be a tensor [B, n]")
             lens = self.emb._check_lengths(lengths, wave.shape[0], wave.shape[1])
         stop = None if to_layer is None else check_layer(to_layer, self.emb.nl)
-        check_chain_frames(self.emb, wave.shape[-1] if length is None else int(length))     # before any allocation, plan or launch
+        check_chain_frames(self.emb, wave.shape[-1] if length is None else int(length), self.long_clips)     # before any allocation, plan or launch
         emb, cfg, lib, sp = self.emb, self.cfg, _lib.lib(), self.split
         wave = wave.contiguous()
         B, n_in = wave.shape
@@ -331,7 +347,16 @@ class EmbedderGrad:
             if self.stable:
                 emb.ln1[l](w["x"][l], M, eps, out_h=h16, split=sp)
             lay["qkv"].run(h16, out_h=w["qkv"][l])
-            if rag is not None and sp:
+            if T > emb.WHOLE_CLIP_MAX_FRAMES:              # long_clips (forward refused otherwise): the streamed kernel, frames or NULL
+                fp = None if rag is None else rag[1].data_ptr()
+                if sp:
+                    _lib.check(lib.advh_attention_long_split(w["qkv"][l].data_ptr(), w["qkv"][l].stride(0), f["ctx"].data_ptr(),
+                                                             f["ctx"].stride(0), fp, B, T, H, cfg.num_attention_heads, st),
+                               "advh_attention_long_split")
+                else:
+                    _lib.check(lib.advh_attention_long_f16(w["qkv"][l].data_ptr(), f["ctx"].data_ptr(), fp, B, T, H,
+                                                           cfg.num_attention_heads, st), "advh_attention_long_f16")
+            elif rag is not None and sp:
                 _lib.check(lib.advh_attention_split_ragged(w["qkv"][l].data_ptr(), w["qkv"][l].stride(0), f["ctx"].data_ptr(),
                                                            f["ctx"].stride(0), rag[1].data_ptr(), B, T, H, cfg.num_attention_heads, st),
                            "advh_attention_split_ragged")
@@ -485,6 +510,29 @@ class EmbedderGrad:
             _lib.check(lib.advh_attention_bwd_f16_ragged(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), frames.data_ptr(), B, T, H,
                                                          heads, st), "advh_attention_bwd_f16_ragged")
 
+    def _att_bwd_long(self, qkv, dctx, dqkv, stats, frames, B, T, H, heads, st):
+        """advh_attention_bwd_long_*: the streamed backward of a ``long_clips`` chain above 256 frames; ``frames`` int32 [B] on
+        the device (a ragged pass) or None."""
+        lib = _lib.lib()
+        fp = None if frames is None else frames.data_ptr()
+        if self.split:
+            _lib.check(lib.advh_attention_bwd_long_split(qkv.data_ptr(), qkv.stride(0), dctx.data_ptr(), dctx.stride(0), dqkv.data_ptr(),
+                                                         dqkv.stride(0), stats.data_ptr(), fp, B, T, H, heads, st),
+                       "advh_attention_bwd_long_split")
+        else:
+            _lib.check(lib.advh_attention_bwd_long_f16(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), stats.data_ptr(), fp, B, T, H,
+                                                       heads, st), "advh_attention_bwd_long_f16")
+
+    def _refuse_maps_above_limit(self, what: str) -> None:
+        """``attention_maps=``, ``attention_probs`` and ``rules=`` run ``T x T`` kernels (csrc/attention_maps.hip, lrp.hip) that hold
+        a whole clip: ``AdvhError`` when the last pass had more frames, before any launch or allocation.  Host only."""
+        L = self._last[3]
+        T = self.emb._lengths(int(L))[-1]
+        if T > self.emb.WHOLE_CLIP_MAX_FRAMES:
+            raise _lib.AdvhError(f"{what}: ADVH_EUNSUPPORTED: the T x T attention kernels behind it are held for T <= "
+                                 f"{self.emb.WHOLE_CLIP_MAX_FRAMES} frames ({self.emb.whole_clip_max_samples()} samples) and the last pass "
+                                 f"had T = {T} ({int(L)} samples); long_clips lifts the limit of the gradient alone")
+
     def _zero_tail(self, g32, g16, rag, B, T, H, st):
         """Rows ``t >= T_b`` of a residual-stream gradient = 0: the fp32 buffer and its fp16 / plane-pair copy."""
         lib = _lib.lib()
@@ -535,6 +583,7 @@ class EmbedderGrad:
             raise ValueError("fuse must be 0 (none), 1 (mean), 2 (max) or 3 (min)")
         if getattr(self, "_last", None) is None:
             raise RuntimeError("attention_probs() needs a forward pass first")
+        self._refuse_maps_above_limit("EmbedderGrad.attention_probs")
         if self._rag is not None:
             raise ValueError("the last pass was ragged (forward(lengths=...)): attention maps take no per-clip lengths")
         if self._start is not None and l < self._start:
@@ -622,6 +671,8 @@ class EmbedderGrad:
             check_layer(to_layer, self.emb.nl)
         if getattr(self, "_last", None) is None:
             raise RuntimeError("backward() needs a forward pass first")
+        if attention_maps is not None or rules is not None:    # before any launch or allocation
+            self._refuse_maps_above_limit("EmbedderGrad.backward(attention_maps=...)" if rules is None else "EmbedderGrad.backward(rules=...)")
         rag = self._rag
         if rag is not None and (attention_maps is not None or rules is not None):
             raise ValueError("the last pass was ragged (forward(lengths=...)): backward takes neither attention_maps nor rules "
@@ -687,7 +738,10 @@ class EmbedderGrad:
         # the rules swap a launch for its conservative form (csrc/lrp.hip); rules=None is the plain chain, launch for launch
         ln_bwd = self._ln_bwd_frozen if (rules is not None and rules.ln) else self._ln_bwd
         att_bwd = self._att_bwd_value if (rules is not None and rules.attention) else self._att_bwd
-        if rag is not None:                                # rows past a clip's frames: never read, written as zeros
+        if T > emb.WHOLE_CLIP_MAX_FRAMES:                  # long_clips; rules were refused above
+            att_bwd = lambda qkv, dctx, dqkv, B_, T_, H_, heads_, st_: self._att_bwd_long(
+                qkv, dctx, dqkv, w["att_stats"], None if rag is None else rag[1], B_, T_, H_, heads_, st_)
+        elif rag is not None:                              # rows past a clip's frames: never read, written as zeros
             att_bwd = lambda qkv, dctx, dqkv, B_, T_, H_, heads_, st_: self._att_bwd_ragged(qkv, dctx, dqkv, rag[1], B_, T_, H_, heads_, st_)
         gelu_id = rules is not None and rules.gelu == "identity"
 

@@ -12,6 +12,7 @@ int advh_init_attention_long();   // attention_long.hip
 int advh_split_flag_attention(int* flag);
 int advh_split_flag_attention_ragged(int* flag);
 int advh_split_flag_attention_long(int* flag);
+int advh_split_flag_attention_bwd_long(int* flag);   // attention_bwd_long.hip raises its LDS limits per launch (advh_ensure_lds): no init function
 int advh_split_flag_attention_bwd_f32(int* flag);
 int advh_split_flag_attention_bwd_ragged(int* flag);
 int advh_split_flag_attribution_layer(int* flag);
