@@ -1438,6 +1438,40 @@ int advh_attention_bwd_long_f16(const void* qkv, const void* dctx, void* dqkv, f
 int advh_attention_bwd_long_split(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, void* dqkv, int64_t dqkv_lo,
                                   float* stats_ws, const int32_t* frames, int B, int T, int H, int heads, advh_stream_t stream);
 
+/* ---- attention maps, the AH-rule and rollout for clips of any length (csrc/attention_maps_long.hip) ------------------------
+ * The streamed forms of advh_attention_maps, advh_attention_bwd_value, advh_rollout_step and advh_rollout_relevance: ANY T >= 1,
+ * head dims that are multiples of 8 up to 128, per-clip lengths.  `frames` is an int32 [B] device array or NULL with the semantics
+ * of advh_attention_bwd_long_*: every bound of clip b is Tv = clamp(frames[b], 1, T), T stays the stride, what is computed for a
+ * clip depends on Tv alone (not on T or B), and rows / columns >= Tv of the inputs are never read.  Every product runs on the
+ * fp32-input matrix instruction for both operand formats; no atomics: results are bit-identical from run to run.
+ * Both attention entries first launch a statistics kernel (grid (heads, B, ceil(T / 128)); keys streamed in blocks of 128 with an
+ * online softmax) that writes (m in the log2 domain, 1 / l) of every query < Tv to planes 0 and 1 of `ws` -- the layout and size
+ * of advh_attention_bwd_long_*'s stats_ws (advh_attention_bwd_long_ws_bytes; plane 2 is not touched), content on entry
+ * irrelevant, shareable by consecutive calls on one stream -- and then one kernel that recomputes P = exp2(s c2 - m) / l per tile.
+ * advh_attention_maps_long: the arguments, semantics and out layout of advh_attention_maps (dctx == NULL: P; otherwise
+ *   max(P * (dO V^T * dscale), 0); fuse 0: out [B][heads][T][T], 1 mean / 2 max / 3 min over heads in index order: out [B][T][T]).
+ *   A workgroup owns one 128 x 128 tile of one clip's (fuse 0: one head's) map.  Every element of out is written: the clip's map
+ *   in the top-left Tv x Tv block, exact zeros elsewhere.  A NaN reaches the elements it enters and wins max and min as it wins
+ *   the sum.
+ * advh_attention_bwd_value_long: the arguments and contract of advh_attention_bwd_value (dV = P^T dO in the V third through the
+ *   checked split conversion; zeros in the Q and K thirds) -- grid (heads, B, ceil(T / 128)), a workgroup owns 128 keys and
+ *   streams Q and dO in blocks of 128 rows in index order.  Rows Tv <= t < T of dqkv are zeros in every plane and third.
+ * ADVH_EINVAL for what the whole-clip entries report and for a NULL ws (frames may be NULL); ADVH_EUNSUPPORTED for dm % 8,
+ *   dm > 128, B > 65535 or more than 65535 blocks of 128 rows, with the output untouched; both before any HIP call, argument errors
+ *   first.  The whole-clip entries keep their T <= 256 limit.
+ * advh_rollout_step_long: advh_rollout_step's arithmetic with every bound, the contraction included, at Tv; Y is exactly 0
+ *   outside its Tv x Tv block.  At frames == NULL and T <= 256 it is bit-equal to advh_rollout_step (same tiles, same k order).
+ * advh_rollout_relevance_long: rel[b][j] = (1 / Tv) sum_{i < Tv} X[b][i][j] for j < Tv, rows in order, and 0 for j >= Tv; a grid
+ *   over column blocks of 256.  Both: NULL pointers (frames excepted), Y == X, Y == M and B, T <= 0 return ADVH_EINVAL before any
+ *   HIP call; B > 65535 or T > 1 048 560 ADVH_EUNSUPPORTED.  */
+int advh_attention_maps_long(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, float dscale, int fuse, float* out,
+                             float* ws, const int32_t* frames, int B, int T, int H, int heads, advh_stream_t stream);
+int advh_attention_bwd_value_long(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, void* dqkv, int64_t dqkv_lo,
+                                  float* ws, const int32_t* frames, int B, int T, int H, int heads, advh_stream_t stream);
+int advh_rollout_step_long(const float* M, const float* X, float* Y, float alpha, float beta, float gamma, int normalize,
+                           const int32_t* frames, int B, int T, advh_stream_t stream);
+int advh_rollout_relevance_long(const float* X, float* rel, const int32_t* frames, int B, int T, advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,10 @@ SIGNATURES = {
     "advh_attention_bwd_long_f16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "advh_attention_bwd_long_split": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, _p]),
     "advh_wave_bwd_ragged": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p, _i, _f, _p, _i64, _i, _i, _p, _p]),
+    "advh_attention_maps_long": (_i, [_p, _i64, _p, _i64, _f, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "advh_attention_bwd_value_long": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, _p]),
+    "advh_rollout_step_long": (_i, [_p, _p, _p, _f, _f, _f, _i, _p, _i, _i, _p]),
+    "advh_rollout_relevance_long": (_i, [_p, _p, _p, _i, _i, _p]),
 }
 
 _lib = None

@@ -1136,15 +1136,18 @@ class HipAttribution:
     _lens = None          # the per-clip lengths of the ragged call in flight (``lengths=``), None outside one
 
     def __init__(self, emb: HipEmbedder, loss_scale: float = 4096.0, precision: Optional[str] = None,
-                 neuron_loss_scale: float = NEURON_LOSS_SCALE, long_clips: bool = False):
+                 neuron_loss_scale: float = NEURON_LOSS_SCALE, long_clips: bool = False, long_maps: bool = False):
         """``precision``: None = the embedder's (an fp32-class embedder gives the fp32-class gradient chain, the reference's
         fp32 autograd class); "f16" = the fp16-operand chain.  ``neuron_loss_scale``: the power of two the neuron methods seed
         ``hidden_states[l]`` with (a unit seed there is far larger than the logit's ``coef / T``; DESIGN).  ``long_clips``: passed
-        to the ``EmbedderGrad`` -- True lets every method built on the gradient chain take clips above 256 frames."""
+        to the ``EmbedderGrad`` -- True lets every method built on the gradient chain take clips above 256 frames, except
+        ``attention_maps``, ``attention_rollout``, ``attention_grad_rollout`` and ``transformer_lrp``, which ``long_maps=True``
+        (it needs ``long_clips=True``) lifts as well and gives their ``lengths=`` argument."""
         v = neuron_loss_scale
         if not (isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0 and math.isfinite(v) and math.frexp(v)[0] == 0.5):
             raise ValueError(f"neuron_loss_scale must be a positive power of two, not {v!r}")
-        self.emb, self.eg, self.loss_scale = emb, EmbedderGrad(emb, precision, long_clips=long_clips), loss_scale
+        kw = {} if long_maps is False else dict(long_maps=long_maps)       # the keyword only when asked for (as the runtime does)
+        self.emb, self.eg, self.loss_scale = emb, EmbedderGrad(emb, precision, long_clips=long_clips, **kw), loss_scale
         self.neuron_loss_scale = float(neuron_loss_scale)
         self.precision = self.eg.precision
 
@@ -2068,14 +2071,28 @@ class HipAttribution:
             raise ValueError(f"{what} must name an encoder layer with an attention block, 0 <= layer < {nl}; got {layer!r}")
         return l
 
-    def _attention_args(self, waves) -> Tuple[int, int, int]:
-        """``(B, L, T)`` before any GPU work; the maps kernel takes ``T <= 256`` frames and head dims ``8, 16, .. 128``."""
+    def _attention_args(self, waves, lengths=None) -> Tuple[int, int, int]:
+        """``(B, L, T)`` before any GPU work; the whole-clip maps kernel takes ``T <= 256`` frames -- a ``long_maps`` engine any
+        number, and ``lengths`` -- and head dims ``8, 16, .. 128``."""
         B, L = _dims(waves)
         cfg = self.eg.emb.cfg
         T, dm = self.eg.emb._lengths(L)[-1], cfg.hidden_size // cfg.num_attention_heads
-        if T > 256 or dm % 8 or dm > 128:
-            raise ValueError(f"attention maps need T <= 256 frames and a head dim that is a multiple of 8 up to 128; got T = {T}, head dim {dm}")
+        long_maps = getattr(self.eg, "long_maps", False)
+        if lengths is not None and not long_maps:
+            raise ValueError("lengths= on the attention maps, rollout and LRP needs an engine built with long_maps=True "
+                             "(HipAttribution(long_clips=True, long_maps=True); ADDVISOR_LONG_MAPS=1 for the runtime singleton)")
+        if (T > 256 and not long_maps) or dm % 8 or dm > 128:
+            raise ValueError(f"attention maps need T <= 256 frames and a head dim that is a multiple of 8 up to 128; got T = {T}, head dim {dm}"
+                             " (long_maps=True lifts the frame limit)")
         return B, L, T
+
+    def _attention_input(self, waves, lengths):
+        """``(x, lens, frames)``: the clips on the device -- of a ragged call with the samples past each length zeroed
+        (``_ragged``) -- their checked lengths or None, and the frame counts as int32 ``[B]`` on the device or None."""
+        if lengths is None:
+            return self._prep(waves), None, None
+        x, lens = self._ragged(waves, lengths)
+        return x, lens, torch.tensor(self.emb.frame_lengths(lens), dtype=torch.int32).to(x.device)
 
     def _target_seed(self, spec, logits: torch.Tensor) -> Optional[torch.Tensor]:
         if spec is None:
@@ -2084,85 +2101,99 @@ class HipAttribution:
             return torch.sign(logits.view(-1))
         return spec.to(self.emb.dev)
 
-    def _rollout_step(self, M, X, Y, alpha, beta, gamma, normalize):
+    def _rollout_step(self, M, X, Y, alpha, beta, gamma, normalize, frames=None):
         B, T = X.shape[0], X.shape[1]
+        if frames is not None or T > 256:                      # long_maps (_attention_args): any T, every bound of clip b at frames[b]
+            _lib.check(_lib.lib().advh_rollout_step_long(M.data_ptr(), X.data_ptr(), Y.data_ptr(), alpha, beta, gamma, int(normalize),
+                                                         None if frames is None else frames.data_ptr(), B, T, _st()),
+                       "advh_rollout_step_long")
+            return
         _lib.check(_lib.lib().advh_rollout_step(M.data_ptr(), X.data_ptr(), Y.data_ptr(), alpha, beta, gamma, int(normalize), B, T, _st()),
                    "advh_rollout_step")
 
-    def _rollout_relevance(self, X: torch.Tensor) -> torch.Tensor:
+    def _rollout_relevance(self, X: torch.Tensor, frames=None) -> torch.Tensor:
         B, T = X.shape[0], X.shape[1]
         rel = torch.empty((B, T), dtype=torch.float32, device=X.device)
+        if frames is not None or T > 256:
+            _lib.check(_lib.lib().advh_rollout_relevance_long(X.data_ptr(), rel.data_ptr(), None if frames is None else frames.data_ptr(),
+                                                              B, T, _st()), "advh_rollout_relevance_long")
+            return rel
         _lib.check(_lib.lib().advh_rollout_relevance(X.data_ptr(), rel.data_ptr(), B, T, _st()), "advh_rollout_relevance")
         return rel
 
-    def attention_maps(self, waves, layer: int, head_fusion: Optional[str] = None, grad: bool = False, target=None):
+    def attention_maps(self, waves, layer: int, head_fusion: Optional[str] = None, grad: bool = False, target=None, lengths=None):
         """The attention maps of encoder layer ``layer`` (``0 <= layer < nl``), fp32, rows = queries: the probabilities
         ``A = softmax(Q K^T / sqrt(d))``, or with ``grad=True`` the gradient-weighted maps ``(dF/dA * A)^+`` of Chefer et al. 2021
         (``target``: None / 1 explains ``+F``, 0 ``-F``, ``"predicted"`` ``sign(F(x_b)) F``, or a ``[B]`` tensor of 0 / 1).
-        ``head_fusion=None``: ``[B, heads, T, T]``; ``"mean"`` / ``"max"`` / ``"min"`` reduce over heads: ``[B, T, T]``."""
+        ``head_fusion=None``: ``[B, heads, T, T]``; ``"mean"`` / ``"max"`` / ``"min"`` reduce over heads: ``[B, T, T]``.
+        ``lengths`` (a ``long_maps`` engine; one sample count per clip, ``EmbedderGrad.forward``): clip b is ``waves[b, :lengths[b]]``
+        and its map the one of that clip run alone, in the top-left ``T_b x T_b`` block, exactly 0 elsewhere."""
         l = self.check_attention_layer(layer)
         fuse = check_head_fusion(head_fusion)
-        B, _, T = self._attention_args(waves)
+        B, _, T = self._attention_args(waves, lengths)
         if not isinstance(grad, bool):
             raise ValueError(f"grad must be a bool, not {grad!r}")
         if target is not None and not grad:
             raise ValueError("target picks the explained output of the gradient-weighted maps: pass grad=True")
         spec = check_attention_target(target, B)
-        x = self._prep(waves)
+        x, lens, _ = self._attention_input(waves, lengths)
         if not grad:
-            self.eg.forward(x, to_layer=l + 1)
+            self.eg.forward(x, to_layer=l + 1, lengths=lens)
             return self._checked(self.eg.attention_probs(l, fuse), "attention map", "the forward pass produced a non-finite activation")
-        logits, _ = self.eg.forward(x)
+        logits, _ = self.eg.forward(x, lengths=lens)
         heads = self.eg.cfg.num_attention_heads
         out = torch.empty((1, B, T, T) if fuse else (1, B, heads, T, T), dtype=torch.float32, device=x.device)
         self.eg.backward(self.loss_scale, seed=self._target_seed(spec, logits), to_layer=l, attention_maps=(out, fuse))
         return self._checked(out[0], "attention map")
 
-    def attention_rollout(self, waves, head_fusion: str = "mean", start_layer: int = 0, return_joint: bool = False):
+    def attention_rollout(self, waves, head_fusion: str = "mean", start_layer: int = 0, return_joint: bool = False, lengths=None):
         """Attention rollout (Abnar & Zuidema 2020): ``R = I``; for ``l = start_layer .. nl-1`` with ``M`` the head-fused
         probabilities of layer ``l``, ``R <- rownorm(R + M R)`` (row ``i`` divided by ``1 + sum_k M[i,k]``; ``"mean"``: ``0.5 A +
         0.5 I``).  The classifier mean-pools over time: the per-frame relevance is ``rel[b, j] = (1/T) sum_i R[b, i, j]``,
-        ``[B, T]`` fp32, rows summing to 1 (``frames_to_wave`` spreads it to the samples).  ``return_joint``: ``(rel, R [B, T, T])``."""
+        ``[B, T]`` fp32, rows summing to 1 (``frames_to_wave`` spreads it to the samples).  ``return_joint``: ``(rel, R [B, T, T])``.
+        ``lengths`` (a ``long_maps`` engine): clip b is ``waves[b, :lengths[b]]``; ``R[b]`` is the cropped clip's in the top-left
+        ``T_b x T_b`` block and 0 elsewhere, ``rel[b, j]`` divides by ``T_b`` and is exactly 0 for ``j >= T_b``."""
         fuse = check_head_fusion(head_fusion, allow_none=False)
         s0 = self.check_attention_layer(start_layer, "start_layer")
-        B, _, T = self._attention_args(waves)
-        x = self._prep(waves)
-        self.eg.forward(x)
+        B, _, T = self._attention_args(waves, lengths)
+        x, lens, frames = self._attention_input(waves, lengths)
+        self.eg.forward(x, lengths=lens)
         R = torch.eye(T, dtype=torch.float32, device=x.device).expand(B, T, T).contiguous()
         Y = torch.empty_like(R)
         for l in range(s0, self.eg.emb.nl):
-            self._rollout_step(self.eg.attention_probs(l, fuse), R, Y, 1.0, 1.0, 0.0, True)
+            self._rollout_step(self.eg.attention_probs(l, fuse), R, Y, 1.0, 1.0, 0.0, True, frames)
             R, Y = Y, R
-        rel = self._checked(self._rollout_relevance(R), "attention rollout", "the forward pass produced a non-finite activation")
+        rel = self._checked(self._rollout_relevance(R, frames), "attention rollout", "the forward pass produced a non-finite activation")
         return (rel, R) if return_joint else rel
 
-    def attention_grad_rollout(self, waves, target=None, start_layer: int = 0, return_joint: bool = False):
+    def attention_grad_rollout(self, waves, target=None, start_layer: int = 0, return_joint: bool = False, lengths=None):
         """Gradient-weighted attention rollout (the self-attention rule of Chefer et al. 2021): ``Abar_l = mean_h (dF/dA_l^h *
         A_l^h)^+`` and ``R <- R + Abar_l R`` from ``R = I``, carried as ``D = R - I`` (``D <- D + Abar_l + Abar_l D`` from 0: the
         identity is never added and subtracted again).  One forward, one backward stopped at ``start_layer`` that writes every
         layer's map on its way.  ``rel[b, j] = (1/T) sum_i D[b, i, j]``, ``[B, T]`` fp32 -- without the identity, which would add a
-        constant ``1/T`` that dwarfs the relevance.  ``target`` as ``attention_maps``; ``return_joint``: ``(rel, D [B, T, T])``."""
+        constant ``1/T`` that dwarfs the relevance.  ``target`` as ``attention_maps``; ``return_joint``: ``(rel, D [B, T, T])``.
+        ``lengths``: as ``attention_rollout`` (``"predicted"`` takes the ragged forward's logit)."""
         s0 = self.check_attention_layer(start_layer, "start_layer")
-        B, _, T = self._attention_args(waves)
+        B, _, T = self._attention_args(waves, lengths)
         spec = check_attention_target(target, B)
-        x = self._prep(waves)
-        logits, _ = self.eg.forward(x)
+        x, lens, frames = self._attention_input(waves, lengths)
+        logits, _ = self.eg.forward(x, lengths=lens)
         nl = self.eg.emb.nl
         maps = torch.empty((nl - s0, B, T, T), dtype=torch.float32, device=x.device)
         self.eg.backward(self.loss_scale, seed=self._target_seed(spec, logits), to_layer=s0, attention_maps=(maps, 1))
         D = torch.zeros((B, T, T), dtype=torch.float32, device=x.device)
         Y = torch.empty_like(D)
         for l in range(s0, nl):
-            self._rollout_step(maps[l - s0], D, Y, 1.0, 1.0, 1.0, False)
+            self._rollout_step(maps[l - s0], D, Y, 1.0, 1.0, 1.0, False, frames)
             D, Y = Y, D
-        rel = self._checked(self._rollout_relevance(D), "attention gradient rollout")
+        rel = self._checked(self._rollout_relevance(D, frames), "attention gradient rollout")
         return (rel, D) if return_joint else rel
 
     # ------------------------------------------------------------------ conservative LRP for the transformer encoder
     # Ali et al., ICML 2022 (LN-rule, AH-rule) and the GELU identity rule of AttnLRP (Achtibat et al. 2024), restated from the
     # publications: Captum's LRP has no rule for LayerNorm, softmax attention or GELU, and the reference has no such method.
     def transformer_lrp(self, waves, target=None, start_layer: int = 0, ln_rule: bool = True, attention_rule: bool = True,
-                        gelu_rule: str = "gradient", return_hidden: bool = False):
+                        gelu_rule: str = "gradient", return_hidden: bool = False, lengths=None):
         """Conservative propagation through the encoder: gradient x input at ``x = hidden_states[start_layer]`` of ``F~``, the
         logit with -- in the layers ``>= start_layer`` and the final LayerNorm of a full-depth pre-LN model -- ``ln_rule``: every
         LayerNorm's ``1/sigma`` held constant (``LN(x) = gamma (x - mean(x)) / sg(sigma) + beta``); ``attention_rule``: the
@@ -2171,15 +2202,17 @@ class HipAttribution:
         and ``rel[b, t] = sum_h R[b, t, h]``, ``[B, T]`` fp32 (``frames_to_wave`` spreads it to the samples); ``return_hidden``:
         ``(rel, R [B, T, H])``.  With all three rules on ``x -> F~`` is affine: on a model without biases ``sum_t rel[b] = +-F(x_b)``.
         With all rules off it is ``layer_gradient_x_activation(waves, start_layer)`` summed over the channels.  ``target`` as
-        ``attention_maps``.  One forward, one backward stopped at ``start_layer`` (``EmbedderGrad.backward(rules=...)``)."""
+        ``attention_maps``.  One forward, one backward stopped at ``start_layer`` (``EmbedderGrad.backward(rules=...)``).
+        ``lengths`` (a ``long_maps`` engine): clip b is ``waves[b, :lengths[b]]``, its relevance that of the clip run alone and
+        exactly 0 on the frames ``t >= T_b``."""
         s0 = self.check_attention_layer(start_layer, "start_layer")
         rules = LrpRules(ln_rule, attention_rule, gelu_rule)
         if not isinstance(return_hidden, bool):
             raise ValueError(f"return_hidden must be a bool, not {return_hidden!r}")
-        B, _, T = self._attention_args(waves)
+        B, _, T = self._attention_args(waves, lengths)
         spec = check_attention_target(target, B)
-        x = self._prep(waves)
-        logits, _ = self.eg.forward(x)
+        x, lens, _ = self._attention_input(waves, lengths)
+        logits, _ = self.eg.forward(x, lengths=lens)
         g = self.eg.backward(self.loss_scale, seed=self._target_seed(spec, logits), to_layer=s0, rules=rules)
         H = g.shape[2]
         rel = torch.empty(B * T, dtype=torch.float32, device=x.device)

@@ -112,20 +112,31 @@ def check_chain_frames(emb: HipEmbedder, L: int, long_clips: bool = False) -> No
 
 class EmbedderGrad:
     long_clips = False          # the default chain refuses clips above 256 frames (check_chain_frames)
+    long_maps = False           # and attention_maps= / attention_probs / rules= above 256 frames or after a ragged pass
 
-    def __init__(self, emb: HipEmbedder, precision: Optional[str] = None, long_clips: bool = False):
+    def __init__(self, emb: HipEmbedder, precision: Optional[str] = None, long_clips: bool = False, long_maps: bool = False):
         """``precision``: None = the embedder's own ("f32": split-format chain; "f16": fp16 chain), or "f16" to run the fp16
         chain next to an fp32-class embedder (``HipEmbedder.f16_twin``).
         ``long_clips=True``: clips above 256 frames (82 319 samples) are taken -- there the attention runs on the streamed kernels,
         forward (advh_attention_long_*) and backward (advh_attention_bwd_long_*, both precisions on the fp32-input matrix
         instruction); ``seed``, ``to_layer``, ``from_layer``, ``forward_from`` and ``lengths=`` work as below that length, while
-        ``attention_maps=``, ``attention_probs`` and ``rules=`` keep the 256-frame limit of their ``T x T`` kernels.  At 256 frames
-        and below every launch is the default chain's."""
+        ``attention_maps=``, ``attention_probs`` and ``rules=`` keep the 256-frame limit of their ``T x T`` kernels unless
+        ``long_maps`` is set.  At 256 frames and below every launch is the default chain's.
+        ``long_maps=True`` (needs ``long_clips=True``): above 256 frames, and after a ragged pass (``forward(lengths=...)``) at
+        any length, ``attention_probs``, ``attention_maps=`` and ``rules=`` run the streamed kernels of
+        csrc/attention_maps_long.hip (advh_attention_maps_long, advh_attention_bwd_value_long); a clip of a ragged pass gets its
+        own map in the top-left ``T_b x T_b`` block and exact zeros elsewhere.  At 256 frames and below after a non-ragged pass
+        every launch is still the whole-clip one."""
         if precision not in (None, "f16", "f32"):
             raise ValueError("precision must be None, 'f16' or 'f32'")
         if not isinstance(long_clips, bool):
             raise ValueError(f"long_clips must be a bool, not {long_clips!r}")
+        if not isinstance(long_maps, bool):
+            raise ValueError(f"long_maps must be a bool, not {long_maps!r}")
+        if long_maps and not long_clips:
+            raise ValueError("long_maps=True needs long_clips=True: the maps of a long clip come from the long gradient chain's saves")
         self.long_clips = long_clips
+        self.long_maps = long_maps
         if precision == "f16":
             emb = emb.f16_twin()
         elif precision == "f32" and not emb.split:
@@ -244,7 +255,9 @@ class EmbedderGrad:
         ``b`` is ``wave[b, :lengths[b]]``, what lies behind is padding of any content, and everything this pass and the
         ``backward`` after it return for the clip is what they return for that clip run alone, unpadded: logits pooled over its
         own ``T_b = frame_lengths(lengths)[b]`` frames, ``to_layer`` hidden states with rows ``t >= T_b`` zero, ``dx[b, lengths[b]:]``
-        and layer gradients on rows ``t >= T_b`` exactly 0.  Workspace and plans are those of the padded ``(B, L)`` call."""
+        and layer gradients on rows ``t >= T_b`` exactly 0.  Workspace and plans are those of the padded ``(B, L)`` call.
+        After a ragged pass ``forward_from`` raises, and ``attention_probs``, ``backward(attention_maps=...)`` and
+        ``backward(rules=...)`` raise unless the chain has ``long_maps=True``."""
         lens = None
         if lengths is not None:                            # host checks, before any allocation, plan or launch
             if length is not None:
@@ -525,13 +538,31 @@ class EmbedderGrad:
 
     def _refuse_maps_above_limit(self, what: str) -> None:
         """``attention_maps=``, ``attention_probs`` and ``rules=`` run ``T x T`` kernels (csrc/attention_maps.hip, lrp.hip) that hold
-        a whole clip: ``AdvhError`` when the last pass had more frames, before any launch or allocation.  Host only."""
+        a whole clip: ``AdvhError`` when the last pass had more frames, before any launch or allocation, unless the chain was
+        built with ``long_maps=True`` (the streamed kernels of csrc/attention_maps_long.hip).  Host only."""
+        if self.long_maps:
+            return
         L = self._last[3]
         T = self.emb._lengths(int(L))[-1]
         if T > self.emb.WHOLE_CLIP_MAX_FRAMES:
             raise _lib.AdvhError(f"{what}: ADVH_EUNSUPPORTED: the T x T attention kernels behind it are held for T <= "
                                  f"{self.emb.WHOLE_CLIP_MAX_FRAMES} frames ({self.emb.whole_clip_max_samples()} samples) and the last pass "
-                                 f"had T = {T} ({int(L)} samples); long_clips lifts the limit of the gradient alone")
+                                 f"had T = {T} ({int(L)} samples); long_clips lifts the limit of the gradient alone, and a chain built "
+                                 "with long_maps=True (EmbedderGrad, HipAttribution; ADDVISOR_LONG_MAPS=1 for the runtime singleton) "
+                                 "lifts this one")
+
+    def _streamed_maps(self, T: int) -> bool:
+        """Whether ``attention_probs`` / ``attention_maps=`` / the AH-rule of the last pass run the streamed kernels: a
+        ``long_maps`` chain above 256 frames or after a ragged pass."""
+        return self.long_maps and (T > self.emb.WHOLE_CLIP_MAX_FRAMES or self._rag is not None)
+
+    def _att_stats(self, w: dict, B: int, T: int) -> torch.Tensor:
+        """The streamed kernels' ``(m, 1/l)`` workspace: ``w["att_stats"]`` of the long chain, allocated here for a ragged pass
+        at 256 frames and below."""
+        if "att_stats" not in w:
+            nb = _lib.lib().advh_attention_bwd_long_ws_bytes(B, T, self.cfg.num_attention_heads)
+            w["att_stats"] = torch.empty(nb // 4, dtype=torch.float32, device=self.dev)
+        return w["att_stats"]
 
     def _zero_tail(self, g32, g16, rag, B, T, H, st):
         """Rows ``t >= T_b`` of a residual-stream gradient = 0: the fp32 buffer and its fp16 / plane-pair copy."""
@@ -574,18 +605,34 @@ class EmbedderGrad:
         _lib.check(_lib.lib().advh_attention_maps(qkv.data_ptr(), lo(qkv), None if dctx is None else dctx.data_ptr(), lo(dctx), dscale,
                                                   fuse, out.data_ptr(), B, T, H, heads, st), "advh_attention_maps")
 
+    def _att_maps_long(self, qkv, dctx, out, fuse, dscale, stats, frames, B, T, H, heads, st):
+        """advh_attention_maps_long: ``_att_maps`` for any ``T`` and per-clip ``frames`` (int32 [B] on the device, or None)."""
+        lo = lambda t: t.stride(0) if (self.split and t is not None) else 0
+        _lib.check(_lib.lib().advh_attention_maps_long(qkv.data_ptr(), lo(qkv), None if dctx is None else dctx.data_ptr(), lo(dctx), dscale,
+                                                       fuse, out.data_ptr(), stats.data_ptr(), None if frames is None else frames.data_ptr(),
+                                                       B, T, H, heads, st), "advh_attention_maps_long")
+
+    def _att_bwd_value_long(self, qkv, dctx, dqkv, stats, frames, B, T, H, heads, st):
+        """advh_attention_bwd_value_long: ``_att_bwd_value`` for any ``T`` and per-clip ``frames``."""
+        lo = lambda t: t.stride(0) if self.split else 0
+        _lib.check(_lib.lib().advh_attention_bwd_value_long(qkv.data_ptr(), lo(qkv), dctx.data_ptr(), lo(dctx), dqkv.data_ptr(), lo(dqkv),
+                                                            stats.data_ptr(), None if frames is None else frames.data_ptr(), B, T, H, heads,
+                                                            st), "advh_attention_bwd_value_long")
+
     def attention_probs(self, layer: int, fuse: int = 0) -> torch.Tensor:
         """The attention probabilities ``softmax(Q K^T / sqrt(d))`` of encoder layer ``layer`` (``0 <= layer < nl``) at the clips
         of the last pass, recomputed from its saved ``qkv`` (read-only: no state of the chain changes): ``[B, heads, T, T]``
-        fp32 (``fuse=0``) or fused over heads, ``[B, T, T]`` (``fuse`` 1 mean, 2 max, 3 min), rows = queries."""
+        fp32 (``fuse=0``) or fused over heads, ``[B, T, T]`` (``fuse`` 1 mean, 2 max, 3 min), rows = queries.  On a ``long_maps``
+        chain after a ragged pass clip ``b``'s map is that of the clip alone in the top-left ``T_b x T_b`` block, 0 elsewhere."""
         l = check_layer(layer, self.emb.nl - 1)
         if fuse not in (0, 1, 2, 3):
             raise ValueError("fuse must be 0 (none), 1 (mean), 2 (max) or 3 (min)")
         if getattr(self, "_last", None) is None:
             raise RuntimeError("attention_probs() needs a forward pass first")
         self._refuse_maps_above_limit("EmbedderGrad.attention_probs")
-        if self._rag is not None:
-            raise ValueError("the last pass was ragged (forward(lengths=...)): attention maps take no per-clip lengths")
+        if self._rag is not None and not self.long_maps:
+            raise ValueError("the last pass was ragged (forward(lengths=...)): attention maps take no per-clip lengths "
+                             "(a chain built with long_maps=True takes them)")
         if self._start is not None and l < self._start:
             raise ValueError(f"the last pass started at layer {self._start}: layer {l}'s attention did not run")
         if self._stop is not None and l >= self._stop:
@@ -594,7 +641,12 @@ class EmbedderGrad:
         w = self._workspace(B, L)
         T, H, heads = w["f"]["T"], self.cfg.hidden_size, self.cfg.num_attention_heads
         out = torch.empty((B, T, T) if fuse else (B, heads, T, T), dtype=torch.float32, device=self.dev)
-        self._att_maps(w["qkv"][l], None, out, fuse, 1.0, B, T, H, heads, torch.cuda.current_stream().cuda_stream)
+        st = torch.cuda.current_stream().cuda_stream
+        if self._streamed_maps(T):
+            self._att_maps_long(w["qkv"][l], None, out, fuse, 1.0, self._att_stats(w, B, T), None if self._rag is None else self._rag[1],
+                                B, T, H, heads, st)
+        else:
+            self._att_maps(w["qkv"][l], None, out, fuse, 1.0, B, T, H, heads, st)
         return out
 
     def neuron_values(self, v: torch.Tensor, box) -> torch.Tensor:
@@ -659,7 +711,10 @@ class EmbedderGrad:
         ``ln``: the LayerNorm backwards hold ``1/sigma`` constant; ``attention``: the attention backward holds the probabilities
         constant (``dV = P^T dO``, ``dQ = dK = 0``); ``gelu="identity"``: the FFN's GELU backward multiplies by ``Phi(g1)``
         instead of ``GELU'(g1)``.  The chain below the encoder has no rules: ``to_layer`` is required, and ``rules`` does not
-        combine with ``from_layer`` (ValueError before any launch).  It combines with ``attention_maps``, which only reads."""
+        combine with ``from_layer`` (ValueError before any launch).  It combines with ``attention_maps``, which only reads.
+        Both stop at 256 frames and refuse a ragged pass unless the chain has ``long_maps=True``: then, above 256 frames or after
+        ``forward(lengths=...)``, the maps come from advh_attention_maps_long (clip ``b``'s in the top-left ``T_b x T_b`` block, 0
+        elsewhere) and the attention rule runs advh_attention_bwd_value_long (csrc/attention_maps_long.hip)."""
         if rules is not None:
             if not isinstance(rules, LrpRules):
                 raise ValueError(f"rules must be an LrpRules or None, not {rules!r}")
@@ -674,9 +729,9 @@ class EmbedderGrad:
         if attention_maps is not None or rules is not None:    # before any launch or allocation
             self._refuse_maps_above_limit("EmbedderGrad.backward(attention_maps=...)" if rules is None else "EmbedderGrad.backward(rules=...)")
         rag = self._rag
-        if rag is not None and (attention_maps is not None or rules is not None):
+        if rag is not None and (attention_maps is not None or rules is not None) and not self.long_maps:
             raise ValueError("the last pass was ragged (forward(lengths=...)): backward takes neither attention_maps nor rules "
-                             "after it (they have no per-clip lengths)")
+                             "after it (they have no per-clip lengths; a chain built with long_maps=True takes both)")
         _w = self._workspace(self._last[1], self._last[3])["f"]
         top, box = self._seed_args(self._last[1], _w["T"], self.cfg.hidden_size, seed, to_layer, from_layer, neuron, layer_seed, row_scale)
         if from_layer is None and self._stop is not None:
@@ -738,9 +793,18 @@ class EmbedderGrad:
         # the rules swap a launch for its conservative form (csrc/lrp.hip); rules=None is the plain chain, launch for launch
         ln_bwd = self._ln_bwd_frozen if (rules is not None and rules.ln) else self._ln_bwd
         att_bwd = self._att_bwd_value if (rules is not None and rules.attention) else self._att_bwd
-        if T > emb.WHOLE_CLIP_MAX_FRAMES:                  # long_clips; rules were refused above
+        att_maps = self._att_maps
+        frames = None if rag is None else rag[1]
+        streamed = self._streamed_maps(T)                  # long_maps: above 256 frames or after a ragged pass
+        if streamed and maps is not None:
+            att_maps = lambda qkv, dctx, out, fuse_, ds, B_, T_, H_, heads_, st_: self._att_maps_long(
+                qkv, dctx, out, fuse_, ds, self._att_stats(w, B, T), frames, B_, T_, H_, heads_, st_)
+        if streamed and rules is not None and rules.attention:                 # the AH-rule, streamed
+            att_bwd = lambda qkv, dctx, dqkv, B_, T_, H_, heads_, st_: self._att_bwd_value_long(
+                qkv, dctx, dqkv, self._att_stats(w, B, T), frames, B_, T_, H_, heads_, st_)
+        elif T > emb.WHOLE_CLIP_MAX_FRAMES:                # long_clips; without long_maps rules were refused above
             att_bwd = lambda qkv, dctx, dqkv, B_, T_, H_, heads_, st_: self._att_bwd_long(
-                qkv, dctx, dqkv, w["att_stats"], None if rag is None else rag[1], B_, T_, H_, heads_, st_)
+                qkv, dctx, dqkv, w["att_stats"], frames, B_, T_, H_, heads_, st_)
         elif rag is not None:                              # rows past a clip's frames: never read, written as zeros
             att_bwd = lambda qkv, dctx, dqkv, B_, T_, H_, heads_, st_: self._att_bwd_ragged(qkv, dctx, dqkv, rag[1], B_, T_, H_, heads_, st_)
         gelu_id = rules is not None and rules.gelu == "identity"
@@ -762,7 +826,7 @@ class EmbedderGrad:
                 ln_bwd(emb.ln2[l], w["m"][l], t16, M, out_f=db, out_h=d16, add=da)            # db = d m
                 bl["out"].run(d16, out_h=w["dctx"])
                 if maps is not None and l - stop < maps.shape[0]:
-                    self._att_maps(w["qkv"][l], w["dctx"], maps[l - stop], fuse, 1.0 / loss_scale, B, T, H, heads, st)
+                    att_maps(w["qkv"][l], w["dctx"], maps[l - stop], fuse, 1.0 / loss_scale, B, T, H, heads, st)
                 att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
                 bl["qkv"].run(w["dqkv"], out_h=t16)                                           # d LN1(x_l)
                 ln_bwd(emb.ln1[l], w["x"][l], t16, M, out_f=da, out_h=d16, add=db)            # da = d x_l
@@ -773,7 +837,7 @@ class EmbedderGrad:
                 ln_bwd(emb.ln1[l], w["s1"][l], da, M, out_f=db, out_h=d16)                    # db = d s1
                 bl["out"].run(d16, out_h=w["dctx"])
                 if maps is not None and l - stop < maps.shape[0]:
-                    self._att_maps(w["qkv"][l], w["dctx"], maps[l - stop], fuse, 1.0 / loss_scale, B, T, H, heads, st)
+                    att_maps(w["qkv"][l], w["dctx"], maps[l - stop], fuse, 1.0 / loss_scale, B, T, H, heads, st)
                 att_bwd(w["qkv"][l], w["dctx"], w["dqkv"], B, T, H, heads, st)
                 bl["qkv"].run(w["dqkv"], out_f=da, resid=db)                                  # da = d x_l
         if to_layer is not None:                                                              # da = d hidden_states[stop]

@@ -11,6 +11,8 @@ default, since none of those artefacts exist offline -- from the seeded syntheti
     ADDVISOR_LAYER_INDEX  hidden-state index returned by extract_features            (default 9)
     ADDVISOR_PRECISION    f32 (default: fp32-class split-format kernels, the reference's arithmetic class) | f16
     ADDVISOR_LONG_CLIPS   1: the gradient chain takes clips above 256 frames (EmbedderGrad(long_clips=True))   (default 0)
+    ADDVISOR_LONG_MAPS    1: so do attention maps, rollout and LRP, which also take per-clip lengths
+                          (EmbedderGrad(long_maps=True); needs ADDVISOR_LONG_CLIPS=1)                           (default 0)
 """
 from __future__ import annotations
 
@@ -107,19 +109,29 @@ def hip_embedder():
     return _state["hip_emb"]
 
 
+def _env_flag(name: str) -> bool:
+    v = os.environ.get(name, "0").strip().lower()
+    if v not in ("0", "1", "", "false", "true"):
+        raise ValueError(f"{name} must be 0 or 1, not {v!r}")
+    return v in ("1", "true")
+
+
 def long_clips() -> bool:
     """ADDVISOR_LONG_CLIPS, read when the gradient-chain singleton is built (after ``reset()``: again)."""
-    v = os.environ.get("ADDVISOR_LONG_CLIPS", "0").strip().lower()
-    if v not in ("0", "1", "", "false", "true"):
-        raise ValueError(f"ADDVISOR_LONG_CLIPS must be 0 or 1, not {v!r}")
-    return v in ("1", "true")
+    return _env_flag("ADDVISOR_LONG_CLIPS")
+
+
+def long_maps() -> bool:
+    """ADDVISOR_LONG_MAPS, read with ADDVISOR_LONG_CLIPS (which it needs: ``EmbedderGrad`` raises ValueError otherwise)."""
+    return _env_flag("ADDVISOR_LONG_MAPS")
 
 
 def hip_embedder_grad():
     """Forward-with-saves + input-gradient engine on the HIP embedder singleton (LMACLoss backward, attributions)."""
     if "hip_eg" not in _state:
         from .embedder_grad import EmbedderGrad
-        _state["hip_eg"] = EmbedderGrad(hip_embedder(), long_clips=long_clips())
+        kw = dict(long_maps=True) if long_maps() else {}       # the keyword only when the variable is set
+        _state["hip_eg"] = EmbedderGrad(hip_embedder(), long_clips=long_clips(), **kw)
     return _state["hip_eg"]
 
 

@@ -70,7 +70,12 @@ class Wav2vec2LogReg(nn.Module):
     def hip_attribution(self):
         if self._att is None:
             from addvisor_hip.attribution import HipAttribution
-            self._att = HipAttribution(_rt.hip_embedder())
+            kw = {}                                            # ADDVISOR_LONG_CLIPS / ADDVISOR_LONG_MAPS, as the runtime's singleton reads them
+            if _rt.long_clips():
+                kw["long_clips"] = True
+            if _rt.long_maps():
+                kw["long_maps"] = True
+            self._att = HipAttribution(_rt.hip_embedder(), **kw)
         return self._att
 
     def hip_robust(self):

@@ -35,6 +35,7 @@ int advh_split_flag_conv_taps2d_head_x3(int* flag);
 int advh_split_flag_upconv_tile_x3(int* flag);
 int advh_split_flag_conv_s21_tile_x3(int* flag);
 int advh_split_flag_lrp(int* flag);
+int advh_split_flag_attention_maps_long(int* flag);   // attention_maps_long.hip: advh_ensure_lds per launch, no init function
 
 // attention backward of the fp32-class mode: the split-arithmetic kernel for head dims <= 64 (attention_bwd_x3.hip), called by
 // advh_attention_bwd_split (attention_bwd_f32.hip) after it validated the arguments; g_att_bwd_force_f32: advh_set_option("attention_bwd_mfma_f32")
