@@ -1357,7 +1357,7 @@ int advh_zero_tail_rows(float* x, const int32_t* frames, int B, int T, int H, ad
 int advh_pool_logreg_ragged(const float* h, const float* coef, float intercept, float* logit, float* prob, float* pooled,
                             const int32_t* frames, int B, int T, int H, advh_stream_t stream);
 
-/* ---- ragged batches: the gradient chain (csrc/attention_bwd_ragged.hip, backward_ragged.hip) -----------------------------
+/* ---- ragged batches: the gradient chain (csrc/backward.hip, attention_bwd_x3.hip, attention_bwd_f32.hip, frontend_bwd.hip) -
  * The backward of the ragged forward above, same definition: what the chain returns for clip b is what the batch form returns
  * for wave[b, :lens[b]] run alone.  `lens` / `frames` are the int32 [B] device arrays of the forward, clamped in every kernel.
  * The row-wise launches of the chain (dgrad GEMMs without bias, LayerNorm backward, the feature encoder's dgrad) need no ragged

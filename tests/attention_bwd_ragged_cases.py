@@ -1,27 +1,29 @@
-"""Cases of tests/test_gpu_attention_bwd_ragged.py and the mirror of the host dispatch of csrc/attention_bwd_ragged.hip
-(advh_attention_bwd_f16_ragged, advh_attention_bwd_split_ragged), free of GPU imports so that
-tests/test_build_resources_attention_bwd_ragged.py can hold the cases against the compiled instances.
+"""Cases of tests/test_gpu_attention_bwd_ragged.py and the mirror of the host dispatch of advh_attention_bwd_f16_ragged
+(csrc/backward.hip) and advh_attention_bwd_split_ragged (csrc/attention_bwd_f32.hip, csrc/attention_bwd_x3.hip), free of GPU
+imports so that tests/test_build_resources_attention_bwd_ragged.py can hold the cases against the compiled instances.
 
-The ragged entry points pick their kernel by the row STRIDE T exactly as the siblings do by T, so the mirror is
-backward_kernel_cases.instance_of with the kernel renamed."""
+The ragged kernels are the RAGGED = true instances of the batch kernels' templates (the siblings: the same template arguments
+with RAGGED = false), and the ragged entry points pick theirs by the row STRIDE T exactly as the batch ones do by T, so the
+mirror is backward_kernel_cases.instance_of with the last argument set."""
 import backward_kernel_cases as K
 
 ENTRIES = K.ENTRIES                                       # "f16" | "split" | "split_f32" (attention_bwd_mfma_f32 = 1)
 STRIDES = (16, 64, 65, 128, 129, 208, 209, 256)           # both edges of every tile-count class, in whole strides
 HEAD_DIMS = (24, 56, 64, 120)                             # D = 32, 64 (padded), 64 (exact: the transposing-read path), 128
 B, HEADS = 3, 2
-SIBLING = {"attention_bwd_ragged_kernel": "attention_bwd_kernel", "attention_bwd_x3_ragged_kernel": "attention_bwd_x3_kernel",
-           "attention_bwd_f32_ragged_kernel": "attention_bwd_f32_kernel"}
-RAGGED = {v: k for k, v in SIBLING.items()}
 SOURCES = {"attention_bwd_kernel": "backward.hip", "attention_bwd_x3_kernel": "attention_bwd_x3.hip",
            "attention_bwd_f32_kernel": "attention_bwd_f32.hip"}
 CLASSES = {4: (16, 64), 8: (65, 128), 13: (129, 208), 16: (209, 256)}
 
 
 def instance_of(entry, T, dm):
-    """(kernel, NT, D, TR | NW) launched for row stride ``T`` and head dim ``dm``."""
-    inst = K.instance_of("f16" if entry == "f16" else "split", T, dm, entry == "split_f32")
-    return (RAGGED[inst[0]],) + inst[1:]
+    """(kernel, NT, D, TR | NW, True) launched for row stride ``T`` and head dim ``dm``."""
+    return K.instance_of("f16" if entry == "f16" else "split", T, dm, entry == "split_f32", ragged=True)
+
+
+def sibling(inst):
+    """The batch instance of the same template arguments."""
+    return inst[:-1] + (False,)
 
 
 def middle(T):

@@ -17,22 +17,23 @@ T_EDGES = (1, 16, 17, 64, 65, 128, 129, 208, 209, 256)      # both edges of ever
 HEAD_DIMS = (8, 24, 32, 40, 56, 64, 72, 120, 128)           # per padded width D = 32 | 64 | 128: two padded head dims and the exact one
 
 
-def instance_of(entry, T, dm, forced_f32=False):
-    """(kernel, NT, D, TR | NW) the host code launches for this shape."""
+def instance_of(entry, T, dm, forced_f32=False, ragged=False):
+    """(kernel, NT, D, TR | NW, RAGGED) the host code launches for this shape; ``ragged``: the entry point with per-clip frames,
+    which picks by the row stride T as the batch entry point does by T."""
     nt = (T + 15) // 16
     D = 32 if dm <= 32 else (64 if dm <= 64 else 128)
     cls = 4 if nt <= 4 else (8 if nt <= 8 else (13 if nt <= 13 else 16))
     if entry == "f16":
         if D == 128 and cls == 8:
             cls = 13                                               # head dim 128 has no 8-tile instance
-        return ("attention_bwd_kernel", cls, D, dm == 64)
+        return ("attention_bwd_kernel", cls, D, dm == 64, ragged)
     if dm <= 64 and not forced_f32:
-        return ("attention_bwd_x3_kernel", cls, D, 4 if cls == 16 else 8)
-    return ("attention_bwd_f32_kernel", cls, D, 8 if D <= 64 else 4)
+        return ("attention_bwd_x3_kernel", cls, D, 4 if cls == 16 else 8, ragged)
+    return ("attention_bwd_f32_kernel", cls, D, 8 if D <= 64 else 4, ragged)
 
 
 def refused_f16(T, dm):
-    """advh_attention_bwd_f16 refuses head dims above 64 with more than 13 key tiles: attention_bwd_kernel<16, 128, false>
+    """advh_attention_bwd_f16 refuses head dims above 64 with more than 13 key tiles: attention_bwd_kernel<16, 128, false, *>
     would need 2 * 128 * 320 * 2 + 3 * 256 * 4 = 166 912 bytes of LDS, above the CU's 160 KiB."""
     return dm > 64 and T > 208
 

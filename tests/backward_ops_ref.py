@@ -39,11 +39,11 @@ def _r16(t, on):
 def attention_bwd_f16_model(q, k, v, dO, rounding=True):
     """Gradients of ``softmax(q k^T / sqrt(d)) v`` on [..., T, d] given dO, in float64, with operands rounded to fp16 exactly
     where ``attention_bwd_kernel`` (csrc/backward.hip) rounds them:
-      * P = softmax(S) and delta = rowsum(P * dP) stay fp32 there (backward.hip:244-265): not rounded here;
-      * dS * scale = P (dP - delta) scale is converted to fp16 before dQ = dS K (backward.hip:272-275) and before
-        dK = dS^T Q (backward.hip:365, 368);
-      * P is converted to fp16 before dV = P^T dO (backward.hip:363-367);
-      * dQ (backward.hip:302), dK and dV (backward.hip:396-397) are stored as fp16.
+      * P = softmax(S) and delta = rowsum(P * dP) stay fp32 there (backward.hip:254-275): not rounded here;
+      * dS * scale = P (dP - delta) scale is converted to fp16 before dQ = dS K (backward.hip:282-285) and before
+        dK = dS^T Q (backward.hip:375, 378);
+      * P is converted to fp16 before dV = P^T dO (backward.hip:373-377);
+      * dQ (backward.hip:312), dK and dV (backward.hip:406-407) are stored as fp16.
     Returns a dict: dq, dk, dv (rounded), p, ds (``dS * scale`` before its rounding) and dq_pre / dk_pre / dv_pre, the
     fp64 sums in front of the output conversion.  ``rounding=False`` is the plain restatement."""
     q, k, v, dO = q.double(), k.double(), v.double(), dO.double()

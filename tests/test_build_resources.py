@@ -58,6 +58,6 @@ def test_attention_and_resblock_kernels_do_not_spill():
     # whole register file (four wavefronts) it measured 392 us against 293 us (profiles/r03_attention_bwd_x3.txt)
     res = resources("attention_bwd_x3.hip")
     hit = {k: v for k, v in res.items() if "attention_bwd_x3_kernel" in k}
-    assert len(hit) == 8, sorted(res)
+    assert len(hit) == 16, sorted(res)                     # eight instances, each for a batch and for a ragged batch (RAGGED)
     for k, v in hit.items():
         assert v["scratch"] <= (96 if "ILi13ELi64ELi8E" in k else 0), (k, v)

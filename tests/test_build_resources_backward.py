@@ -21,17 +21,19 @@ def instances(src, kernel):
 
 
 def test_every_attention_bwd_instance_has_a_case():
-    compiled = (instances("backward.hip", "attention_bwd_kernel") | instances("attention_bwd_x3.hip", "attention_bwd_x3_kernel")
-                | instances("attention_bwd_f32.hip", "attention_bwd_f32_kernel"))
-    assert len(compiled) == 15 + 8 + 12, sorted(compiled)
+    sets = [instances("backward.hip", "attention_bwd_kernel"), instances("attention_bwd_x3.hip", "attention_bwd_x3_kernel"),
+            instances("attention_bwd_f32.hip", "attention_bwd_f32_kernel")]
+    # the last template argument is RAGGED: the batch set here, the ragged one in tests/test_build_resources_attention_bwd_ragged.py
+    assert [sum(not i[-1] for i in s) for s in sets] == [15, 8, 12], [sorted(s) for s in sets]
+    compiled = {i for s in sets for i in s if not i[-1]}
     selected = K.att_selected()
     refused = {K.instance_of("f16", T, dm) for T, dm in K.REFUSED_CASES}
-    assert refused == {("attention_bwd_kernel", 16, 128, False)}           # compiled, but its LDS need is above 160 KiB: never launched
+    assert refused == {("attention_bwd_kernel", 16, 128, False, False)}    # compiled, but its LDS need is above 160 KiB: never launched
     assert all(K.refused_f16(T, dm) for T, dm in K.REFUSED_CASES)
     assert not refused & set(selected)
     assert set(selected) | refused == compiled, (sorted(compiled - set(selected) - refused), sorted(set(selected) - compiled))
     for inst, cases in selected.items():
-        kernel, NT, D, last = inst
+        kernel, NT, D, last, _ = inst
         lo, hi = {4: (1, 64), 8: (65, 128), 13: (129, 208), 16: (209, 256)}[NT]
         if kernel == "attention_bwd_kernel" and D == 128 and NT == 13:
             lo = 65                                                         # head dim 128 has no 8-tile instance

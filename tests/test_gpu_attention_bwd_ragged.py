@@ -1,4 +1,5 @@
-"""Kernel-level suite of the ragged attention backward (csrc/attention_bwd_ragged.hip): every compiled instance at strides at both
+"""Kernel-level suite of the ragged attention backward (the RAGGED instances of csrc/backward.hip, attention_bwd_x3.hip and
+attention_bwd_f32.hip; the siblings are the batch instances of the same template arguments): every compiled instance at strides at both
 edges of its tile-count class, three clips with ``frames = (T, 1, m)`` (``m % 16 == 1``: one frame into a tile), two heads.
 
 Setup: NaN in the rows of qkv and dctx past ``frames[b]``, dqkv prefilled with NaN, NaN guard rows in front of and behind it.

@@ -1,4 +1,4 @@
-"""Kernel-level suite of the row and waveform-end kernels of the ragged gradient chain (csrc/backward_ragged.hip):
+"""Kernel-level suite of the row and waveform-end kernels of the ragged gradient chain (csrc/backward.hip, csrc/frontend_bwd.hip):
 advh_pool_logreg_bwd_ragged / _split_ragged, advh_zero_tail_rows_h, advh_w2v2_frontend_bwd_group_ragged / _split_ragged and
 advh_wave_bwd_ragged, each against a float64 restatement on every clip CROPPED to its length (autograd through
 tests/embedder_ops_ref.py for the two front-end kernels), bit-identical to its sibling at full lengths, and with NaN in every

@@ -1,5 +1,5 @@
-"""Kernel-level suite of the ragged row kernels: the waveform front end with per-clip lengths (csrc/frontend_ragged.hip), the
-tail zeroing and the pool + logistic head over each clip's valid frames (csrc/rows_ragged.hip), against the float64
+"""Kernel-level suite of the ragged row kernels: the waveform front end with per-clip lengths (csrc/frontend.hip), the
+tail zeroing and the pool + logistic head over each clip's valid frames (csrc/rowops.hip), against the float64
 ``tests/embedder_ops_ref.py`` evaluated on each clip CROPPED to its length.  Samples / rows past a clip's length are NaN, so a
 kernel that reads one for its value fails.  Bars: those of the sibling kernels' suites (tests/test_gpu_frontend.py check_rows and
 check_saved's statistics terms, tests/test_gpu_rowops.py test_pool_logreg), 5e-6 of the clip's largest value for fp32 and

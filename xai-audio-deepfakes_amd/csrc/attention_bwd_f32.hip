@@ -28,6 +28,7 @@
 #include "common.h"
 #include "device_math.h"
 #include "attention_f32_tiles.h"
+#include "ragged_clip.h"
 
 namespace advh {
 
@@ -42,10 +43,12 @@ struct AttBwdF32 {
 // NW wavefronts per workgroup: 8 (two per SIMD, <= 256 VGPRs each) where the register budget allows -- head dims <= 64 --, so that
 // one wavefront's LDS / global latency and MFMA dependency stalls are covered by the other's issue (one workgroup per CU: the
 // staged matrices take most of the LDS); 4 for head dim 128.
-template <int NT, int D, int NW>
+// RAGGED (advh_attention_bwd_split_ragged): Ts is the clip stride, T = clamp(frames[b], 1, Ts) the bound, rows [T, Ts) of this
+// head's dq | dk | dv are zeroed first, in both planes -- the contract written out at attention_bwd_kernel (backward.hip).
+template <int NT, int D, int NW, bool RAGGED>
 __global__ __launch_bounds__(64 * NW) void attention_bwd_f32_kernel(const _Float16* __restrict__ qkv, long qkv_lo, const _Float16* __restrict__ dctx,
-                                                                long dctx_lo, _Float16* __restrict__ dqkv, long dqkv_lo, int T, int H, int dm,
-                                                                float scale) {
+                                                                long dctx_lo, _Float16* __restrict__ dqkv, long dqkv_lo, int Ts, int H, int dm,
+                                                                float scale, const int* __restrict__ frames) {
     typedef AttBwdF32<NT, D> G;
     constexpr int NKEY = G::NKEY, PITCH = G::PITCH, DG = G::DG;
     constexpr bool TWO = G::TWO;
@@ -59,10 +62,13 @@ __global__ __launch_bounds__(64 * NW) void attention_bwd_f32_kernel(const _Float
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int fr = lane & 15, g = lane >> 4;
     const int head = blockIdx.x, b = blockIdx.y;
+    int T = Ts;                                                          // the bound; Ts is the clip stride
+    if constexpr (RAGGED) T = clip_frames(frames, b, Ts);
     const long ld = 3L * H;
-    const _Float16* base = qkv + (long)b * T * ld + head * dm;           // q at +0, k at +H, v at +2H
-    const _Float16* dob = dctx + (long)b * T * H + head * dm;
-    _Float16* dbase = dqkv + (long)b * T * ld + head * dm;
+    const _Float16* base = qkv + (long)b * Ts * ld + head * dm;          // q at +0, k at +H, v at +2H
+    const _Float16* dob = dctx + (long)b * Ts * H + head * dm;
+    _Float16* dbase = dqkv + (long)b * Ts * ld + head * dm;
+    if constexpr (RAGGED) zero_tail<64 * NW>(dbase, dqkv_lo, ld, H, T, Ts, dm, tid);
     const float c2 = scale * LOG2E;
 
     stage_f32<NKEY, D, 64 * NW>(M0, base + H, qkv_lo, ld, T, dm, tid);
@@ -259,37 +265,26 @@ __global__ __launch_bounds__(64 * NW) void attention_bwd_f32_kernel(const _Float
     }
 }
 
-template <int NT, int D>
-static int launch_att_bwd_f32(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, int B, int T, int H,
-                              int heads, int dm, float scale, hipStream_t s) {
+template <int NT, int D, bool RAGGED>
+static int launch_att_bwd_f32(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, const int* frames,
+                              int B, int T, int H, int heads, int dm, float scale, hipStream_t s) {
     constexpr int lds = AttBwdF32<NT, D>::LDS_BYTES;
     static_assert(lds <= 160 * 1024, "one staged matrix must fit");
     constexpr int NW = D <= 64 ? 8 : 4;
-    if (advh_ensure_lds((const void*)attention_bwd_f32_kernel<NT, D, NW>) != ADVH_OK) return ADVH_ELAUNCH;
-    hipLaunchKernelGGL((attention_bwd_f32_kernel<NT, D, NW>), dim3(heads, B), dim3(64 * NW), lds, s, (const _Float16*)qkv, qkv_lo,
-                       (const _Float16*)dctx, dctx_lo, (_Float16*)dqkv, dqkv_lo, T, H, dm, scale);
+    if (advh_ensure_lds((const void*)attention_bwd_f32_kernel<NT, D, NW, RAGGED>) != ADVH_OK) return ADVH_ELAUNCH;
+    hipLaunchKernelGGL((attention_bwd_f32_kernel<NT, D, NW, RAGGED>), dim3(heads, B), dim3(64 * NW), lds, s, (const _Float16*)qkv, qkv_lo,
+                       (const _Float16*)dctx, dctx_lo, (_Float16*)dqkv, dqkv_lo, T, H, dm, scale, frames);
     return ADVH_LAUNCH_CHECK();
 }
 
-}  // namespace advh
-
-using namespace advh;
-
-int g_att_bwd_force_f32 = 0;
-
-extern "C" int advh_attention_bwd_split(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, void* dqkv, int64_t dqkv_lo,
-                                        int B, int T, int H, int heads, advh_stream_t stream) {
-    if (!qkv || !dctx || !dqkv || B <= 0 || T <= 0 || heads <= 0 || H % heads) return ADVH_EINVAL;
-    if (qkv_lo <= 0 || dctx_lo <= 0 || dqkv_lo <= 0 || qkv_lo % 8 || dctx_lo % 8 || dqkv_lo % 8) return ADVH_EINVAL;
-    const int dm = H / heads;
-    if (T > 256 || dm % 8 || dm > 128) return ADVH_EUNSUPPORTED;
-    if (dm <= 64 && !g_att_bwd_force_f32)           // three fp16 MFMAs per product instead of eight fp32 MFMAs (attention_bwd_x3.hip)
-        return advh_attention_bwd_x3_launch(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, B, T, H, heads, (hipStream_t)stream);
+template <bool RAGGED>
+static int att_bwd_f32_dispatch(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, const int* frames,
+                                int B, int T, int H, int heads, int dm, hipStream_t s) {
     const int D = dm <= 32 ? 32 : (dm <= 64 ? 64 : 128);
     const float scale = 1.f / sqrtf((float)dm);
-    hipStream_t s = (hipStream_t)stream;
-    const int nt = (T + 15) / 16;
-#define ATB(NT_, D_) return launch_att_bwd_f32<NT_, D_>(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, B, T, H, heads, dm, scale, s)
+    const int nt = (T + 15) / 16;                   // the instance class follows the row stride, ragged or not
+#define ATB(NT_, D_) \
+    return launch_att_bwd_f32<NT_, D_, RAGGED>(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, frames, B, T, H, heads, dm, scale, s)
 #define ATB_D(D_)                                                                     \
     do {                                                                              \
         if (nt <= 4) ATB(4, D_); else if (nt <= 8) ATB(8, D_); else if (nt <= 13) ATB(13, D_); else ATB(16, D_); \
@@ -300,6 +295,38 @@ extern "C" int advh_attention_bwd_split(const void* qkv, int64_t qkv_lo, const v
 #undef ATB_D
 #undef ATB
     return ADVH_EUNSUPPORTED;
+}
+
+}  // namespace advh
+
+using namespace advh;
+
+int g_att_bwd_force_f32 = 0;
+
+// both entry points, after their own argument checks; frames != nullptr: the ragged instances
+static int attention_bwd_split_launch(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo,
+                                      const int* frames, int B, int T, int H, int heads, hipStream_t s) {
+    const int dm = H / heads;
+    if (T > 256 || dm % 8 || dm > 128) return ADVH_EUNSUPPORTED;
+    if (dm <= 64 && !g_att_bwd_force_f32)           // three fp16 MFMAs per product instead of eight fp32 MFMAs (attention_bwd_x3.hip)
+        return advh_attention_bwd_x3_launch(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, frames, B, T, H, heads, s);
+    return frames ? att_bwd_f32_dispatch<true>(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, frames, B, T, H, heads, dm, s)
+                  : att_bwd_f32_dispatch<false>(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, nullptr, B, T, H, heads, dm, s);
+}
+
+extern "C" int advh_attention_bwd_split(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, void* dqkv, int64_t dqkv_lo,
+                                        int B, int T, int H, int heads, advh_stream_t stream) {
+    if (!qkv || !dctx || !dqkv || B <= 0 || T <= 0 || heads <= 0 || H % heads) return ADVH_EINVAL;
+    if (qkv_lo <= 0 || dctx_lo <= 0 || dqkv_lo <= 0 || qkv_lo % 8 || dctx_lo % 8 || dqkv_lo % 8) return ADVH_EINVAL;
+    return attention_bwd_split_launch(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, nullptr, B, T, H, heads, (hipStream_t)stream);
+}
+
+extern "C" int advh_attention_bwd_split_ragged(const void* qkv, int64_t qkv_lo, const void* dctx, int64_t dctx_lo, void* dqkv,
+                                               int64_t dqkv_lo, const int32_t* frames, int B, int T, int H, int heads,
+                                               advh_stream_t stream) {
+    if (!qkv || !dctx || !dqkv || !frames || B <= 0 || T <= 0 || H <= 0 || heads <= 0 || H % heads) return ADVH_EINVAL;
+    if (qkv_lo <= 0 || dctx_lo <= 0 || dqkv_lo <= 0 || qkv_lo % 8 || dctx_lo % 8 || dqkv_lo % 8) return ADVH_EINVAL;
+    return attention_bwd_split_launch(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, (const int*)frames, B, T, H, heads, (hipStream_t)stream);
 }
 
 ADVH_SPLIT_FLAG_SETTER(advh_split_flag_attention_bwd_f32)

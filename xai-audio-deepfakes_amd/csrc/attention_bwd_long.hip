@@ -1,6 +1,6 @@
 // Attention backward for clips of any length: dqkv from (qkv, dctx) for softmax(Q K^T / sqrt(d)) V, any T >= 1, head dim <= 128.
 //
-// The whole-clip kernels (backward.hip, attention_bwd_x3.hip, attention_bwd_f32.hip, attention_bwd_ragged.hip) hold a (clip, head)
+// The whole-clip kernels (backward.hip, attention_bwd_x3.hip, attention_bwd_f32.hip, batch and ragged instances) hold a (clip, head)
 // in LDS and stop at T = 256 frames.  Here two kernels run one after the other on the same stream, each streaming the other side's
 // rows through LDS in blocks of 128, with the row statistics of the softmax in a caller-provided fp32 workspace between them; no
 // atomics.  Every product runs on v_mfma_f32_16x16x4_f32 for both operand formats: split plane pairs and plain fp16 (lo == 0) are

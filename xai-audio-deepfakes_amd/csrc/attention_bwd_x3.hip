@@ -22,10 +22,10 @@
 #include "addvisor_hip.h"
 #include "common.h"
 #include "device_math.h"
+#include "ragged_clip.h"
 
 namespace advh {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 trvec __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef const __attribute__((address_space(3))) char* lds_cptr;
@@ -99,10 +99,12 @@ __device__ __forceinline__ f16x8 gfrag(const _Float16* p, bool in) {
         accx = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, accx, 0, 0, 0);        \
     } while (0)
 
-template <int NT, int D, int NW>
+// RAGGED (advh_attention_bwd_split_ragged): Ts is the clip stride, T = clamp(frames[b], 1, Ts) the bound, rows [T, Ts) of this
+// head's dq | dk | dv are zeroed first, in both planes -- the contract written out at attention_bwd_kernel (backward.hip).
+template <int NT, int D, int NW, bool RAGGED>
 __global__ __launch_bounds__(64 * NW) void attention_bwd_x3_kernel(const _Float16* __restrict__ qkv, long qkv_lo, const _Float16* __restrict__ dctx,
-                                                                   long dctx_lo, _Float16* __restrict__ dqkv, long dqkv_lo, int T, int H, int dm,
-                                                                   float scale) {
+                                                                   long dctx_lo, _Float16* __restrict__ dqkv, long dqkv_lo, int Ts, int H, int dm,
+                                                                   float scale, const int* __restrict__ frames) {
     typedef AttBwdX3<NT, D> G;
     constexpr int ROWS = G::ROWS, PLANE = G::PLANE, KK = D / 32, DG = D / 16, NS = G::NS;
     extern __shared__ __attribute__((aligned(16))) _Float16 smx[];
@@ -119,10 +121,13 @@ __global__ __launch_bounds__(64 * NW) void attention_bwd_x3_kernel(const _Float1
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int fr = lane & 15, g = lane >> 4;
     const int head = blockIdx.x, b = blockIdx.y;
+    int T = Ts;                                                          // the bound; Ts is the clip stride
+    if constexpr (RAGGED) T = clip_frames(frames, b, Ts);
     const long ld = 3L * H;
-    const _Float16* base = qkv + (long)b * T * ld + head * dm;           // q at +0, k at +H, v at +2H
-    const _Float16* dob = dctx + (long)b * T * H + head * dm;
-    _Float16* dbase = dqkv + (long)b * T * ld + head * dm;
+    const _Float16* base = qkv + (long)b * Ts * ld + head * dm;          // q at +0, k at +H, v at +2H
+    const _Float16* dob = dctx + (long)b * Ts * H + head * dm;
+    _Float16* dbase = dqkv + (long)b * Ts * ld + head * dm;
+    if constexpr (RAGGED) zero_tail<64 * NW>(dbase, dqkv_lo, ld, H, T, Ts, dm, tid);
     const float c2 = scale * LOG2E_X3;
     const int nst = (T + 31) / 32;                                       // 32-row steps that hold any row < T
     int troff[DG], rowoff[KK];                                           // per-lane LDS offsets (bytes / halfs) within a 32-row step / 16-row tile
@@ -319,29 +324,26 @@ __global__ __launch_bounds__(64 * NW) void attention_bwd_x3_kernel(const _Float1
     }
 }
 
-template <int NT, int D, int NW>
-static int launch_att_bwd_x3(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, int B, int T, int H,
-                             int heads, int dm, float scale, hipStream_t s) {
+template <int NT, int D, int NW, bool RAGGED>
+static int launch_att_bwd_x3(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, const int* frames,
+                             int B, int T, int H, int heads, int dm, float scale, hipStream_t s) {
     constexpr int lds = AttBwdX3<NT, D>::LDS_BYTES;
     static_assert(lds <= 160 * 1024, "two matrices in two planes must fit");
-    if (advh_ensure_lds((const void*)attention_bwd_x3_kernel<NT, D, NW>) != ADVH_OK) return ADVH_ELAUNCH;
-    hipLaunchKernelGGL((attention_bwd_x3_kernel<NT, D, NW>), dim3(heads, B), dim3(64 * NW), lds, s, (const _Float16*)qkv, qkv_lo,
-                       (const _Float16*)dctx, dctx_lo, (_Float16*)dqkv, dqkv_lo, T, H, dm, scale);
+    if (advh_ensure_lds((const void*)attention_bwd_x3_kernel<NT, D, NW, RAGGED>) != ADVH_OK) return ADVH_ELAUNCH;
+    hipLaunchKernelGGL((attention_bwd_x3_kernel<NT, D, NW, RAGGED>), dim3(heads, B), dim3(64 * NW), lds, s, (const _Float16*)qkv, qkv_lo,
+                       (const _Float16*)dctx, dctx_lo, (_Float16*)dqkv, dqkv_lo, T, H, dm, scale, frames);
     return ADVH_LAUNCH_CHECK();
 }
 
-}  // namespace advh
-
-using namespace advh;
-
-// head dims <= 64 (D = 32 | 64), T <= 256; arguments validated by advh_attention_bwd_split (attention_bwd_f32.hip)
-int advh_attention_bwd_x3_launch(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, int B, int T, int H,
-                                 int heads, hipStream_t s) {
+template <bool RAGGED>
+static int att_bwd_x3_dispatch(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, const int* frames,
+                               int B, int T, int H, int heads, hipStream_t s) {
     const int dm = H / heads;
     const int D = dm <= 32 ? 32 : 64;
     const float scale = 1.f / sqrtf((float)dm);
     const int nt = (T + 15) / 16;
-#define ATX(NT_, D_, NW_) return launch_att_bwd_x3<NT_, D_, NW_>(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, B, T, H, heads, dm, scale, s)
+#define ATX(NT_, D_, NW_) \
+    return launch_att_bwd_x3<NT_, D_, NW_, RAGGED>(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, frames, B, T, H, heads, dm, scale, s)
     // eight wavefronts (two per SIMD, 256 VGPRs each: the 13-tile / head-dim-64 instance keeps 68 bytes per lane of scratch for values
     // that live across the passes, outside the product loops, and still beats four wavefronts 293 to 392 us); 16 key tiles x head dim 64
     // need 2 x 16 score registers per lane in pass A: four wavefronts with the whole register file (356 us at 64 x 12 x 249) instead of
@@ -355,6 +357,18 @@ int advh_attention_bwd_x3_launch(const void* qkv, long qkv_lo, const void* dctx,
 #undef ATX_D
 #undef ATX
     return ADVH_EUNSUPPORTED;
+}
+
+}  // namespace advh
+
+using namespace advh;
+
+// head dims <= 64 (D = 32 | 64), T <= 256; arguments validated by advh_attention_bwd_split / _split_ragged (attention_bwd_f32.hip);
+// frames != nullptr: the ragged instances
+int advh_attention_bwd_x3_launch(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, const int* frames,
+                                 int B, int T, int H, int heads, hipStream_t s) {
+    return frames ? att_bwd_x3_dispatch<true>(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, frames, B, T, H, heads, s)
+                  : att_bwd_x3_dispatch<false>(qkv, qkv_lo, dctx, dctx_lo, dqkv, dqkv_lo, nullptr, B, T, H, heads, s);
 }
 
 ADVH_SPLIT_FLAG_SETTER(advh_split_flag_attention_bwd_x3)

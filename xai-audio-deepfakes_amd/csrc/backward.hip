@@ -10,12 +10,12 @@
 #include "addvisor_hip.h"
 #include "common.h"
 #include "device_math.h"
+#include "ragged_clip.h"
 
 namespace advh {
 
 constexpr float LOG2E = 1.4426950408889634f;
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -135,6 +135,12 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
 // LDS DMA and the three operands that need the transposed orientation (K^T for dQ, dO^T for dV, Q^T for dK) are read with
 // ds_read_b64_tr_b16; the key / query order of its two 4-row reads (4g+q | 16+4g+q) is the order the dS / P registers
 // already have.  LDS drops from 88 KB to 53 KB (+ statistics).
+// RAGGED (advh_attention_bwd_f16_ragged): frames is int32 [B] on the device, clip b has frames[b] valid rows of its Ts.  Ts stays
+// the clip stride (and picks the instance class) and T = clamp(frames[b], 1, Ts) is the bound of every staging loop, tile loop, key
+// mask, row clamp and store: rows >= T of qkv / dctx are never read for their value, and rows T <= t < Ts of this head's columns of
+// dq | dk | dv are written as zeros as the FIRST thing the workgroup does (the stores retire behind the staging loads; no register
+// outlives them).  Padded keys and queries contribute exact zeros, so frames[b] = Ts reproduces the batch instance bit for bit and
+// a clip's rows do not depend on the batch around it.  The batch instance (RAGGED = false) never reads frames (ragged_clip.h).
 typedef __fp16 trvec __attribute__((__vector_size__(4 * sizeof(__fp16))));
 #define ADVH_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define ADVH_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -151,9 +157,10 @@ __device__ __forceinline__ f16x8 tr_frag64(const __attribute__((address_space(3)
     return r;
 }
 
-template <int NT, int D, bool TR>
+template <int NT, int D, bool TR, bool RAGGED>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ dctx,
-                                                            _Float16* __restrict__ dqkv, int T, int H, int dm, float scale) {
+                                                            _Float16* __restrict__ dqkv, int Ts, int H, int dm, float scale,
+                                                            const int* __restrict__ frames) {
     constexpr int NKEY = NT * 16, CH = D / 8, VP = NKEY + 64, NS = (NT + 1) / 2, KK = D / 32, DT = D / 16;
     constexpr int ROWB = NKEY * D, TRB = TR ? 0 : D * VP;
     static_assert(!TR || D == 64, "the transposing-read path is for head dim 64");
@@ -174,10 +181,13 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const _Float16* __re
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int head = blockIdx.x, b = blockIdx.y;
+    int T = Ts;                                                    // the bound; Ts is the clip stride
+    if constexpr (RAGGED) T = clip_frames(frames, b, Ts);
     const long ld = 3L * H;
-    const _Float16* base = qkv + (long)b * T * ld + head * dm;     // q at +0, k at +H, v at +2H
-    const _Float16* dob = dctx + (long)b * T * H + head * dm;
-    _Float16* dbase = dqkv + (long)b * T * ld + head * dm;
+    const _Float16* base = qkv + (long)b * Ts * ld + head * dm;    // q at +0, k at +H, v at +2H
+    const _Float16* dob = dctx + (long)b * Ts * H + head * dm;
+    _Float16* dbase = dqkv + (long)b * Ts * ld + head * dm;
+    if constexpr (RAGGED) zero_tail<256>(dbase, 0, ld, H, T, Ts, dm, tid);
     const int chm = dm / 8;                                        // real 16-byte chunks per row (D - dm is zero padding)
     const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
     const int fr = lane & 15, g = lane >> 4;
@@ -418,6 +428,50 @@ __global__ __launch_bounds__(256) void pool_logreg_bwd_kernel(const float* __res
     }
 }
 
+// dh[b][t][:] = coef[:] * (dlogit[b] / Tv_b) for t < Tv_b, 0 for Tv_b <= t < T      (mean over the clip's own frames + Linear(H,1))
+// A kernel of its own, not a RAGGED instance of the one above: that kernel reads gridDim from the implicit arguments behind the
+// explicit ones, so one more explicit argument moves an offset in the batch code.
+__global__ __launch_bounds__(256) void pool_logreg_bwd_ragged_kernel(const float* __restrict__ coef, const float* __restrict__ dlogit,
+                                                                     float* __restrict__ dh, _Float16* __restrict__ dh16,
+                                                                     const int* __restrict__ frames, int T, int H, long total4, long dh16_lo) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
+        int c = (int)(i % (H / 4)) * 4;
+        long bt = i / (H / 4);
+        int b = (int)(bt / T), t = (int)(bt - (long)b * T);
+        const int Tv = clip_frames(frames, b, T);
+        float o[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t < Tv) {
+            float s = dlogit[b] / Tv;
+            float4 w = *(const float4*)(coef + c);
+            o[0] = w.x * s; o[1] = w.y * s; o[2] = w.z * s; o[3] = w.w * s;
+        }
+        if (dh) *(float4*)(dh + bt * H + c) = make_float4(o[0], o[1], o[2], o[3]);
+        if (dh16) store_h_rt<4>(dh16, bt * H + c, dh16_lo, o);
+    }
+}
+
+// x[b, frames[b]:, :] = 0 for fp16 rows, and for the lo plane `lo` elements behind when lo != 0.  Grid row b = clip b.
+// VEC: 16-byte stores (x 16-byte aligned, H % 8 == 0, lo % 8 == 0).
+template <bool VEC>
+__global__ __launch_bounds__(256) void zero_tail_rows_h_kernel(_Float16* __restrict__ x, long lo, const int* __restrict__ frames, int T, int H) {
+    const int b = blockIdx.y, f0 = clip_frames(frames, b, T, 0);
+    _Float16* xb = x + ((long)b * T + f0) * H;
+    const long n = (long)(T - f0) * H;
+    const long start = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+    if (VEC) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (long i = start; i < n / 8; i += step) {
+            ((float4*)xb)[i] = z;
+            if (lo) ((float4*)(xb + lo))[i] = z;
+        }
+    } else {
+        for (long i = start; i < n; i += step) {
+            xb[i] = (_Float16)0.f;
+            if (lo) xb[i + lo] = (_Float16)0.f;
+        }
+    }
+}
+
 // y[i] = alpha[row] * x[i] (+ y[i] if accumulate);  row = i / n.  IG path scaling and step accumulation.
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ x, const float* __restrict__ alpha,
                                                          float* __restrict__ y, long n, long total, int accumulate, int xrows) {
@@ -526,29 +580,31 @@ extern "C" int advh_layernorm_bwd_split(const void* x, int x_is_f32, int64_t x_l
                                 remap_P, x_is_f32 ? 0 : x_lo, dy_is_f32 ? 0 : dy_lo, dact_src ? dact_lo : 0, out_h ? out_lo : 0, stream);
 }
 
-template <int NT, int D, bool TR>
-static int launch_att_bwd(const void* qkv, const void* dctx, void* dqkv, int B, int T, int H, int heads, int dm, float scale, hipStream_t s) {
+template <int NT, int D, bool TR, bool RAGGED>
+static int launch_att_bwd(const void* qkv, const void* dctx, void* dqkv, const int* frames, int B, int T, int H, int heads, int dm,
+                          float scale, hipStream_t s) {
     constexpr int NKEY = NT * 16, VP = NKEY + 64, ROWB = NKEY * D, TRB = TR ? 0 : D * VP;
     constexpr int PA = TR ? 2 * ROWB : (D <= 64 ? 2 * ROWB + TRB : ROWB + TRB);
     const size_t lds = (size_t)(PA > 2 * TRB ? PA : 2 * TRB) * 2 + 3 * NKEY * 4;
     if (lds > 160 * 1024) return ADVH_EUNSUPPORTED;
-    if (advh_ensure_lds((const void*)attention_bwd_kernel<NT, D, TR>) != ADVH_OK) return ADVH_ELAUNCH;
-    hipLaunchKernelGGL((attention_bwd_kernel<NT, D, TR>), dim3(heads, B), dim3(256), lds, s, (const _Float16*)qkv, (const _Float16*)dctx,
-                       (_Float16*)dqkv, T, H, dm, scale);
+    if (advh_ensure_lds((const void*)attention_bwd_kernel<NT, D, TR, RAGGED>) != ADVH_OK) return ADVH_ELAUNCH;
+    hipLaunchKernelGGL((attention_bwd_kernel<NT, D, TR, RAGGED>), dim3(heads, B), dim3(256), lds, s, (const _Float16*)qkv,
+                       (const _Float16*)dctx, (_Float16*)dqkv, T, H, dm, scale, frames);
     return ADVH_LAUNCH_CHECK();
 }
 
-extern "C" int advh_attention_bwd_f16(const void* qkv, const void* dctx, void* dqkv, int B, int T, int H, int heads,
+// arguments validated by the two entry points; the instance class follows the row stride T, ragged or not
+template <bool RAGGED>
+static int attention_bwd_f16_dispatch(const void* qkv, const void* dctx, void* dqkv, const int* frames, int B, int T, int H, int heads,
                                       advh_stream_t stream) {
-    if (!qkv || !dctx || !dqkv || B <= 0 || T <= 0 || heads <= 0 || H % heads) return ADVH_EINVAL;
     const int dm = H / heads;
     if (T > 256 || dm % 8 || dm > 128) return ADVH_EUNSUPPORTED;
     const int D = dm <= 32 ? 32 : (dm <= 64 ? 64 : 128);
     const float scale = 1.f / sqrtf((float)dm);
     hipStream_t s = (hipStream_t)stream;
     const int nt = (T + 15) / 16;
-#define ATB(NT_, D_) return launch_att_bwd<NT_, D_, false>(qkv, dctx, dqkv, B, T, H, heads, dm, scale, s)
-#define ATBT(NT_) return launch_att_bwd<NT_, 64, true>(qkv, dctx, dqkv, B, T, H, heads, dm, scale, s)
+#define ATB(NT_, D_) return launch_att_bwd<NT_, D_, false, RAGGED>(qkv, dctx, dqkv, frames, B, T, H, heads, dm, scale, s)
+#define ATBT(NT_) return launch_att_bwd<NT_, 64, true, RAGGED>(qkv, dctx, dqkv, frames, B, T, H, heads, dm, scale, s)
     if (dm == 64) { if (nt <= 4) ATBT(4); else if (nt <= 8) ATBT(8); else if (nt <= 13) ATBT(13); else ATBT(16); }
     else if (D == 64) { if (nt <= 4) ATB(4, 64); else if (nt <= 8) ATB(8, 64); else if (nt <= 13) ATB(13, 64); else ATB(16, 64); }
     else if (D == 32) { if (nt <= 4) ATB(4, 32); else if (nt <= 8) ATB(8, 32); else if (nt <= 13) ATB(13, 32); else ATB(16, 32); }
@@ -557,26 +613,65 @@ extern "C" int advh_attention_bwd_f16(const void* qkv, const void* dctx, void* d
 #undef ATBT
 }
 
-static int pool_logreg_bwd_launch(const float* coef, const float* dlogit, float* dh, void* dh16, long dh16_lo, int B, int T, int H,
-                                  advh_stream_t stream) {
+extern "C" int advh_attention_bwd_f16(const void* qkv, const void* dctx, void* dqkv, int B, int T, int H, int heads,
+                                      advh_stream_t stream) {
+    if (!qkv || !dctx || !dqkv || B <= 0 || T <= 0 || heads <= 0 || H % heads) return ADVH_EINVAL;
+    return attention_bwd_f16_dispatch<false>(qkv, dctx, dqkv, nullptr, B, T, H, heads, stream);
+}
+
+extern "C" int advh_attention_bwd_f16_ragged(const void* qkv, const void* dctx, void* dqkv, const int32_t* frames, int B, int T, int H,
+                                             int heads, advh_stream_t stream) {
+    if (!qkv || !dctx || !dqkv || !frames || B <= 0 || T <= 0 || H <= 0 || heads <= 0 || H % heads) return ADVH_EINVAL;
+    return attention_bwd_f16_dispatch<true>(qkv, dctx, dqkv, (const int*)frames, B, T, H, heads, stream);
+}
+
+// frames != nullptr: the ragged kernel (the ragged entry points refuse a null frames before they come here)
+static int pool_logreg_bwd_launch(const float* coef, const float* dlogit, float* dh, void* dh16, long dh16_lo, const int32_t* frames,
+                                  int B, int T, int H, advh_stream_t stream) {
     if (!coef || !dlogit || (!dh && !dh16) || B <= 0 || T <= 0 || H <= 0 || H % 4) return ADVH_EINVAL;
     long total4 = (long)B * T * (H / 4);
     long blocks = (total4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(pool_logreg_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, coef, dlogit, dh,
-                       (_Float16*)dh16, T, H, total4, dh16_lo);
+    if (frames)
+        hipLaunchKernelGGL(pool_logreg_bwd_ragged_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, coef, dlogit, dh,
+                           (_Float16*)dh16, (const int*)frames, T, H, total4, dh16_lo);
+    else
+        hipLaunchKernelGGL(pool_logreg_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, coef, dlogit, dh,
+                           (_Float16*)dh16, T, H, total4, dh16_lo);
     return ADVH_LAUNCH_CHECK();
 }
 
 extern "C" int advh_pool_logreg_bwd(const float* coef, const float* dlogit, float* dh, void* dh16, int B, int T, int H,
                                     advh_stream_t stream) {
-    return pool_logreg_bwd_launch(coef, dlogit, dh, dh16, 0, B, T, H, stream);
+    return pool_logreg_bwd_launch(coef, dlogit, dh, dh16, 0, nullptr, B, T, H, stream);
 }
 
 extern "C" int advh_pool_logreg_bwd_split(const float* coef, const float* dlogit, float* dh, void* dh16, int64_t dh16_lo, int B, int T,
                                           int H, advh_stream_t stream) {
     if (dh16 && (dh16_lo <= 0 || dh16_lo % 4)) return ADVH_EINVAL;
-    return pool_logreg_bwd_launch(coef, dlogit, dh, dh16, dh16 ? dh16_lo : 0, B, T, H, stream);
+    return pool_logreg_bwd_launch(coef, dlogit, dh, dh16, dh16 ? dh16_lo : 0, nullptr, B, T, H, stream);
+}
+
+extern "C" int advh_pool_logreg_bwd_ragged(const float* coef, const float* dlogit, float* dh, void* dh16, const int32_t* frames, int B,
+                                           int T, int H, advh_stream_t stream) {
+    if (!frames) return ADVH_EINVAL;
+    return pool_logreg_bwd_launch(coef, dlogit, dh, dh16, 0, frames, B, T, H, stream);
+}
+
+extern "C" int advh_pool_logreg_bwd_split_ragged(const float* coef, const float* dlogit, float* dh, void* dh16, int64_t dh16_lo,
+                                                 const int32_t* frames, int B, int T, int H, advh_stream_t stream) {
+    if (!frames || (dh16 && (dh16_lo <= 0 || dh16_lo % 4))) return ADVH_EINVAL;
+    return pool_logreg_bwd_launch(coef, dlogit, dh, dh16, dh16 ? dh16_lo : 0, frames, B, T, H, stream);
+}
+
+extern "C" int advh_zero_tail_rows_h(void* x, int64_t lo, const int32_t* frames, int B, int T, int H, advh_stream_t stream) {
+    if (!x || !frames || lo < 0 || B <= 0 || T <= 0 || H <= 0) return ADVH_EINVAL;
+    if (B > 65535) return ADVH_EUNSUPPORTED;                 // one grid row per clip
+    const bool vec = aligned16(x) && H % 8 == 0 && lo % 8 == 0;
+    const dim3 grid(grid_for((long)T * H / (vec ? 8 : 1), 64), B);
+    launch_vec(vec, zero_tail_rows_h_kernel<true>, zero_tail_rows_h_kernel<false>, grid, (hipStream_t)stream, (_Float16*)x, (long)lo,
+               (const int*)frames, T, H);
+    return ADVH_LAUNCH_CHECK();
 }
 
 extern "C" int advh_scale_rows(const float* x, int x_rows, const float* alpha, float* y, int rows, int64_t n, int accumulate,

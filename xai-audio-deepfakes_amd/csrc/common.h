@@ -14,15 +14,12 @@ int advh_split_flag_attention_ragged(int* flag);
 int advh_split_flag_attention_long(int* flag);
 int advh_split_flag_attention_bwd_long(int* flag);   // attention_bwd_long.hip raises its LDS limits per launch (advh_ensure_lds): no init function
 int advh_split_flag_attention_bwd_f32(int* flag);
-int advh_split_flag_attention_bwd_ragged(int* flag);
 int advh_split_flag_attribution_layer(int* flag);
 int advh_split_flag_attribution_neuron(int* flag);
 int advh_split_flag_attention_bwd_x3(int* flag);
 int advh_split_flag_backward(int* flag);
-int advh_split_flag_backward_ragged(int* flag);
 int advh_split_flag_conv_taps(int* flag);
 int advh_split_flag_frontend(int* flag);
-int advh_split_flag_frontend_ragged(int* flag);
 int advh_split_flag_frontend_bwd(int* flag);
 int advh_split_flag_gemm(int* flag);
 int advh_split_flag_hifigan(int* flag);
@@ -38,9 +35,10 @@ int advh_split_flag_lrp(int* flag);
 int advh_split_flag_attention_maps_long(int* flag);   // attention_maps_long.hip: advh_ensure_lds per launch, no init function
 
 // attention backward of the fp32-class mode: the split-arithmetic kernel for head dims <= 64 (attention_bwd_x3.hip), called by
-// advh_attention_bwd_split (attention_bwd_f32.hip) after it validated the arguments; g_att_bwd_force_f32: advh_set_option("attention_bwd_mfma_f32")
-int advh_attention_bwd_x3_launch(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, int B, int T, int H,
-                                 int heads, hipStream_t s);
+// advh_attention_bwd_split / _split_ragged (attention_bwd_f32.hip) after they validated the arguments; frames != nullptr: the ragged
+// instances; g_att_bwd_force_f32: advh_set_option("attention_bwd_mfma_f32")
+int advh_attention_bwd_x3_launch(const void* qkv, long qkv_lo, const void* dctx, long dctx_lo, void* dqkv, long dqkv_lo, const int* frames,
+                                 int B, int T, int H, int heads, hipStream_t s);
 extern int g_att_bwd_force_f32;
 
 // Raise a kernel's dynamic-LDS limit to `bytes` once per (kernel, DEVICE): the attribute belongs to the device's copy of

@@ -6,6 +6,7 @@
 #include "addvisor_hip.h"
 #include "common.h"
 #include "device_math.h"
+#include "ragged_clip.h"
 
 namespace advh {
 
@@ -120,15 +121,20 @@ __global__ __launch_bounds__(256) void posconv_gather_kernel(const float* __rest
 // (LMAC_metrics.py:130,146,156 pooling + classifier_embedder.py:34-38).  One workgroup per clip.
 // Fast path (H % 4 == 0, H <= 2048): wavefront w sums the frames t = w, w+4, ... with 16-byte loads (NV independent
 // accumulators per lane, two frames in flight), the four partial rows meet in LDS in a fixed order -> deterministic.
-template <int NV>
+// RAGGED (advh_pool_logreg_ragged): frames is int32 [B] on the device; the clip base stays at b * Ts rows and the frame loop and
+// divisor are T = clamp(frames[b], 1, Ts).  The valid frames are added in the batch form's order, so frames[b] = Ts reproduces it
+// bit for bit.  The batch instance never reads frames (ragged_clip.h).
+template <int NV, bool RAGGED>
 __global__ __launch_bounds__(256) void pool_logreg_rows_kernel(const float* __restrict__ h, const float* __restrict__ coef,
                                                                float intercept, float* __restrict__ logit,
                                                                float* __restrict__ prob, float* __restrict__ pooled,
-                                                               int T, int H) {
+                                                               int Ts, int H, const int* __restrict__ frames) {
     extern __shared__ float part[];                       // [4][H]
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float* hb = h + (long)b * T * H;
+    int T = Ts;
+    if constexpr (RAGGED) T = clip_frames(frames, b, Ts);
+    const float* hb = h + (long)b * Ts * H;
     float4 acc[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -170,13 +176,16 @@ __global__ __launch_bounds__(256) void pool_logreg_rows_kernel(const float* __re
 }
 
 // any H: one thread per channel, frames in order
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void pool_logreg_kernel(const float* __restrict__ h, const float* __restrict__ coef,
                                                           float intercept, float* __restrict__ logit,
                                                           float* __restrict__ prob, float* __restrict__ pooled,
-                                                          int T, int H) {
+                                                          int Ts, int H, const int* __restrict__ frames) {
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float* hb = h + (long)b * T * H;
+    int T = Ts;
+    if constexpr (RAGGED) T = clip_frames(frames, b, Ts);
+    const float* hb = h + (long)b * Ts * H;
     float dot = 0.f;
     for (int c = tid; c < H; c += 256) {
         float s = 0.f;
@@ -192,6 +201,23 @@ __global__ __launch_bounds__(256) void pool_logreg_kernel(const float* __restric
         float z = (red[0] + red[1]) + (red[2] + red[3]) + intercept;
         logit[b] = z;
         prob[b] = 1.f / (1.f + expf(-z));
+    }
+}
+
+// x[b, frames[b]:, :] = 0.  Grid row b = clip b.  VEC: 16-byte stores (x 16-byte aligned and H % 4 == 0).
+// HF zeroes padded rows after the feature projection (Wav2Vec2Encoder / Wav2Vec2EncoderStableLayerNorm .forward,
+// modeling_wav2vec2.py: hidden_states[~expand_attention_mask] = 0), so the positional convolution of a valid frame sees the
+// zero padding it would see in the clip run alone; advh_zero_tail_rows is that statement, and also clears the returned hidden states.
+template <bool VEC>
+__global__ __launch_bounds__(256) void zero_tail_rows_kernel(float* __restrict__ x, const int* __restrict__ frames, int T, int H) {
+    const int b = blockIdx.y, f0 = clip_frames(frames, b, T, 0);
+    float* xb = x + ((long)b * T + f0) * H;
+    const long n = (long)(T - f0) * H;
+    const long start = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+    if (VEC) {
+        for (long i = start; i < n / 4; i += step) ((float4*)xb)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        for (long i = start; i < n; i += step) xb[i] = 0.f;
     }
 }
 
@@ -283,17 +309,38 @@ extern "C" int advh_posconv_gather_bwd_split(const float* dh, void* xg, int64_t 
     return posconv_gather_launch(dh, xg, xg_lo, B, T, H, G, K, pad_left, dact_src, dact_lo, stream);
 }
 
-extern "C" int advh_pool_logreg(const float* h, const float* coef, float intercept, float* logit, float* prob,
-                                float* pooled, int B, int T, int H, advh_stream_t stream) {
-    if (!h || !coef || !logit || !prob || B <= 0 || T <= 0 || H <= 0) return ADVH_EINVAL;
+template <bool RAGGED>
+static int pool_logreg_launch(const float* h, const float* coef, float intercept, float* logit, float* prob, float* pooled,
+                              const int* frames, int B, int T, int H, advh_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = 4 * (size_t)H * sizeof(float);
     if (H % 4 == 0 && H <= 1024)
-        hipLaunchKernelGGL(pool_logreg_rows_kernel<4>, dim3(B), dim3(256), lds, s, h, coef, intercept, logit, prob, pooled, T, H);
+        hipLaunchKernelGGL((pool_logreg_rows_kernel<4, RAGGED>), dim3(B), dim3(256), lds, s, h, coef, intercept, logit, prob, pooled, T, H, frames);
     else if (H % 4 == 0 && H <= 2048)
-        hipLaunchKernelGGL(pool_logreg_rows_kernel<8>, dim3(B), dim3(256), lds, s, h, coef, intercept, logit, prob, pooled, T, H);
+        hipLaunchKernelGGL((pool_logreg_rows_kernel<8, RAGGED>), dim3(B), dim3(256), lds, s, h, coef, intercept, logit, prob, pooled, T, H, frames);
     else
-        hipLaunchKernelGGL(pool_logreg_kernel, dim3(B), dim3(256), 0, s, h, coef, intercept, logit, prob, pooled, T, H);
+        hipLaunchKernelGGL(pool_logreg_kernel<RAGGED>, dim3(B), dim3(256), 0, s, h, coef, intercept, logit, prob, pooled, T, H, frames);
+    return ADVH_LAUNCH_CHECK();
+}
+
+extern "C" int advh_pool_logreg(const float* h, const float* coef, float intercept, float* logit, float* prob,
+                                float* pooled, int B, int T, int H, advh_stream_t stream) {
+    if (!h || !coef || !logit || !prob || B <= 0 || T <= 0 || H <= 0) return ADVH_EINVAL;
+    return pool_logreg_launch<false>(h, coef, intercept, logit, prob, pooled, nullptr, B, T, H, stream);
+}
+
+extern "C" int advh_pool_logreg_ragged(const float* h, const float* coef, float intercept, float* logit, float* prob,
+                                       float* pooled, const int32_t* frames, int B, int T, int H, advh_stream_t stream) {
+    if (!h || !coef || !logit || !prob || !frames || B <= 0 || T <= 0 || H <= 0) return ADVH_EINVAL;
+    return pool_logreg_launch<true>(h, coef, intercept, logit, prob, pooled, (const int*)frames, B, T, H, stream);
+}
+
+extern "C" int advh_zero_tail_rows(float* x, const int32_t* frames, int B, int T, int H, advh_stream_t stream) {
+    if (!x || !frames || B <= 0 || T <= 0 || H <= 0) return ADVH_EINVAL;
+    if (B > 65535) return ADVH_EUNSUPPORTED;                 // one grid row per clip
+    const bool vec = aligned16(x) && H % 4 == 0;
+    const dim3 grid(grid_for((long)T * H / (vec ? 4 : 1), 64), B);
+    launch_vec(vec, zero_tail_rows_kernel<true>, zero_tail_rows_kernel<false>, grid, (hipStream_t)stream, x, (const int*)frames, T, H);
     return ADVH_LAUNCH_CHECK();
 }
 

@@ -547,7 +547,7 @@ extern "C" int advh_init(void) {
     }
     int* dflag = nullptr;
     if (hipHostGetDevicePointer((void**)&dflag, g_split_flag_host, 0) != hipSuccess) return ADVH_ELAUNCH;
-    int (*const setters[])(int*) = {advh_split_flag_attention, advh_split_flag_attention_ragged, advh_split_flag_attention_long, advh_split_flag_attention_bwd_long, advh_split_flag_attention_bwd_f32, advh_split_flag_attention_bwd_ragged, advh_split_flag_attention_bwd_x3, advh_split_flag_attribution_layer, advh_split_flag_attribution_neuron, advh_split_flag_backward, advh_split_flag_backward_ragged, advh_split_flag_conv_taps, advh_split_flag_frontend, advh_split_flag_frontend_ragged, advh_split_flag_frontend_bwd, advh_split_flag_gemm, advh_split_flag_hifigan, advh_split_flag_rowops, advh_split_flag_unet_misc, advh_split_flag_unet_train, advh_split_flag_resblock_pair_x3,
+    int (*const setters[])(int*) = {advh_split_flag_attention, advh_split_flag_attention_ragged, advh_split_flag_attention_long, advh_split_flag_attention_bwd_long, advh_split_flag_attention_bwd_f32, advh_split_flag_attention_bwd_x3, advh_split_flag_attribution_layer, advh_split_flag_attribution_neuron, advh_split_flag_backward, advh_split_flag_conv_taps, advh_split_flag_frontend, advh_split_flag_frontend_bwd, advh_split_flag_gemm, advh_split_flag_hifigan, advh_split_flag_rowops, advh_split_flag_unet_misc, advh_split_flag_unet_train, advh_split_flag_resblock_pair_x3,
                                    advh_split_flag_conv_taps2d_x3, advh_split_flag_conv_taps2d_head_x3, advh_split_flag_upconv_tile_x3, advh_split_flag_conv_s21_tile_x3, advh_split_flag_lrp,
                                    advh_split_flag_attention_maps_long};
     for (auto set : setters)
