@@ -1472,6 +1472,41 @@ int advh_rollout_step_long(const float* M, const float* X, float* Y, float alpha
                            const int32_t* frames, int B, int T, advh_stream_t stream);
 int advh_rollout_relevance_long(const float* X, float* rel, const int32_t* frames, int B, int T, advh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ragged batches in the explanation pipeline (csrc/stft_ragged.hip, csrc/unet_ragged.hip): clip b of a [B][L] buffer gets what
+ * it gives when its first lens[b] samples are run alone.  `lens` / `widths` are int32 [B] device arrays; every kernel clamps
+ * what it reads from them, so no content moves an access out of the clip's row.  Write L_b = clamp(lens[b], 513, L),
+ * T_b = 1 + L_b / hop and W_b = 4 (T_b / 4).
+ *
+ * advh_stft_forward_ragged: advh_stft_forward's plain forward with `lens` in place of n_in.  wave [B][wave_stride >= L]; the
+ *   reflection of clip b happens at L_b; frames t < T_b of X / mag / phase (each may be NULL, not all three) are the sibling's
+ *   result for wave[b, :L_b] with L = L_b, bit for bit, frames T_b <= t < T are written as zeros; samples >= L_b are not read.
+ *   Optional window, both frames-per-workgroup values, the interior-frame fast path (aligned 8-byte loads) kept.
+ * advh_istft_masked_c64_ragged: advh_istft_masked_c64 with per-clip bounds, both branches in one launch (either may be NULL,
+ *   not both): frames >= T_b of spec and mask columns >= min(Tm, W_b) count as 0 and are not read; samples [0, L_b) of a
+ *   clip's row are the sibling's result on the cropped clip bit for bit, samples [L_b, L) are written as zeros.
+ * advh_fmap_clip_tail: x is a zero-haloed NHWC fp16 map [B][H + 2 PH][W + 2 PW][C] (lo = 0) or a split plane pair whose lo
+ *   plane lies lo elements behind (lo % 8 == 0, lo >= one plane).  For clip b, every interior row and the interior columns
+ *   x >= w_b = clamp(widths[b] >> shift, 0, W): all C channels of every plane are set to 0 with 16-byte stores (C % 8 == 0, x
+ *   16-byte aligned); halo rows and columns are not touched, columns < w_b keep their bits.  shift = 0 / 1 / 2 for the full-,
+ *   half- and quarter-width maps of the U-Net.  ind_channel >= 0: that channel is also rewritten over the whole interior, 1.0
+ *   (hi 1, lo 0) for x < w_b and 0 past it: the in-image indicator of the fused up-convolutions.  < 0: no indicator.
+ * advh_zero_tail_cols_f32: x [B][H][W] fp32, t fastest: columns >= clamp(widths[b], 0, W) of every row of clip b are set to 0.
+ * Negative codes, all before any HIP call.  ADVH_EINVAL, all four: a NULL or misaligned pointer (optional ones excepted; no
+ *   output requested counts as NULL) and bad geometry -- the two STFT entries: what their siblings refuse, wave_stride < L,
+ *   T != 1 + L / hop, L <= 512; the map kernel: C % 8, shift outside 0..2, lo % 8 or lo inside the first plane, ind_channel >= C.
+ *   ADVH_EUNSUPPORTED: B > 65535 (all four), H > 65535 (advh_fmap_clip_tail), and win spanning more hops than half the frames
+ *   per workgroup (advh_istft_masked_c64_ragged only, as its sibling).  The two STFT entries then return ADVH_ENOTINIT without
+ *   advh_init.  No scratch, no atomics.                                                                                    */
+int advh_stft_forward_ragged(const float* wave, int64_t wave_stride, const int32_t* lens, int B, int L, int hop, int win,
+                             const float* window, float* X, float* mag, float* phase, int T, advh_stream_t stream);
+int advh_istft_masked_c64_ragged(const float* spec, const float* mask, int Fm, int Tm, int mode, float* wave_in, float* wave_out,
+                                 int64_t wave_stride, const int32_t* lens, int B, int T, int L, int hop, int win,
+                                 const float* window, advh_stream_t stream);
+int advh_fmap_clip_tail(void* x, int64_t lo, const int32_t* widths, int shift, int B, int H, int W, int C, int PH, int PW,
+                        int ind_channel, advh_stream_t stream);
+int advh_zero_tail_cols_f32(float* x, const int32_t* widths, int B, int H, int W, advh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

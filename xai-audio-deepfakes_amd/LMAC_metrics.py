@@ -192,9 +192,12 @@ def _pipeline(domain="log1p"):
     return _pipes[key]
 
 
-def explain_batch(waveforms, magnitude=None, phase=None, domain="log1p"):
+def explain_batch(waveforms, magnitude=None, phase=None, domain="log1p", lengths=None):
     """Loop body of run_addvisor_metrics (LMAC_metrics.py:125-157) for one batch; returns the three
     probability vectors ``(predictions, theta_out, masked_predictions)``, each ``[B,1]``.
+
+    ``lengths`` (one sample count per clip, e.g. from ``audioprocessor.pad_clips``): a ragged batch on the fused step -- every clip
+    is explained as it is alone at its own length (``ExplainPipeline.explain``); explicit spectrograms are then refused.
 
     With the collate's lazy ``magnitude`` / ``phase`` (or None) the batch takes the fused step: 3 embedder passes per clip in
     one 3B batch, the masked resynthesis straight from the complex spectrogram.  Explicit spectrogram TENSORS (a caller that
@@ -203,6 +206,11 @@ def explain_batch(waveforms, magnitude=None, phase=None, domain="log1p"):
     L = int(ap.audio_length * ap.sampling_rate)
     w = waveforms.to(device, torch.float32)
     explicit = lambda t: t is not None and not (isinstance(t, LazyTensor) and not t.materialized)
+    if lengths is not None:
+        if explicit(magnitude) or explicit(phase):
+            raise ValueError("lengths= runs the fused step from the waveforms: explicit magnitude / phase tensors have no per-clip form")
+        out = _pipeline(domain).explain(w, lengths=lengths)
+        return out["predictions"], out["theta_out"], out["masked_predictions"]
     if not explicit(magnitude) and not explicit(phase):
         out = _pipeline(domain).explain(w)
         return out["predictions"], out["theta_out"], out["masked_predictions"]

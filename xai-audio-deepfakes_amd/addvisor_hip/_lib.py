@@ -218,6 +218,10 @@ SIGNATURES = {
     "advh_attention_bwd_value_long": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, _p]),
     "advh_rollout_step_long": (_i, [_p, _p, _p, _f, _f, _f, _i, _p, _i, _i, _p]),
     "advh_rollout_relevance_long": (_i, [_p, _p, _p, _i, _i, _p]),
+    "advh_stft_forward_ragged": (_i, [_p, _i64, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
+    "advh_istft_masked_c64_ragged": (_i, [_p, _p, _i, _i, _i, _p, _p, _i64, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "advh_fmap_clip_tail": (_i, [_p, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "advh_zero_tail_cols_f32": (_i, [_p, _p, _i, _i, _i, _p]),
 }
 
 _lib = None

@@ -51,13 +51,68 @@ def _window(window, win: int, device) -> Optional[torch.Tensor]:
     return window
 
 
+def min_clip_samples(hop: int) -> int:
+    """The shortest clip of a ragged STFT / ISTFT call: ``3 * hop`` samples give a mask width ``4 * (T_b // 4) >= 4`` and 513
+    keep the reflection inside the clip."""
+    return max(3 * int(hop), NFFT // 2 + 1)
+
+
+def check_clip_lengths(lengths, B: int, L: int, lo: int, what: str = "the STFT's reflection and a four-frame mask") -> list:
+    """``lengths`` of a ragged batch ``[B, L]`` as a list of ints in ``[lo, L]``; ``ValueError`` for anything else, with the
+    messages of ``HipEmbedder._check_lengths``.  Host only: called before any allocation, plan or launch."""
+    import numpy as np
+    bad = "lengths must be a sequence or a 1-D integer tensor with one entry per clip"
+    if torch.is_tensor(lengths):
+        if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+            raise ValueError(bad)
+        lengths = lengths.tolist()
+    elif isinstance(lengths, np.ndarray):
+        if lengths.ndim != 1 or not np.issubdtype(lengths.dtype, np.integer):
+            raise ValueError(bad)
+        lengths = lengths.tolist()
+    else:
+        try:
+            lengths = list(lengths)
+        except TypeError:
+            raise ValueError(bad) from None
+    if len(lengths) != B:
+        raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} clips")
+    out = []
+    for b, n in enumerate(lengths):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise ValueError(f"lengths[{b}] = {n!r} is not an integer sample count")
+        n = int(n)
+        if n > L:
+            raise ValueError(f"lengths[{b}] = {n} exceeds the batch's {L} samples")
+        if n < lo:
+            raise ValueError(f"clip {b} has {n} samples, too short for {what}: the shortest supported length is {lo} samples")
+        out.append(n)
+    return out
+
+
+def _lens_tensor(lens, device) -> torch.Tensor:
+    return torch.tensor(lens, dtype=torch.int32).to(device)
+
+
 def stft_forward(wave: torch.Tensor, length: int, hop: int = 322, win: int = 644,
                  window: Optional[torch.Tensor] = None, want_complex: bool = True,
-                 want_mag: bool = True, want_phase: bool = True
+                 want_mag: bool = True, want_phase: bool = True, lengths=None
                  ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
     """``wave [B, n_in]`` fp32 -> ``X [B,513,T] complex64, |X|, angle(X) [B,513,T]`` (audioprocessor.py:82-112).
 
-    The clip is zero-padded / cropped to ``length`` inside the kernel."""
+    The clip is zero-padded / cropped to ``length`` inside the kernel.
+
+    ``lengths`` (``B`` sample counts in ``[max(3 hop, 513), length]``; ``wave`` then has at least ``length`` columns): a ragged
+    batch.  Clip ``b`` is ``wave[b, :lengths[b]]`` with the reflection at its own end; its frames ``t < 1 + lengths[b] // hop``
+    are what the clip gives alone, bit for bit, and the frames behind are exactly 0.  What lies past a clip is never read."""
+    if lengths is not None:
+        if wave.dim() != 2:
+            raise ValueError("wave must be [B, n]")
+        if wave.shape[1] < length:
+            raise ValueError(f"a ragged batch needs wave [B, >= length = {length}], got {wave.shape[1]} columns")
+        lens = check_clip_lengths(lengths, wave.shape[0], int(length), min_clip_samples(hop))
+        if not (want_complex or want_mag or want_phase):
+            raise ValueError("no output requested")
     _lib.init()
     wave = _req(wave, torch.float32, "wave")
     if wave.dim() != 2:
@@ -69,6 +124,12 @@ def stft_forward(wave: torch.Tensor, length: int, hop: int = 322, win: int = 644
     mag = torch.empty((B, NBIN, T), dtype=torch.float32, device=dev) if want_mag else None
     ph = torch.empty((B, NBIN, T), dtype=torch.float32, device=dev) if want_phase else None
     window = _window(window, win, dev)
+    if lengths is not None:
+        lens_d = _lens_tensor(lens, dev)
+        rc = _lib.lib().advh_stft_forward_ragged(wave.data_ptr(), wave.stride(0), lens_d.data_ptr(), B, length, hop, win, _ptr(window),
+                                                 _ptr(X), _ptr(mag), _ptr(ph), T, _stream())
+        _lib.check(rc, "advh_stft_forward_ragged")
+        return (torch.view_as_complex(X) if X is not None else None), mag, ph
     rc = _lib.lib().advh_stft_forward(wave.data_ptr(), wave.stride(0), n_in, B, length, hop, win, _ptr(window),
                                       _ptr(X), _ptr(mag), _ptr(ph), T, _stream())
     _lib.check(rc, "advh_stft_forward")
@@ -110,11 +171,21 @@ def istft_masked(mag: torch.Tensor, phase: torch.Tensor, mask: Optional[torch.Te
 
 
 def istft_masked_c64(spec: torch.Tensor, mask: torch.Tensor, length: int, domain: str = "log1p", want_in: bool = True,
-                     want_out: bool = True, hop: int = 322, win: int = 644, window: Optional[torch.Tensor] = None
+                     want_out: bool = True, hop: int = 322, win: int = 644, window: Optional[torch.Tensor] = None, lengths=None
                      ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
     """:func:`istft_masked` from the complex spectrogram ``spec [B, 513, T]`` complex64 instead of ``(|X|, angle X)``:
     ``X' = X * g(mask, |X|) / |X|`` -- the same masked signal (loss_function.py:36-45, LMAC_metrics.py:136-153) without the
-    atan2 / sincos round trip; both resyntheses come out of one launch that reads the spectrogram from HBM once."""
+    atan2 / sincos round trip; both resyntheses come out of one launch that reads the spectrogram from HBM once.
+
+    ``lengths``: a ragged batch as in :func:`stft_forward`.  Clip ``b`` is resynthesised from its own ``T_b = 1 + lengths[b] //
+    hop`` frames and mask columns ``< min(Tm, 4 * (T_b // 4))`` to ``lengths[b]`` samples, bit for bit what the cropped clip
+    gives alone; samples behind are exactly 0, and frames / mask columns past the clip's are never read."""
+    if lengths is not None:
+        if spec.dim() != 3:
+            raise ValueError("spec must be complex64 [B, 513, T]")
+        lens = check_clip_lengths(lengths, spec.shape[0], int(length), min_clip_samples(hop))
+        if not (want_in or want_out):
+            raise ValueError("no output requested")
     _lib.init()
     if not torch.is_complex(spec) or spec.dtype != torch.complex64 or spec.dim() != 3 or spec.shape[1] != NBIN:
         raise ValueError("spec must be complex64 [B, 513, T]")
@@ -129,6 +200,12 @@ def istft_masked_c64(spec: torch.Tensor, mask: torch.Tensor, length: int, domain
     window = _window(window, win, spec.device)
     w_in = torch.empty((B, length), dtype=torch.float32, device=spec.device) if want_in else None
     w_out = torch.empty((B, length), dtype=torch.float32, device=spec.device) if want_out else None
+    if lengths is not None:
+        lens_d = _lens_tensor(lens, spec.device)
+        rc = _lib.lib().advh_istft_masked_c64_ragged(sr.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[2], mode, _ptr(w_in),
+                                                     _ptr(w_out), length, lens_d.data_ptr(), B, T, length, hop, win, _ptr(window), _stream())
+        _lib.check(rc, "advh_istft_masked_c64_ragged")
+        return w_in, w_out
     rc = _lib.lib().advh_istft_masked_c64(sr.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[2], mode, _ptr(w_in), _ptr(w_out),
                                           length, B, T, length, hop, win, _ptr(window), _stream())
     _lib.check(rc, "advh_istft_masked_c64")

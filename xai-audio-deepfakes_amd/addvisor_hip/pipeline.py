@@ -50,8 +50,74 @@ class ExplainPipeline:
         self.nstreams = max(1, streams)
         self._streams = [torch.cuda.Stream(device=device) for _ in range(self.nstreams - 1)]
 
-    def explain(self, waves: torch.Tensor, keep: bool = False) -> Dict[str, torch.Tensor]:
-        """``waves [B, n]`` fp32 on the GPU -> clean / mask-in / mask-out probabilities ``[B,1]`` and the mask."""
+    def min_length(self) -> int:
+        """The shortest clip of a ragged ``explain``: one embedder frame, a mask of four columns (``3 * hop`` samples) and the
+        STFT's reflection inside the clip (513 samples) -- 966 samples for the reference geometry."""
+        return max(self.embedder.min_length(), ops.min_clip_samples(self.hop))
+
+    def _check_lengths(self, lengths, B: int):
+        return ops.check_clip_lengths(lengths, B, self.L, self.min_length(), "one explanation (an encoder frame, the STFT's "
+                                      "reflection and a four-frame mask)")
+
+    def frame_counts(self, lengths):
+        """``(T_b list, W_b list)``: spectrogram frames ``1 + n_b // hop`` and mask widths ``4 * (T_b // 4)`` of clips with
+        ``lengths`` samples; ``ValueError`` for a length ``explain`` would refuse."""
+        lens = self._check_lengths(lengths, len(lengths))
+        Tb = [1 + n // self.hop for n in lens]
+        return Tb, [4 * (t // 4) for t in Tb]
+
+    def _explain_ragged(self, waves: torch.Tensor, keep: bool, lengths) -> Dict[str, torch.Tensor]:
+        """``explain`` with per-clip lengths: ragged STFT -> U-Net with per-clip widths -> ragged masked ISTFT -> one ragged 3B
+        embedder pass.  Everything is checked on the host before the first launch."""
+        L = self.L
+        if waves.dim() != 2 or waves.dtype != torch.float32 or not waves.is_cuda:
+            raise ValueError("waves must be a CUDA fp32 tensor [B, n]")
+        B, n = waves.shape
+        lens = self._check_lengths(lengths, B)
+        if self.vocoder is not None:
+            raise ValueError("explain(lengths=...) does not cover the vocoder variant: its mel front end and generator take no lengths")
+        if n < max(lens):
+            raise ValueError(f"lengths has a clip of {max(lens)} samples but waves has {n} columns")
+        Tb = [1 + m // self.hop for m in lens]
+        widths = [4 * (t // 4) for t in Tb]
+        dev, lib, st = waves.device, _lib.lib(), torch.cuda.current_stream().cuda_stream
+        _lib.init()
+        allw = torch.empty((3 * B, L), dtype=torch.float32, device=dev)
+        k = min(n, L)
+        allw[:B, :k].copy_(waves[:, :k])                   # what lies past a clip's length is never read below
+        if k < L:
+            allw[:B, k:].zero_()
+        rag = torch.tensor([lens, widths], dtype=torch.int32).to(dev)      # sample counts and mask widths in one small copy
+        T = 1 + L // self.hop
+        X = torch.empty((B, ops.NBIN, T, 2), dtype=torch.float32, device=dev)
+        mag = torch.empty((B, ops.NBIN, T), dtype=torch.float32, device=dev)
+        # X and |X| only, as in the padded call: the masked resynthesis scales X itself
+        _lib.check(lib.advh_stft_forward_ragged(allw.data_ptr(), L, rag[0].data_ptr(), B, L, self.hop, self.win, None, X.data_ptr(),
+                                                mag.data_ptr(), None, T, st), "advh_stft_forward_ragged")
+        spec = torch.view_as_complex(X)
+        W = 4 * (T // 4)
+        mask = self.unet._forward_ragged(mag, 512, W, False, widths, wd=rag[1])
+        rc = lib.advh_istft_masked_c64_ragged(
+            X.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[2], {"linear": 1, "log1p": 2}[self.domain],
+            allw[B:].data_ptr(), allw[2 * B:].data_ptr(), L, rag[0].data_ptr(), B, T, L, self.hop, self.win, None, st)
+        _lib.check(rc, "advh_istft_masked_c64_ragged")
+        _, _, p3 = self.embedder.forward(allw, want_hidden=False, lengths=lens * 3)
+        out = dict(predictions=p3[:B], theta_out=p3[B:2 * B], masked_predictions=p3[2 * B:], mask=mask)
+        if keep:
+            out.update(mag=mag, spec=spec, wave_in=allw[B:2 * B], wave_out=allw[2 * B:])
+        return out
+
+    def explain(self, waves: torch.Tensor, keep: bool = False, lengths=None) -> Dict[str, torch.Tensor]:
+        """``waves [B, n]`` fp32 on the GPU -> clean / mask-in / mask-out probabilities ``[B,1]`` and the mask.
+
+        ``lengths`` (``B`` sample counts in ``[min_length(), L]``): a ragged batch.  Clip ``b`` is ``waves[b, :lengths[b]]`` and gets
+        what it gives when it is explained alone at an audio length of exactly ``lengths[b]`` samples: the STFT reflects at the
+        clip's end, the U-Net sees its ``512 x W_b`` crop, both resyntheses have ``lengths[b]`` samples and the classifier pools
+        over the clip's own frames.  In the returned buffers (``keep=True``: ``spec``, ``mag``, ``wave_in``, ``wave_out``)
+        everything past a clip's extent is exactly 0, as are the mask columns ``>= W_b`` (``frame_counts``).  Runs on one
+        stream (``streams`` is ignored); not available with a vocoder or through ``explain_graphed``."""
+        if lengths is not None:
+            return self._explain_ragged(waves, keep, lengths)
         L = self.L
         B, n = waves.shape
         # X and |X| only: the masked resynthesis scales X itself (advh_istft_masked_c64), so no phase is computed or read

@@ -93,12 +93,13 @@ class HipUNet:
         """fp32-class mode with line tiles: ``d1.block.3`` carries the mask head, ``y1`` has no storage."""
         return self.split and self.line_tile
 
-    def _workspace(self, B: int, H: int, W: int) -> dict:
-        """Maps and launches of one input shape.  With ``fuse_up`` the stages up4+d4 .. up1+d1 are fused launches and the up-sampled
+    def _workspace(self, B: int, H: int, W: int, ragged: bool = False) -> dict:
+        """Maps and launches of one input shape (``ragged``: the set of its own that calls with ``widths`` use, so that a padded
+        call on the same engine finds its indicator channels as it left them).  With ``fuse_up`` the stages up4+d4 .. up1+d1 are fused launches and the up-sampled
         maps u4..u1 do not exist; the coarse maps b2 / y4 / y3 then carry one extra 8-channel chunk whose first channel is the
         in-image indicator (and unused channels up to the next multiple of 64, so every pixel starts on a 128-byte line), and for
         d1 the indicator rides in the 8-channel spectrogram map ``xin`` = (x, 1, 0, ...) that ``advh_unet_pack_x`` fills."""
-        key = (B, H, W)
+        key = (B, H, W, "ragged") if ragged else (B, H, W)
         if key in self._ws:
             return self._ws[key]
         if H % 16 or W % 4:
@@ -173,20 +174,92 @@ class HipUNet:
     def flops(self, B: int, H: int, W: int) -> float:
         return self._workspace(B, H, W)["flops"]
 
-    def forward(self, mag: torch.Tensor, H: int = 512, W: Optional[int] = None, want_logits: bool = False):
-        """``mag``: fp32 CUDA ``[B, Fq, Tq]`` (t fastest); the ``H x W`` crop is read in place."""
+    @staticmethod
+    def _check_widths(widths, B: int, W: int):
+        """``widths`` of a ragged call as a list of ints: one per clip, each a multiple of 4 in ``[4, W]``.  Host only."""
+        import numpy as np
+        if torch.is_tensor(widths):
+            if widths.dim() != 1 or widths.dtype.is_floating_point or widths.dtype.is_complex or widths.dtype == torch.bool:
+                raise ValueError("widths must be a sequence or a 1-D integer tensor with one entry per clip")
+            widths = widths.tolist()
+        elif isinstance(widths, np.ndarray):
+            if widths.ndim != 1 or not np.issubdtype(widths.dtype, np.integer):
+                raise ValueError("widths must be a sequence or a 1-D integer tensor with one entry per clip")
+            widths = widths.tolist()
+        try:
+            widths = list(widths)
+        except TypeError:
+            raise ValueError("widths must be a sequence or a 1-D integer tensor with one entry per clip") from None
+        if len(widths) != B:
+            raise ValueError(f"widths has {len(widths)} entries for a batch of {B} clips")
+        out = []
+        for b, w in enumerate(widths):
+            if isinstance(w, bool) or not isinstance(w, (int, np.integer)):
+                raise ValueError(f"widths[{b}] = {w!r} is not an integer column count")
+            w = int(w)
+            if w < 4 or w > W or w % 4:
+                raise ValueError(f"widths[{b}] = {w}: a clip's mask width is a multiple of 4 in [4, {W}]")
+            out.append(w)
+        return out
+
+    def tail_maps(self, ws: dict, W: int) -> dict:
+        """The feature maps a ragged forward clears past each clip's width, in launch order: ``name -> (map, shift, indicator
+        channel or -1)``.  The stem's output, the packed spectrogram and every step's output that has storage (``y1`` has none when
+        ``d1.block.3`` carries the head); ``shift`` = 0 / 1 / 2 for the full-, half- and quarter-width maps; the indicator is the
+        in-image channel of the maps the fused up-convolutions read (``_workspace``), rewritten on every ragged call."""
+        m = ws["maps"]
+        shift = {W: 0, W // 2: 1, W // 4: 2}                   # W >= 4: the three widths are distinct
+        ind = {"b2": 512, "y4": 256, "y3": 128, "xin": 1} if self.fuse_up else {}
+        names = ["x1a", "xin" if self.fuse_up else "u1"] + [dst for _, _, dst in ws["steps"]]
+        return {n: (m[n], shift[m[n].W], ind.get(n, -1)) for n in names if m[n].t is not None}
+
+    def _clip_tail(self, f: "G.FMap", shift: int, ind: int, widths_p: int, st: int) -> None:
+        lo = f.t.stride(0) if self.split else 0
+        _lib.check(_lib.lib().advh_fmap_clip_tail(f.t.data_ptr(), lo, widths_p, shift, f.B, f.H, f.W, f.C, f.PH, f.PW, ind, st),
+                   "advh_fmap_clip_tail")
+
+    def forward(self, mag: torch.Tensor, H: int = 512, W: Optional[int] = None, want_logits: bool = False, widths=None):
+        """``mag``: fp32 CUDA ``[B, Fq, Tq]`` (t fastest); the ``H x W`` crop is read in place.
+
+        ``widths`` (one multiple of 4 in ``[4, W]`` per clip): a ragged batch.  Clip ``b``'s mask columns ``< widths[b]`` are what
+        the network gives on its ``H x widths[b]`` crop alone; columns behind are exactly 0 in mask and logits.  The existing
+        kernels and plans run over the full ``W``; after the stem, the spectrogram pack and every layer, ``advh_fmap_clip_tail``
+        clears the columns past each clip's width (``widths >> 0 / 1 / 2`` on the full-, half- and quarter-width maps), so a
+        clip's last columns read the zeros its own padding would give, and rewrites the in-image indicator of the fused
+        up-convolutions so the transposed convolution's bias stops at the clip's edge.  ``mag`` is never written and its columns
+        ``>= widths[b]`` are never read for their value: the call works on a private ``H x W`` copy whose tail is zeroed first."""
         if mag.dim() != 3 or mag.dtype != torch.float32 or not mag.is_cuda:
             raise ValueError("mag must be a CUDA fp32 tensor [B, F, T]")
-        mag = mag.contiguous()
         B, Fq, Tq = mag.shape
         W = (Tq // 4) * 4 if W is None else W
         if H > Fq or W > Tq:
             raise ValueError("crop exceeds the spectrogram")
-        ws = self._workspace(B, H, W)
+        if widths is not None:
+            return self._forward_ragged(mag, H, W, want_logits, self._check_widths(widths, B, W))
+        mag = mag.contiguous()
+        return self._forward(mag, H, W, want_logits, self._workspace(B, H, W), None)
+
+    def _forward_ragged(self, mag: torch.Tensor, H: int, W: int, want_logits: bool, widths, wd: Optional[torch.Tensor] = None):
+        """``widths``: the checked list; ``wd``: the same as int32 on the device where the caller has uploaded it already."""
+        B = mag.shape[0]
+        ws = self._workspace(B, H, W, ragged=True)
+        if wd is None:
+            wd = torch.tensor(widths, dtype=torch.int32).to(mag.device)
+        st = torch.cuda.current_stream().cuda_stream
+        priv = mag[:, :H, :W].contiguous()                     # a copy even when the crop is the whole tensor
+        if priv.data_ptr() == mag.data_ptr():
+            priv = priv.clone()
+        _lib.check(_lib.lib().advh_zero_tail_cols_f32(priv.data_ptr(), wd.data_ptr(), B, H, W, st), "advh_zero_tail_cols_f32")
+        return self._forward(priv, H, W, want_logits, ws, wd)
+
+    def _forward(self, mag: torch.Tensor, H: int, W: int, want_logits: bool, ws: dict, wd: Optional[torch.Tensor]):
+        """The launches of one forward; ``wd``: the int32 device widths of a ragged call (``mag`` is then its private copy)."""
+        B, Fq, Tq = mag.shape
         m, lib = ws["maps"], _lib.lib()
         st = torch.cuda.current_stream().cuda_stream
         x1a = m["x1a"]
         xcat, xc0 = (m["xin"], 0) if self.fuse_up else (m["u1"], 32)
+        tails = self.tail_maps(ws, W) if wd is not None else {}
         if self.split:
             _lib.check(lib.advh_unet_stem_split(mag.data_ptr(), Fq, Tq, B, H, W, self.stem_w.data_ptr(), self.stem_b.data_ptr(),
                                                 x1a.t.data_ptr(), x1a.t.stride(0), x1a.PH, x1a.PW, SLOPE, st), "advh_unet_stem_split")
@@ -197,10 +270,15 @@ class HipUNet:
                                           x1a.t.data_ptr(), x1a.PH, x1a.PW, SLOPE, st), "advh_unet_stem")
             _lib.check(lib.advh_unet_pack_x(mag.data_ptr(), Fq, Tq, B, H, W, xcat.t.data_ptr(), xcat.C, xc0, xcat.PH, xcat.PW, st),
                        "advh_unet_pack_x")
+        if wd is not None:
+            self._clip_tail(*tails["x1a"], wd.data_ptr(), st)
+            self._clip_tail(*tails["xin" if self.fuse_up else "u1"], wd.data_ptr(), st)
         for plan, srcs, dst in ws["steps"]:
             a0 = m[srcs[0]].t
             a1 = m[srcs[1]].t if len(srcs) > 1 else None
             plan.run(a0, a1, out_h=m[dst].t)
+            if dst in tails:
+                self._clip_tail(*tails[dst], wd.data_ptr(), st)
         y1 = m["y1"]
         if self._fused_head:
             pass                                               # mask and logits came out of d1.block.3's epilogue
@@ -210,5 +288,8 @@ class HipUNet:
         else:
             _lib.check(lib.advh_unet_head(y1.t.data_ptr(), B, H, W, y1.PH, y1.PW, self.head_w.data_ptr(), self.head_b,
                                           ws["mask"].data_ptr(), ws["logits"].data_ptr(), st), "advh_unet_head")
+        if wd is not None:
+            for plane in (ws["mask"], ws["logits"]):
+                _lib.check(lib.advh_zero_tail_cols_f32(plane.data_ptr(), wd.data_ptr(), B, H, W, st), "advh_zero_tail_cols_f32")
         mask = ws["mask"].clone()
         return (mask, ws["logits"].clone()) if want_logits else mask

@@ -8,6 +8,8 @@ int advh_init_rest();
 int advh_init_attention();   // attention.hip
 int advh_init_attention_ragged();   // attention_ragged.hip
 int advh_init_attention_long();   // attention_long.hip
+int advh_init_stft_ragged();   // stft_ragged.hip: its own twiddle table and LDS limits
+int advh_stft_ragged_set_fb(int fb);   // stft_ragged.hip follows advh_set_option("stft_frames_per_workgroup")
 // per-translation-unit setters of the split-format range flag pointer (csrc/device_math.h: ADVH_SPLIT_FLAG_SETTER)
 int advh_split_flag_attention(int* flag);
 int advh_split_flag_attention_ragged(int* flag);

@@ -501,7 +501,7 @@ extern "C" int advh_set_option(const char* name, int value) {
     if (!strcmp(name, "stft_frames_per_workgroup")) {
         if (value != 8 && value != 16) return ADVH_EINVAL;
         g_stft_fb = value;
-        return ADVH_OK;
+        return advh_stft_ragged_set_fb(value);
     }
     if (!strcmp(name, "attention_bwd_mfma_f32")) {          // 1: head dims <= 64 on the fp32 matrix instruction too (the pre-x3 kernel; A/B runs)
         g_att_bwd_force_f32 = value != 0;
@@ -539,6 +539,8 @@ extern "C" int advh_init(void) {
     rc = advh_init_attention_ragged();
     if (rc != ADVH_OK) return rc;
     rc = advh_init_attention_long();
+    if (rc != ADVH_OK) return rc;
+    rc = advh_init_stft_ragged();
     if (rc != ADVH_OK) return rc;
     // the split format's sticky range flag: ONE host-mapped word per process, written by the kernels of every device
     if (!g_split_flag_host) {
